@@ -64,7 +64,13 @@ def parse() -> argparse.Namespace:
     ap.add_argument("--cpu-baseline-only", action="store_true", help="(internal) measure the CPU oracle and print its JSON")
     ap.add_argument("--profile-steps", type=int, default=2)
     ap.add_argument("--eval-steps", type=int, default=10, help="f32 eval-mode forward passes timed after the train steps (0: skip)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, logits, updated parameters, "
+                         "gradients, BatchNorm / bias buffers) as DIR/<name>.npy in float32, at most 64 MB in all")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def usable_cores() -> int:
@@ -221,6 +227,48 @@ def extra_model_line(name: str, args) -> dict:
         return {"value": None, "note": "did not finish within 300 s"}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+# elements per array (float32); 4 B x their sum plus the .npy headers stays under DUMP_BUDGET_BYTES
+DUMP_CAPS = {"loss": 1, "logits": 1 << 19, "params": 7 << 20, "grads": 7 << 20, "buffers": 1 << 20}
+
+
+def dump_outputs(out_dir: str, model: torch.nn.Module, loss: torch.Tensor, logits: torch.Tensor | None) -> dict:
+    """--dump-outputs: what the last timed step computed, as out_dir/<name>.npy (float32).  params / grads are every
+    parameter and its gradient flattened in named_parameters() order, buffers every floating-point state_dict() buffer
+    (BatchNorm running statistics, attention bias tables).  An array longer than its DUMP_CAPS entry is replaced by a
+    fixed sample of its elements (randperm seeded with 0, sorted): the same positions in every run of the same model, so
+    two builds can be compared element for element.  logits is absent where the step does not expose them (N > 1 split)."""
+    import numpy as np
+
+    def flat(ts: list[torch.Tensor]) -> torch.Tensor:
+        return torch.cat([t.detach().reshape(-1).float() for t in ts]) if ts else torch.zeros(0)
+
+    def sample(v: torch.Tensor, cap: int) -> torch.Tensor:
+        if v.numel() <= cap:
+            return v
+        idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values
+        return v[idx.to(v.device)]
+
+    params = [p for _, p in model.named_parameters()]
+    param_names = {n for n, _ in model.named_parameters()}
+    arrays = {"loss": loss.detach().float().reshape(1),
+              "params": flat(params),
+              "grads": flat([p.grad if p.grad is not None else torch.zeros_like(p) for p in params]),
+              "buffers": flat([b for n, b in model.state_dict().items() if n not in param_names and b.is_floating_point()])}
+    if logits is not None:                     # [batch, classes] as the caller sees them, unless over the cap
+        arrays["logits"] = logits.detach().float() if logits.numel() <= DUMP_CAPS["logits"] else flat([logits])
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    written = {}
+    for name, v in arrays.items():
+        a = sample(v, DUMP_CAPS[name])
+        np.save(out / f"{name}.npy", a.cpu().numpy().astype(np.float32))
+        written[name] = {"shape": list(a.shape), "of": int(v.numel())}
+    total = sum((out / f"{n}.npy").stat().st_size for n in written)
+    assert total <= DUMP_BUDGET_BYTES, f"--dump-outputs wrote {total} bytes (budget {DUMP_BUDGET_BYTES})"
+    return written
+
+
 def progress(msg: str) -> None:
     print(f"[bench] {msg}", file=sys.stderr, flush=True)
 
@@ -266,6 +314,7 @@ def main() -> None:
     x = torch.randn(args.batch, 3, args.size, args.size, generator=g).to(device).contiguous(memory_format=torch.channels_last)
     y = torch.randint(0, args.classes, (args.batch,), generator=g).to(device)
     loss_box: list[torch.Tensor] = [torch.zeros((), device=device)]
+    logits_box: list[torch.Tensor | None] = [None]      # for --dump-outputs (inside a captured graph: the replays' buffer)
 
     overlap = reducer is not None and args.dp_mode == "overlap"
     if overlap:
@@ -274,11 +323,13 @@ def main() -> None:
     def fwd_bwd() -> None:
         opt.zero_grad(set_to_none=True)
         with torch.autocast("cuda", dtype=torch.bfloat16):
-            loss = crit(model(x), y)
+            logits = model(x)
+            loss = crit(logits, y)
         if overlap:
             reducer.arm()
         loss.backward()
         loss_box[0] = loss.detach()
+        logits_box[0] = logits.detach()
 
     def fwd_bwd_plain() -> None:           # the same without arming the hooks (profiling on one rank)
         opt.zero_grad(set_to_none=True)
@@ -334,6 +385,7 @@ def main() -> None:
                 from deepfakedetection_amd.graph_step import GraphedTrainStep
 
                 stepper = GraphedTrainStep(model, crit, opt, accum_steps=1, use_amp=True, eager_cycles=1, reducer=reducer)
+                logits_box[0] = None        # its steps do not go through fwd_bwd: the warm-up's logits would be stale
                 for _ in range(3):          # eager cycle, first sight of the shape, capture + first replay
                     loss_box[0] = stepper.micro_batch(x, y, first=True, last=True)
                     stepper.optimizer_step()
@@ -388,6 +440,11 @@ def main() -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     final_loss = float(loss_box[0])
+    if rank == 0 and args.dump_outputs:
+        # before the eval and per-kernel passes below, which run further steps on the same model
+        written = dump_outputs(args.dump_outputs, model, loss_box[0], logits_box[0])
+        progress(f"last timed step's outputs in {args.dump_outputs}: " +
+                 ", ".join(f"{n} {w['shape']} of {w['of']}" for n, w in written.items()))
 
     # evaluate()'s forward (reference trainers/efficientnet.py:237-262: eval mode, f32, no autocast), same batch
     eval_ips = None

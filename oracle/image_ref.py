@@ -1,6 +1,6 @@
 """CPU restatement (numpy, integer / IEEE arithmetic spelled out) of the PIL transforms between the crop and ToTensor in the
 reference's DEFAULT 224-pixel training pipeline — RandomRotation(10) and ColorJitter(0.2, 0.2, 0.2, 0.05),
-/root/reference/trainers/efficientnet.py:173-181 (same in trainers/efficientformer_v2.py and trainers/fastervit.py) — as
+the reference's trainers/efficientnet.py:173-181 (same in trainers/efficientformer_v2.py and trainers/fastervit.py) — as
 deepfakedetection_amd/data.py performs them with Pillow (RandomRotation.__call__, ColorJitter.__call__, _shift_hue).
 
 TEST INFRASTRUCTURE: only tests/ may import this module.  It is the oracle of csrc/dfd_augment.hip.

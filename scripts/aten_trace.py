@@ -1,5 +1,6 @@
 import sys, collections, torch
-sys.path.insert(0, "/root/repo")
+from pathlib import Path
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from torch.utils._python_dispatch import TorchDispatchMode
 from deepfakedetection_amd.efficientnet import HipEfficientNet
 from deepfakedetection_amd.optim import HipAdamW, HipCrossEntropyLoss

@@ -1,6 +1,7 @@
 """Inference forward of EfficientNet-B0 over batch sizes, eager and as a replayed hipGraph: python eval_small.py [f32|bf16]."""
 import contextlib, sys, time, torch
-sys.path.insert(0, "/root/repo")
+from pathlib import Path
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from deepfakedetection_amd.efficientnet import HipEfficientNet
 amp = len(sys.argv) > 1 and sys.argv[1] == "bf16"
 cast = (lambda: torch.autocast("cuda", dtype=torch.bfloat16)) if amp else contextlib.nullcontext

@@ -1,5 +1,6 @@
 import sys, torch
-sys.path.insert(0, "/root/repo")
+from pathlib import Path
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from deepfakedetection_amd import kernels as K
 from deepfakedetection_amd._lib import ACT_SILU
 from deepfakedetection_amd.arch import efficientnet_plan

@@ -4,7 +4,7 @@ set -e
 TAG=$1; shift
 OUT=$PWD/gpurun_out/pmc_lds_$TAG
 mkdir -p "$OUT"
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$OUT" -o g -- python3 $REPO/scripts/"$@" > "$OUT/run.log" 2> "$OUT/run.err"
 cd "$REPO"

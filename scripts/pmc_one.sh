@@ -4,7 +4,7 @@ set -e
 OP=$1; BLK=$2; TAG=${3:-pmc}
 OUT=$PWD/gpurun_out/pmc_$TAG
 mkdir -p "$OUT"
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 i=0
 for grp in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE" \

@@ -4,7 +4,7 @@ set -e
 TAG=${1:-x}
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o b0 -- python3 $REPO/bench.py --steps 10 --warmup 2 --no-cpu-baseline --profile-steps 0 --eval-steps 0 ${@:2} > "$OUT/b0.json" 2> "$OUT/b0.err"
 find "$OUT" -name "*kernel_trace.csv" -delete

@@ -2,7 +2,7 @@
 # rocprofv3 kernel statistics of the B0 inference forward, both kernel chains and both dtypes:
 #   bash scripts/profile_eval.sh  ->  gpurun_out/prof_eval_<form>_<dtype>/table.txt
 set -e
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 for FORM in 1 0; do
   for DT in f32 bf16; do

@@ -8,7 +8,7 @@ TAG=${1:-r02}
 shift || true
 OUT=$PWD/gpurun_out/pmc_$TAG
 mkdir -p "$OUT"
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 ARGS="--steps 2 --warmup 1 --no-cpu-baseline --no-graph --profile-steps 0 --eval-steps 0 --extra-models none $*"
 run() { name=$1; shift; rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d "$OUT" -o $name -- python3 $REPO/bench.py $ARGS > "$OUT/$name.json" 2> "$OUT/$name.err"; echo "pass $name done"; }

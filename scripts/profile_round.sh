@@ -5,8 +5,8 @@ set -e
 TAG=${1:-r02}
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
 COMMON="--steps 10 --warmup 2 --no-cpu-baseline --profile-steps 0 --eval-steps 0 --extra-models none"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o b0 -- python3 $REPO/bench.py $COMMON > "$OUT/b0.json" 2> "$OUT/b0.err"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o ef -- python3 $REPO/bench.py --model efficientformerv2_s1 $COMMON > "$OUT/ef.json" 2> "$OUT/ef.err"

@@ -1,7 +1,7 @@
-"""Writes the committed golden fixtures.  Run from the repo root IN THE BUILD CONTAINER
-(it reads /root/reference, which never travels to the GPU box):
+"""Writes the committed golden fixtures.  Run from the repo root with a checkout of the reference
+(thourihan/DeepfakeDetection); the tests only read what this writes, never the reference itself:
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py PATH_TO_REFERENCE_CHECKOUT
 
 Outputs
   tests/golden/reference_contract.json  — values produced by IMPORTING the reference's own
@@ -26,7 +26,7 @@ import torch
 import yaml
 
 ROOT = Path(__file__).resolve().parents[2]
-REF = Path("/root/reference")
+REF = Path(sys.argv[1]) if len(sys.argv) == 2 else None        # the reference checkout (see above)
 OUT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT))
 
@@ -129,6 +129,8 @@ def vit_logits() -> dict:
 
 
 if __name__ == "__main__":
+    if REF is None:
+        raise SystemExit("usage: python tests/golden/make_golden.py PATH_TO_REFERENCE_CHECKOUT")
     (OUT / "reference_contract.json").write_text(json.dumps(reference_contract(), indent=1, sort_keys=True))
     (OUT / "effnet_logits.json").write_text(json.dumps(oracle_logits(), indent=1))
     (OUT / "vit_logits.json").write_text(json.dumps(vit_logits(), indent=1))

@@ -1,6 +1,6 @@
 """The plug-in surface (YAML schema, env-var contract, registry, checkpoints) against values
 captured from the REFERENCE's own modules (tests/golden/reference_contract.json, written by
-tests/golden/make_golden.py importing /root/reference/orchestration/{config_schema,train_env}.py)
+tests/golden/make_golden.py importing the reference's orchestration/{config_schema,train_env}.py)
 and against the contract table of SURVEY.md App. A.  CPU only.
 """
 

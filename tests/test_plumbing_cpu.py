@@ -277,7 +277,7 @@ def test_rccl_log_summary_never_raises_and_picks_the_decisions(tmp_path):
 
 def test_default_224_training_pipeline_qualifies_for_the_device_path(monkeypatch):
     """the reference's default toggles at 224 pixels switch rotation AND colour jitter on
-    (/root/reference/trainers/efficientnet.py:134-135); with training.gpu_resize the whole training pipeline must still move to the
+    (reference trainers/efficientnet.py:134-135); with training.gpu_resize the whole training pipeline must still move to the
     device (workers decode + plan only, GpuInputTail rotates / jitters), and fall back to PIL for pictures too large for the kernel."""
     from deepfakedetection_amd import data as D
     from deepfakedetection_amd.trainers.efficientnet import build_transforms
