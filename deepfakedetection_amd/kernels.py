@@ -1174,6 +1174,43 @@ def softmax_argmax(logits: torch.Tensor, want_probs: bool = True):
     return probs, preds
 
 
+# ------------------------------------------------------------------ Grad-CAM (ABI 136)
+def gradcam_map(act: torch.Tensor, grad: torch.Tensor) -> torch.Tensor:
+    """Target-layer activation and its gradient, NHWC [N, h, w, C] (f32 or bf16) -> the ReLU'd Grad-CAM map f32 [N, h, w]:
+    max(0, sum_c mean_hw(grad) * act)."""
+    if act.dim() != 4 or act.shape != grad.shape or act.dtype != grad.dtype:
+        raise ValueError(f"gradcam_map: act {tuple(act.shape)} {act.dtype} and grad {tuple(grad.shape)} {grad.dtype} must be equal NHWC")
+    N, h, w, C = act.shape
+    cam = torch.empty((N, h, w), dtype=torch.float32, device=act.device)
+    check(_L().dfd_gradcam_map(_p(act), _p(grad), _dt(act), N, h * w, C, _p(cam), _stream()), "dfd_gradcam_map",
+          f"{tuple(act.shape)}")
+    return cam
+
+
+def cam_render(cam: torch.Tensor, size: tuple[int, int], image: torch.Tensor | None = None, mean_std: torch.Tensor | None = None,
+               lut: torch.Tensor | None = None, image_weight: float = 0.5) -> tuple[torch.Tensor, torch.Tensor | None]:
+    """Low-resolution map f32 [N, h, w] -> (heatmap f32 [N, H, W], overlay uint8 [N, H, W, 3] or None).  The overlay is drawn
+    when `image` (the normalised model input, f32 [N, 3, H, W]), `mean_std` (f32 [6] on the device) and `lut` (uint8 [256, 3])
+    are given."""
+    N, h, w = cam.shape
+    H, W = size
+    heat = torch.empty((N, H, W), dtype=torch.float32, device=cam.device)
+    overlay = None
+    if image is not None:
+        if image.dtype != torch.float32 or tuple(image.shape) != (N, 3, H, W):
+            raise ValueError(f"cam_render: image must be f32 [{N}, 3, {H}, {W}], got {tuple(image.shape)} {image.dtype}")
+        if lut is None or mean_std is None or lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3) or mean_std.numel() != 6:
+            raise ValueError("cam_render: an overlay needs a uint8 [256, 3] lut and f32 [6] mean_std")
+        image = image.contiguous()
+        overlay = torch.empty((N, H, W, 3), dtype=torch.uint8, device=cam.device)
+    ws_bytes = _L().dfd_cam_render_ws(N, h, w, H, W)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=cam.device)
+    check(_L().dfd_cam_render(_p(cam), N, h, w, H, W, _p(image), _p(mean_std if image is not None else None),
+                              _p(lut if image is not None else None), float(image_weight), _p(heat), _p(overlay), _p(ws), ws_bytes,
+                              _stream()), "dfd_cam_render", f"{N}x{h}x{w} -> {H}x{W}")
+    return heat, overlay
+
+
 def adamw_step(table: torch.Tensor, hp: torch.Tensor) -> None:
     check(_L().dfd_adamw_step(_p(table), table.shape[0], _p(hp), _stream()), "dfd_adamw_step")
 

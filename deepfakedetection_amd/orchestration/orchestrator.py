@@ -311,6 +311,60 @@ def class_probabilities(model: nn.Module, images: torch.Tensor, device: torch.de
     return probs, preds
 
 
+def cam_limit(infer_cfg: dict[str, Any]) -> int | None:
+    """Extra key `inference.cam`: Grad-CAM overlays of the first `limit` images of the split after the metrics pass.
+    `{limit: 64}` / `{limit: all}` / `true` (all) / an integer; absent, `false`, `{enabled: false}` or a limit of 0: off (None)."""
+    raw = infer_cfg.get("cam")
+    if isinstance(raw, dict):
+        if not as_bool(raw.get("enabled", True)):
+            return None
+        raw = raw.get("limit", "all")
+    if raw is None or raw is False:
+        return None
+    if raw is True or str(raw).strip().lower() in ("all", "true", "yes", "on"):
+        return sys.maxsize
+    if str(raw).strip().lower() in ("", "false", "no", "off"):
+        return None
+    limit = int(raw)
+    return limit if limit > 0 else None
+
+
+def write_cam_overlays(model: nn.Module, dataset, probs: torch.Tensor, preds: torch.Tensor, limit: int, cam_dir: Path, *,
+                       batch_size: int, num_workers: int) -> int:
+    """Grad-CAM overlays (deepfakedetection_amd.cam) of the first `limit` images of `dataset`, each explaining the class the
+    metrics pass predicted: <cam_dir>/<true_class>/<stem>__pred-<class>_<prob>.png plus one line per image in
+    <cam_dir>/index.jsonl.  Returns the number of images written."""
+    from PIL import Image
+
+    from ..cam import GradCam
+
+    n = min(limit, len(dataset))
+    subset = torch.utils.data.Subset(dataset, range(n))
+    subset.transform = getattr(dataset, "transform", None)           # build_inference_loader picks the collate function by it
+    cam_dir.mkdir(parents=True, exist_ok=True)
+    device = next(model.parameters()).device
+    done = 0
+    with (cam_dir / "index.jsonl").open("w", encoding="utf-8") as index, GradCam(model, batch_size=batch_size) as cam:
+        for images, targets in build_inference_loader(dataset=subset, batch_size=batch_size, num_workers=num_workers):
+            count = int(targets.shape[0])
+            chosen = preds[done:done + count]
+            if isinstance(images, torch.Tensor):
+                images = images.to(device, non_blocking=True)
+            overlays = cam(images, targets=chosen.to(device), overlay=True).overlay.cpu().numpy()
+            for k in range(count):
+                i = done + k
+                path, truth = dataset.samples[i]
+                pred = int(chosen[k])
+                prob = float(probs[i, pred])
+                dest = cam_dir / dataset.classes[truth] / f"{Path(path).stem}__pred-{dataset.classes[pred]}_{prob:.3f}.png"
+                dest.parent.mkdir(parents=True, exist_ok=True)
+                Image.fromarray(overlays[k]).save(dest, format="PNG")
+                index.write(json.dumps({"path": str(path), "truth": dataset.classes[truth], "prediction": dataset.classes[pred],
+                                        "probability": prob, "png": str(dest.relative_to(cam_dir.parent))}) + "\n")
+            done += count
+    return done
+
+
 def best_balanced_accuracy_threshold(scores: np.ndarray, truth: np.ndarray, steps: int = 501) -> float:
     """First threshold on linspace(0,1,steps) that maximises balanced accuracy of
     (scores >= thr); same result as the reference's per-threshold sklearn loop (:533-544)."""
@@ -505,6 +559,14 @@ def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: 
         handle.write(json.dumps(metrics) + "\n")
     extras = " ".join(f"{k}={v:.4f}" for k, v in metrics.items() if isinstance(v, float) and k != "accuracy")
     out.print(f"[bold]Accuracy[/]: {accuracy:.4f} {extras}")
+    limit = cam_limit(infer_cfg)
+    if limit is not None:
+        if device.type != "cuda":
+            out.print("[bold yellow]inference.cam skipped[/]: Grad-CAM runs on the HIP device only")
+        else:
+            count = write_cam_overlays(model, dataset, probs_t, preds_t, limit, run_paths.run_dir / "cam",
+                                       batch_size=batch_size, num_workers=num_workers)
+            out.print(f"[bold]Grad-CAM[/]: {count} overlays in {run_paths.run_dir / 'cam'}")
 
 
 def orchestrate(config_path: Path, *, mode: str) -> None:

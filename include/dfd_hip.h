@@ -79,7 +79,8 @@ typedef void* dfd_stream;          /* a hipStream_t */
  * 132 = dfd_pw_ntd_plan (mid-size 1x1 layers on the LDS-DMA ring kernel; same entry points), tune keys 4-7;
  * 133 = dfd_attn_scores / dfd_attn_apply; 134 = dfd_act_bn_bwd_se, dfd_sum_batch_end_deferred, dfd_sum_passengers_flush / _discard;
  * 135 = dfd_tune keys 8-13 (grids of the vector-unit depthwise kernels — their default changed, so partial-row counts did — and of the
- * tiled weight gradient); immediate partial-row sums of 33..256 rows in one launch (same order, same bits). */
+ * tiled weight gradient); immediate partial-row sums of 33..256 rows in one launch (same order, same bits);
+ * 136 = Grad-CAM: dfd_gradcam_map, dfd_cam_render / dfd_cam_render_ws. */
 int dfd_version(void);
 
 /* Planner knobs (A/B switches and sizes the host-side kernel selection reads).  Process-wide plain ints: set them once at
@@ -682,6 +683,28 @@ typedef struct dfd_relpos_job {
 } dfd_relpos_job;
 int dfd_relpos_bias_fwd_multi(const dfd_relpos_job* jobs, int njobs, dfd_stream stream);
 int dfd_relpos_bias_bwd_multi(const dfd_relpos_job* jobs, int njobs, dfd_stream stream);
+
+/* ---------------------------------------------------------------- Grad-CAM ---
+ * Reference call site web_ui.py:275-282:
+ *     with GradCAM(model=..., target_layers=[target]) as cam:
+ *         grayscale = cam(input_tensor=batch, targets=[ClassifierOutputTarget(cls_idx)])[0]
+ *     overlay = show_cam_on_image(_tensor_to_rgb(tensor), grayscale, use_rgb=True)
+ * pytorch_grad_cam's GradCAM with one target layer and show_cam_on_image with image_weight 0.5, for a whole batch
+ * (csrc/dfd_cam.hip spells the arithmetic out; tests/_cam_ref.py restates it in numpy f32, operation by operation).
+ *
+ * dfd_gradcam_map: act, grad NHWC [N*HW][C] of `dtype` (the target layer's output and its gradient) -> cam_out f32 [N][HW]
+ *   = max(0, sum_c mean_p(grad[n,p,c]) * act[n,p,c]).  1 <= C <= 16384, any C; one launch, fixed summation order.     */
+int dfd_gradcam_map(const void* act, const void* grad, int dtype, int N, int HW, int C, float* cam_out, dfd_stream stream);
+/* dfd_cam_render: cam f32 [N][h][w] (dfd_gradcam_map's output) -> heat_out f32 [N][H][W], min-max scaled, cv2 INTER_LINEAR
+ *   resized, ReLU'd and min-max scaled again; and, unless overlay_out is NULL, overlay_out uint8 [N][H][W][3] =
+ *   uint8(255 * o / max(o)) with o = (1 - image_weight) * lut[uint8(255 heat)] / 255 + image_weight * clamp(x * std + mean, 0, 1).
+ *   image: the normalised model input, f32 NCHW [N][3][H][W]; mean_std f32 [6] (mean[3], std[3]) and lut uint8 [256][3] (RGB)
+ *   in device memory.  image, mean_std and lut may be NULL when overlay_out is.  One launch; the workspace holds the
+ *   horizontal pass (dfd_cam_render_ws bytes, DFD_EWORKSPACE when smaller).                                                */
+int dfd_cam_render(const float* cam, int N, int h, int w, int H, int W, const float* image, const float* mean_std,
+                   const unsigned char* lut, double image_weight, float* heat_out, unsigned char* overlay_out,
+                   void* workspace, size_t ws_bytes, dfd_stream stream);
+size_t dfd_cam_render_ws(int N, int h, int w, int H, int W);
 
 #ifdef __cplusplus
 }
