@@ -100,6 +100,11 @@ void dfd_sum_passengers_take(hipStream_t st, SumJobs* stage1, SumJobs* stage2) {
         g_pass[0].j.n = 0;
     }
 }
+void dfd_sum_passengers_untake(hipStream_t st, const SumJobs* stage1, const SumJobs* stage2) {
+    std::lock_guard<std::mutex> lock(g_pass_mu);
+    if (stage1->n > 0) { g_pass[0].j = *stage1; g_pass[0].st = st; g_pass[1].j.n = 0; }
+    if (stage2->n > 0) { g_pass[1].j = *stage2; g_pass[1].st = st; }
+}
 extern "C" int dfd_sum_passengers_flush(dfd_stream stream) {
     hipStream_t st = (hipStream_t)stream;
     std::lock_guard<std::mutex> lock(g_pass_mu);

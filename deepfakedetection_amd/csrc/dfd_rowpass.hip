@@ -546,6 +546,14 @@ static int act_bn_bwd_t(const void* D, const void* y, const float* gate, const f
     const long rows = (long)N * HW;
     const int P = pick_parts(rows, cm.rpb, pcap);
     *nparts = P;
+    // every way to fail comes BEFORE the passengers are taken: a batch taken by a launch that never runs would be lost (stage 1
+    // moved on to the stage-2 slot unrun, or stage 2 never written)
+    int mode;
+    if (D && gate && dpool) mode = 1;
+    else if (D && !gate && !dpool) mode = 0;
+    else if (!D && !gate && dpool) mode = 2;
+    else return DFD_EINVAL;
+    if (act != DFD_ACT_NONE && act != DFD_ACT_SILU && act != DFD_ACT_RELU && act != DFD_ACT_GELU) return DFD_EUNSUPPORTED;
     SeWgradJob job{nullptr, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, 0};
     SumJobs sum1, sum2;
     dfd_sum_passengers_take(st, &sum1, &sum2);           // slab sums waiting for a launch on this stream (usually none)
@@ -557,11 +565,6 @@ static int act_bn_bwd_t(const void* D, const void* y, const float* gate, const f
     const int extra = (int)((passengers + cm.nvc - 1) / cm.nvc);
     dim3 grid(P + extra, cm.nvc);
     const float invHW = 1.0f / (float)HW;
-    int mode;
-    if (D && gate && dpool) mode = 1;
-    else if (D && !gate && !dpool) mode = 0;
-    else if (!D && !gate && dpool) mode = 2;
-    else return DFD_EINVAL;
 #define LAUNCH_ABB(MODE) \
     hipLaunchKernelGGL((k_act_bn_bwd<T, ACT, MODE>), grid, dim3(DFD_THREADS), 0, st, (const T*)D, (const T*)y, gate, dpool, \
                        bnstate, (T*)dz, rows, HW, C, invHW, cm, partials, P, job, sum1, sum2)
@@ -571,7 +574,11 @@ static int act_bn_bwd_t(const void* D, const void* y, const float* gate, const f
         else LAUNCH_ABB(2);
     });
 #undef LAUNCH_ABB
-    return DFD_CHECK_LAUNCH();
+    if (hipGetLastError() != hipSuccess) {               // nothing ran: the batches wait for the next carrier or the flush
+        dfd_sum_passengers_untake(st, &sum1, &sum2);
+        return DFD_ELAUNCH;
+    }
+    return DFD_OK;
 }
 extern "C" int dfd_act_bn_bwd(int dtype, const void* D, const void* y, const float* gate, const float* dpool,
                               const float* bnstate, int act, void* dz, int N, int HW, int C, float* partials, int pcap,

@@ -53,3 +53,5 @@ __device__ __forceinline__ void sum_multi_body(const SumJobs& J, int stage, int 
 // host side (dfd_dwconv.hip): batches handed over by dfd_sum_batch_end_deferred wait here for a launch on their stream that can carry
 // them; `take` moves the stage-1 batch on to stage 2 and hands out both for this launch (n = 0: nothing)
 void dfd_sum_passengers_take(hipStream_t st, SumJobs* stage1, SumJobs* stage2);
+// and `untake` gives back what `take` handed out, for a launch that failed (the state is as before the take)
+void dfd_sum_passengers_untake(hipStream_t st, const SumJobs* stage1, const SumJobs* stage2);

@@ -130,8 +130,11 @@ class GradAllReducer:
         self.params = [p for p in params if p.requires_grad]
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         # a bucket leaves as soon as its last backward kernel has been launched: weight-gradient sums may not wait for a carrier launch
+        # (one process exchanges nothing: the flag stays; detach() gives back the value found here)
         from . import kernels as _K
-        _K.passenger_sums_enabled = False
+        self._passengers_before = _K.passenger_sums_enabled
+        if self.world > 1:
+            _K.passenger_sums_enabled = False
         self.arena = arena                      # a GradArena (arena.py): flat, copy-free path
         self.bucket_elems = max(1, bucket_bytes // 4)
         # reverse order: the last layers' gradients are ready first in backward
@@ -190,6 +193,9 @@ class GradAllReducer:
         for h in self._hooks:
             h.remove()
         self._hooks = []
+        if self.world > 1:
+            from . import kernels as _K
+            _K.passenger_sums_enabled = self._passengers_before
 
     def _sync_for_gloo(self, t: torch.Tensor) -> None:
         # gloo stages device tensors through the host: hand it finished data (one-GPU rehearsals and tests only;

@@ -187,6 +187,8 @@ class GraphedTrainStep:
     def _give_up(self, exc: Exception) -> None:
         self.failed = True
         torch.cuda.synchronize()
+        # sums parked by the failed capture point at slabs in the graph's pool, and its backward never reached the flush
+        K.drop_passengers()
         if os.environ.get("DFD_GRAPH_DEBUG"):
             import traceback
 

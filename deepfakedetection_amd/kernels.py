@@ -247,6 +247,7 @@ def sum_batch():
             rc = _L().dfd_sum_batch_end_deferred()
             with _passenger_lock:
                 _passenger_keep.extend(_sum_batch.keep)     # (captured runs: the slabs live until the flush)
+            deferred_ends[0] += 1
             _sum_batch.gen = (_sum_batch.gen + 1) % 3
         else:
             rc = _L().dfd_sum_batch_end()
@@ -261,27 +262,44 @@ PASSENGER_SUMS = os.environ.get("DFD_PASSENGER_SUMS", "1") != "0"
 passenger_sums_enabled = True
 _passenger_lock = threading.Lock()
 _passenger_keep: list = []
-_passenger_flush_registered = False
+# the autograd graph task (torch._C._current_graph_task_id) whose end-of-backward callback will flush what is parked; None: no flush is
+# queued.  A backward that dies in an exception never runs its callbacks, so a bool set here and cleared by the flush would stay set and
+# every later backward would park its last batches without a flush: keyed by the task, the next backward sees a different id
+_passenger_task: int | None = None
+deferred_ends = [0]                                 # batches handed to dfd_sum_batch_end_deferred (a counter for tests)
 
 
 def flush_passengers() -> None:
     """Launch every sum that still waits for a carrier on the current stream (the end of a backward pass; also safe to call at any
     time on the stream the backward ran on)."""
-    global _passenger_flush_registered
+    global _passenger_task
     with _passenger_lock:
-        _passenger_flush_registered = False
+        _passenger_task = None
         keep = list(_passenger_keep)
         _passenger_keep.clear()
     check(_L().dfd_sum_passengers_flush(_stream()), "dfd_sum_passengers_flush")
     del keep
 
 
+def drop_passengers() -> None:
+    """Forget every parked sum and its workspaces without launching anything (a backward pass or a capture that failed: the parked jobs
+    point at memory that may no longer be theirs)."""
+    global _passenger_task
+    with _passenger_lock:
+        check(_L().dfd_sum_passengers_discard(), "dfd_sum_passengers_discard")
+        _passenger_keep.clear()
+        _passenger_task = None
+
+
 def _register_backward_flush() -> bool:
     """flush_passengers as an end-of-backward callback of the autograd engine, once per backward pass; False outside of one (the caller
     then sums at once)."""
-    global _passenger_flush_registered
+    global _passenger_task
+    task = torch._C._current_graph_task_id()
+    if task < 0:
+        return False
     with _passenger_lock:
-        if _passenger_flush_registered:
+        if _passenger_task == task:
             return True
     try:
         torch.autograd.Variable._execution_engine.queue_callback(flush_passengers)
@@ -289,10 +307,10 @@ def _register_backward_flush() -> bool:
         return False
     # the first batch of this backward pass: nothing may be waiting (the previous pass flushed); after a pass that died in an exception
     # something is — drop it, its workspaces may be gone
-    check(_L().dfd_sum_passengers_discard(), "dfd_sum_passengers_discard")
     with _passenger_lock:
+        check(_L().dfd_sum_passengers_discard(), "dfd_sum_passengers_discard")
         _passenger_keep.clear()
-        _passenger_flush_registered = True
+        _passenger_task = task
     return True
 
 
@@ -453,6 +471,8 @@ def act_bn_bwd(D: torch.Tensor | None, y: torch.Tensor, gate: torch.Tensor | Non
     workgroups of this launch (dfd_act_bn_bwd_se) instead of being a launch of their own."""
     _chk_nhwc(y)
     N, H, W, C = y.shape
+    if _passenger_task is not None and torch._C._current_graph_task_id() != _passenger_task:
+        drop_passengers()               # parked by a backward pass that never reached its flush: this launch must not carry them
     dz = torch.empty_like(y)
     parts = partials_buf(y.device, C)
     n = ctypes.c_int(0)

@@ -130,11 +130,12 @@ int dfd_sum_batch_end(void);
  * the optimizer only, so they need not sit on the backward pass's dependency chain), and dfd_sum_passengers_flush(stream) launches whatever
  * is still waiting.  Contract on top of _end()'s: the workspaces stay untouched, and dw is valid, only after the SECOND carrying launch
  * or the flush — callers keep three generations of workspaces and flush at the end of the backward pass (kernels.sum_batch).  A batch that
- * finds the previous one still waiting launches that one at once.  Process-wide state keyed by the stream.                          */
+ * finds the previous one still waiting launches that one at once.  Process-wide state keyed by the stream.  A carrying call that
+ * returns an error carries nothing: the waiting batches stay as they were.                                                              */
 int dfd_sum_batch_end_deferred(void);
 int dfd_sum_passengers_flush(dfd_stream stream);
-/* drops every waiting batch without launching it (the first batch of a backward pass calls it: after a pass that ended in an exception
- * the waiting jobs point at memory the next pass may no longer own) */
+/* drops every waiting batch without launching it (a new backward pass calls it before anything carries: after a pass that ended in an
+ * exception the waiting jobs point at memory the next pass may no longer own) */
 int dfd_sum_passengers_discard(void);
 
 /* ---------------------------------------------------------------- BatchNorm ---

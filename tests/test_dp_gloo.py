@@ -26,6 +26,16 @@ def _worker(rank: int, world: int, port: int, out_dir: str) -> None:
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
+        # an exchanging reducer keeps every weight-gradient sum on the backward's own launches while it is attached, no longer
+        from deepfakedetection_amd import kernels as K
+
+        assert K.passenger_sums_enabled
+        probe = GradAllReducer([torch.nn.Parameter(torch.ones(2))])
+        probe.attach()
+        assert not K.passenger_sums_enabled, "passenger sums left on under data parallelism"
+        probe.detach()
+        assert K.passenger_sums_enabled, "passenger sums not restored by detach()"
+
         torch.manual_seed(100 + rank)                       # different init per rank on purpose
         model = torch.nn.Sequential(torch.nn.Linear(7, 5), torch.nn.BatchNorm1d(5), torch.nn.Linear(5, 3))
         broadcast_module_state(model)
@@ -172,11 +182,19 @@ def test_sharded_sampler_properties():
 
 
 def test_single_process_is_a_no_op():
+    from deepfakedetection_amd import kernels as K
+
+    was = K.passenger_sums_enabled
     p = torch.nn.Parameter(torch.ones(3))
     p.grad = torch.full((3,), 2.0)
     red = GradAllReducer([p])
+    # one process exchanges nothing: the weight-gradient sums may keep waiting for their carrier launches
+    assert K.passenger_sums_enabled == was
+    red.attach()
     red.reduce()
+    red.detach()
     assert red.world == 1 and torch.equal(p.grad, torch.full((3,), 2.0))
+    assert K.passenger_sums_enabled == was
     assert all_reduce_counts(1.0, 2.0) == [1.0, 2.0]
 
 
