@@ -942,6 +942,47 @@ extern "C" int dfd_adamw_step(const int64_t* table, int nchunks, const float* hp
 }
 
 // ===========================================================================
+// exponential moving average of the weights (ema.ModelEma): rows {src, dst, count, kind}, one workgroup per chunk
+// ===========================================================================
+// dst + w * (src - dst) as exactly three f32 roundings in this order (no FMA), so that a numpy f32 restatement
+// reproduces it bit for bit.  The library is built with -ffp-contract=off; the pragma also holds under hipcc's default
+// (fast-honor-pragmas), not under an explicit -ffp-contract=fast
+__device__ __forceinline__ float ema_lerp(float d, float s, float w) {
+#pragma clang fp contract(off)
+    const float diff = s - d;
+    const float t = w * diff;
+    return d + t;
+}
+__global__ void __launch_bounds__(DFD_THREADS)
+k_ema(const int64_t* __restrict__ table, const float* __restrict__ wp) {
+    const int64_t* row = table + (long)blockIdx.x * DFD_EMA_TABLE_COLS;
+    const int cnt = (int)row[2];
+    if (row[3] == DFD_EMA_COPY) {                                     // integer buffers: 8-byte words copied unchanged
+        const int64_t* s = reinterpret_cast<const int64_t*>(row[0]);
+        int64_t* d = reinterpret_cast<int64_t*>(row[1]);
+        for (int i = threadIdx.x; i < cnt; i += DFD_THREADS) d[i] = s[i];
+        return;
+    }
+    const float* s = reinterpret_cast<const float*>(row[0]);
+    float* d = reinterpret_cast<float*>(row[1]);
+    const float w = *wp;                                              // device scalar: a replayed graph sees each step's weight
+    const bool vec = ((row[0] | row[1]) & 15) == 0;
+    const int nv = vec ? cnt / 4 : 0;
+    for (int i = threadIdx.x; i < nv; i += DFD_THREADS) {
+        const float4 sq = reinterpret_cast<const float4*>(s)[i];
+        float4 dq = reinterpret_cast<float4*>(d)[i];
+        dq.x = ema_lerp(dq.x, sq.x, w); dq.y = ema_lerp(dq.y, sq.y, w); dq.z = ema_lerp(dq.z, sq.z, w); dq.w = ema_lerp(dq.w, sq.w, w);
+        reinterpret_cast<float4*>(d)[i] = dq;
+    }
+    for (int i = nv * 4 + threadIdx.x; i < cnt; i += DFD_THREADS) d[i] = ema_lerp(d[i], s[i], w);
+}
+extern "C" int dfd_ema_update(const int64_t* table, int nchunks, const float* w, dfd_stream stream) {
+    if (!table || !w || nchunks < 1) return DFD_EINVAL;
+    hipLaunchKernelGGL(k_ema, dim3(nchunks), dim3(DFD_THREADS), 0, (hipStream_t)stream, table, w);
+    return DFD_CHECK_LAUNCH();
+}
+
+// ===========================================================================
 // input tail: uint8 NHWC batch -> [horizontal flip] -> /255 -> (x - mean) / std -> [erase box] -> f32 NHWC
 // (RandomHorizontalFlip, ToTensor, Normalize, RandomErasing(value=0) of trainers/efficientnet.py:111-234,
 //  in that order; the random decisions arrive as per-image parameters).  One thread = one pixel (3 channels).

@@ -9,6 +9,9 @@ them.  `GraphedTrainStep` captures the loop body once per (batch shape, role) an
     [exchange]    data parallel: sum-all-reduce of the flat gradient arena     (RCCL, OUTSIDE of any capture)
     "step"        the fused AdamW launch                                        (hyper-parameters live in device memory:
                                                                                  HipAdamW.prepare_step() runs before each replay)
+                  [+ the EMA update]                                            (`ema`, ema.ModelEma: its weight lives in device
+                                                                                 memory too; ModelEma.prepare() runs beside
+                                                                                 prepare_step())
 
 Protocol.  The first `eager_cycles` optimizer cycles run eagerly — they build every lazily created buffer (derived-weight
 caches, optimizer state and pointer tables, the Philox state).  A (shape, role) key is run eagerly the FIRST time it
@@ -117,8 +120,9 @@ class GraphedTrainStep:
     MAX_SHAPES = 4
 
     def __init__(self, model: torch.nn.Module, criterion, opt, *, accum_steps: int = 1, use_amp: bool = True,
-                 eager_cycles: int = 1, reducer=None) -> None:
+                 eager_cycles: int = 1, reducer=None, ema=None) -> None:
         self.model, self.criterion, self.opt = model, criterion, opt
+        self.ema = ema                  # ema.ModelEma: updated once per optimizer cycle, right after AdamW
         self.accum, self.use_amp = max(1, accum_steps), use_amp
         self.graphs: dict = {}          # (x shape, x dtype, y shape, role) -> (graph, static_x, static_y, static_loss, views, guard)
         self.seen: set = set()          # keys that have run eagerly once (every lazily built cache of that shape exists)
@@ -267,24 +271,36 @@ class GraphedTrainStep:
         arena = getattr(self.opt, "arena", None)
         if self.failed or self.cycles_done <= self.eager_cycles or arena is None or not arena.holds_all_grads():
             self.opt.step()                                 # eager (also: gradients outside the arena have no static address)
+            if self.ema is not None:
+                self.ema.step()
             return
         if self.step_graph is None:
+            ema_prepared = False
             try:
                 self.opt.prepare_step()                     # uploads this step's hyper-parameters; the capture reads them
+                if self.ema is not None:
+                    self.ema.prepare()
+                    ema_prepared = True
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 with K.capture_journal() as notes:
                     with torch.cuda.graph(g, pool=self.pool, capture_error_mode="thread_local"):
                         self.opt.step()
+                        if self.ema is not None:
+                            self.ema.update()
                 self.step_graph, self.step_guard = g, K.journal_guard(notes, arena.flat.device)
             except Exception as exc:  # noqa: BLE001
                 self._give_up(exc)
                 self.opt.step()
+                if self.ema is not None:
+                    self.ema.update() if ema_prepared else self.ema.step()
                 return
             self.step_graph.replay()                        # the capture recorded, this executes the step just prepared
             return
         _check_guard(self.step_guard, "optimizer-step graph")
         self.opt.prepare_step()
+        if self.ema is not None:
+            self.ema.prepare()
         self.step_graph.replay()
 
 

@@ -1235,6 +1235,11 @@ def adamw_step(table: torch.Tensor, hp: torch.Tensor) -> None:
     check(_L().dfd_adamw_step(_p(table), table.shape[0], _p(hp), _stream()), "dfd_adamw_step")
 
 
+def ema_update(table: torch.Tensor, w: torch.Tensor) -> None:
+    """One dfd_ema_update launch over a device int64 table [nchunks][EMA_TABLE_COLS]; `w` is the f32 weight in device memory."""
+    check(_L().dfd_ema_update(_p(table), table.shape[0], _p(w), _stream()), "dfd_ema_update")
+
+
 # ------------------------------------------------------------------ token-mixer set (ABI 110)
 def _rows_c(t: torch.Tensor) -> tuple[int, int]:
     C = t.shape[-1]

@@ -163,7 +163,8 @@ _TRAIN_ENV = (("batch_size", "BATCH_SIZE"), ("epochs", "EPOCHS"), ("num_workers"
               ("weight_decay", "WEIGHT_DECAY"), ("accum_steps", "ACCUM_STEPS"), ("warmup_epochs", "WARMUP_EPOCHS"),
               ("early_stop_patience", "EARLY_STOP_PATIENCE"))
 _EXTRA_TRAIN_ENV = (("ft_batch_size", "FT_BATCH_SIZE"), ("pretrained", "PRETRAINED"), ("gpu_input_tail", "GPU_INPUT_TAIL"),
-                    ("graph_step", "GRAPH_STEP"), ("fp8_weights", "FP8_WEIGHTS"), ("gpu_resize", "GPU_RESIZE"))
+                    ("graph_step", "GRAPH_STEP"), ("fp8_weights", "FP8_WEIGHTS"), ("gpu_resize", "GPU_RESIZE"),
+                    ("ema_decay", "EMA_DECAY"), ("ema_warmup", "EMA_WARMUP"), ("ema_eval", "EMA_EVAL"))
 
 
 def _first_set(*values: Any) -> Any:

@@ -196,9 +196,10 @@ def save_latest_checkpoint(env: TrainingEnvironment, *, model: torch.nn.Module, 
     return state
 
 
-def save_best_checkpoint(env: TrainingEnvironment, state: dict[str, Any]) -> None:
+def save_best_checkpoint(env: TrainingEnvironment, state: dict[str, Any], weights_key: str = "model") -> None:
+    """best.ckpt = `state`; the best-weights file = state[weights_key] ("model_ema" when the weight EMA is selected)."""
     torch.save(state, env.best_checkpoint_path)
-    torch.save(state["model"], env.best_weights_path)
+    torch.save(state[weights_key], env.best_weights_path)
 
 
 def maybe_load_checkpoint(env: TrainingEnvironment, *, model: torch.nn.Module, optimizer=None,

@@ -94,9 +94,10 @@ def evaluate(model: nn.Module, dl: DataLoader, device: str, tail=None) -> EvalRe
 def train_one_epoch(model: nn.Module, dl: DataLoader, opt: optim.Optimizer, scaler, criterion: nn.Module, device: str, *,
                     use_cuda_amp: bool, progress: Progress, task: TaskID, accum_steps: int = 1, zero_grad_first: bool = False,
                     reducer: GradAllReducer | None = None, tail=None, label: str = "train", ips_in_extra: bool = False,
-                    stepper=None) -> dict:
+                    stepper=None, ema=None) -> dict:
     """One epoch (efficientformer_v2.py:222-257; fastervit.py:243-300 when accum_steps > 1).  Returns throughput
-    figures for logs/throughput.jsonl."""
+    figures for logs/throughput.jsonl.  `ema` (ema.ModelEma) is updated after every eager optimizer step; a `stepper`
+    updates its own."""
     model.train()
     start = perf_counter()
     if not zero_grad_first:
@@ -127,6 +128,8 @@ def train_one_epoch(model: nn.Module, dl: DataLoader, opt: optim.Optimizer, scal
                     reducer.finish()
                 scaler.step(opt)
                 scaler.update()
+                if ema is not None:
+                    ema.step()
                 if not zero_grad_first:
                     opt.zero_grad(set_to_none=True)
                 pending = 0
@@ -148,6 +151,8 @@ def train_one_epoch(model: nn.Module, dl: DataLoader, opt: optim.Optimizer, scal
                 reducer.finish()
             scaler.step(opt)
             scaler.update()
+            if ema is not None:
+                ema.step()
         opt.zero_grad(set_to_none=True)
     if str(device).startswith("cuda"):
         torch.cuda.synchronize()
@@ -277,9 +282,16 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
         if reducer is not None:
             reducer.attach()
         scheduler = optim.lr_scheduler.CosineAnnealingLR(opt, T_max=max(1, epochs - 1))
-        stepper = _base.make_stepper(model, criterion, opt, accum_steps=accum, use_cuda=use_cuda, world=world, reducer=reducer)
+        # weight EMA ($EMA_DECAY): starts here as a copy of the warmed-up model, or from the checkpoint's model_ema
+        ema_cfg = _base.ema_settings()
+        ema = None if ema_cfg is None else _base.make_model_ema(
+            model, lambda: builder(model_name, num_classes, img_size) if spec.pass_img_size else builder(model_name, num_classes),
+            device, ema_cfg)
+        stepper = _base.make_stepper(model, criterion, opt, accum_steps=accum, use_cuda=use_cuda, world=world, reducer=reducer,
+                                     ema=ema)
         start_epoch = 0
         resume_state = maybe_load_checkpoint(env, model=model, optimizer=opt, scheduler=scheduler)
+        _base.restore_model_ema(ema, resume_state)
         if resume_state is not None:
             start_epoch = int(resume_state.get("epoch", 0))
             best_val_acc = float(resume_state.get("best_val_acc", best_val_acc))
@@ -294,7 +306,7 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
             task = progress.add_task(f"epoch {epoch}", total=len(ft_dl), extra="")
             stats = train_one_epoch(model, ft_dl, opt, scaler, criterion, device, use_cuda_amp=use_cuda, progress=progress, task=task,
                                     accum_steps=accum, zero_grad_first=spec.zero_grad_first, reducer=reducer, tail=train_tail,
-                                    stepper=stepper)
+                                    stepper=stepper, ema=ema)
             log_throughput(env, chief, world, phase="fine-tune", epoch=epoch, model=model_name,
                            batch_size=ft_dl.batch_size, accum_steps=accum, **stats)
             scheduler.step()
@@ -304,17 +316,24 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
                               f"lr={scheduler.get_last_lr()[0]:.2e}")
             else:
                 console.print(f"[bold cyan]epoch {epoch}[/] | val_acc={res.acc:.4f}")
-            improved = res.acc > best_val_acc + 1e-4
+            acc = res.acc
+            if ema is not None:
+                res_ema = evaluate(ema.module, val_dl, device, val_tail)
+                console.print(f"[bold cyan]epoch {epoch} EMA[/] | val_acc={res_ema.acc:.4f} ({res_ema.correct}/{res_ema.total}) | "
+                              f"updates={ema.updates}")
+                if ema_cfg.select:
+                    acc = res_ema.acc
+            improved = acc > best_val_acc + 1e-4
             if improved:
-                best_val_acc, best_epoch, epochs_no_improve = res.acc, epoch, 0
+                best_val_acc, best_epoch, epochs_no_improve = acc, epoch, 0
             else:
                 epochs_no_improve += 1
             if chief:
                 state = save_latest_checkpoint(env, model=model, optimizer=opt, scheduler=scheduler, epoch=epoch,
                                                best_val_acc=best_val_acc, best_epoch=best_epoch,
-                                               extra={"warmup_done": warmup_done})
+                                               extra={"warmup_done": warmup_done, **_base.ema_checkpoint_extra(ema)})
                 if improved:
-                    save_best_checkpoint(env, state)
+                    save_best_checkpoint(env, state, weights_key="model_ema" if ema is not None and ema_cfg.select else "model")
                     console.print(f"[bold green]new best[/] val_acc={best_val_acc:.4f} (epoch {best_epoch}) → saved "
                                   f"{env.best_weights_path.name}")
             if spec.early_stop and not improved and epochs_no_improve >= patience:

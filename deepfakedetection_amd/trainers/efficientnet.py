@@ -296,25 +296,70 @@ def eval_forward(model: nn.Module, device: str):
     return fwd
 
 
-def make_stepper(model: nn.Module, criterion: nn.Module, opt, *, accum_steps: int, use_cuda: bool, world: int, reducer=None):
+def make_stepper(model: nn.Module, criterion: nn.Module, opt, *, accum_steps: int, use_cuda: bool, world: int, reducer=None,
+                 ema=None):
     """hipGraph replay of the loop body ($GRAPH_STEP, YAML training.graph_step; default on) on a HIP device with the
     HIP optimizer; with `world` > 1 the object also drives the gradient exchange (`reducer`): graph(zero_grad + forward +
-    backward) -> all-reduce of the flat gradient arena (RCCL, outside of capture) -> graph(AdamW).  Otherwise None: the
-    loop runs eagerly as the reference's does."""
+    backward) -> all-reduce of the flat gradient arena (RCCL, outside of capture) -> graph(AdamW [+ EMA update]).  Otherwise
+    None: the loop runs eagerly as the reference's does."""
     if not use_cuda or getattr(opt, "arena", None) is None or (world > 1 and reducer is None):
         return None
     if env_str("GRAPH_STEP", "1").lower() in {"0", "false", "no", "off"}:
         return None
     from ..graph_step import GraphedTrainStep
 
-    return GraphedTrainStep(model, criterion, opt, accum_steps=accum_steps, use_amp=True, reducer=reducer)
+    return GraphedTrainStep(model, criterion, opt, accum_steps=accum_steps, use_amp=True, reducer=reducer, ema=ema)
+
+
+@dataclass(frozen=True)
+class EmaSettings:
+    decay: float
+    warmup: bool
+    select: bool            # best epoch / early stopping / best weights follow the EMA model
+
+
+def ema_settings() -> EmaSettings | None:
+    """$EMA_DECAY (YAML training.ema_decay; absent or 0: off), $EMA_WARMUP (default on), $EMA_EVAL (default on)."""
+    decay = env_float("EMA_DECAY", 0.0)
+    if not decay:
+        return None
+    on = lambda name: env_str(name, "1").lower() not in {"0", "false", "no", "off"}     # noqa: E731
+    return EmaSettings(decay=decay, warmup=on("EMA_WARMUP"), select=on("EMA_EVAL"))
+
+
+def make_model_ema(model: nn.Module, build, device: str, settings: EmaSettings):
+    """ema.ModelEma of `model` with a shadow from `build()` (the model's own registry builder) placed like the model."""
+    from ..ema import ModelEma
+
+    if not str(device).startswith("cuda"):
+        raise RuntimeError("the weight EMA (training.ema_decay) runs on a HIP device only (no CPU fallback)")
+    shadow = build()
+    shadow.to(memory_format=torch.channels_last)
+    shadow = shadow.to(device)
+    return ModelEma(model, shadow, decay=settings.decay, warmup=settings.warmup)
+
+
+def restore_model_ema(ema, state: dict | None) -> None:
+    """On resume: the checkpoint's `model_ema` (+ `model_ema_updates`); without one EMA starts over as a copy of the model."""
+    if ema is None or state is None:
+        return
+    if state.get("model_ema") is None:
+        console.print("[bold yellow]⚠️  The checkpoint holds no model_ema[/]; the EMA starts over as a copy of the model")
+        ema.reset()
+        return
+    ema.load_state_dict({"module": state["model_ema"], "updates": int(state.get("model_ema_updates", 0))})
+
+
+def ema_checkpoint_extra(ema) -> dict:
+    return {} if ema is None else {"model_ema": ema.module.state_dict(), "model_ema_updates": ema.updates}
 
 
 def train_one_epoch(model: nn.Module, dl: DataLoader, opt: optim.Optimizer, scaler, criterion: nn.Module, device: str, *,
                     use_cuda_amp: bool, progress: Progress, task: TaskID, accum_steps: int = 1,
-                    reducer: GradAllReducer | None = None, tail=None, stepper=None, stats: dict | None = None) -> float:
+                    reducer: GradAllReducer | None = None, tail=None, stepper=None, stats: dict | None = None, ema=None) -> float:
     """One epoch; returns the mean training loss (reference :265-333).  `stepper` (graph_step.GraphedTrainStep)
-    replays the captured loop body instead of dispatching it; `stats` receives throughput figures."""
+    replays the captured loop body instead of dispatching it (and updates its own `ema`); `stats` receives throughput
+    figures; `ema` (ema.ModelEma) is updated after every eager optimizer step."""
     model.train()
     start = perf_counter()
     opt.zero_grad(set_to_none=True)
@@ -343,6 +388,8 @@ def train_one_epoch(model: nn.Module, dl: DataLoader, opt: optim.Optimizer, scal
                     reducer.finish()
                 scaler.step(opt)
                 scaler.update()
+                if ema is not None:
+                    ema.step()
                 opt.zero_grad(set_to_none=True)
                 pending = 0
         bsz = targets.size(0)
@@ -361,6 +408,8 @@ def train_one_epoch(model: nn.Module, dl: DataLoader, opt: optim.Optimizer, scal
                 reducer.finish()
             scaler.step(opt)
             scaler.update()
+            if ema is not None:
+                ema.step()
         opt.zero_grad(set_to_none=True)
     if stats is not None:
         if str(device).startswith("cuda"):
@@ -518,9 +567,15 @@ def main() -> None:  # noqa: PLR0915
         if reducer is not None:
             reducer.attach()
         scheduler = optim.lr_scheduler.CosineAnnealingLR(opt, T_max=max(1, epochs - 1))
-        stepper = make_stepper(model, criterion, opt, accum_steps=accum_steps, use_cuda=use_cuda, world=world, reducer=reducer)
+        # weight EMA ($EMA_DECAY): starts here as a copy of the warmed-up model, or from the checkpoint's model_ema
+        ema_cfg = ema_settings()
+        ema = None if ema_cfg is None else make_model_ema(
+            model, lambda: get_model_spec(model_name).builder(model_name, num_classes), device, ema_cfg)
+        stepper = make_stepper(model, criterion, opt, accum_steps=accum_steps, use_cuda=use_cuda, world=world, reducer=reducer,
+                               ema=ema)
         start_epoch = 0
         resume_state = maybe_load_checkpoint(env, model=model, optimizer=opt, scheduler=scheduler)
+        restore_model_ema(ema, resume_state)
         if resume_state is not None:
             start_epoch = int(resume_state.get("epoch", 0))
             best_val_acc = float(resume_state.get("best_val_acc", best_val_acc))
@@ -536,24 +591,31 @@ def main() -> None:  # noqa: PLR0915
             stats = {}
             train_loss = train_one_epoch(model, train_dl_ft, opt, scaler, criterion, device, use_cuda_amp=use_cuda,
                                          progress=progress, task=task, accum_steps=accum_steps, reducer=reducer,
-                                         tail=train_tail, stepper=stepper, stats=stats)
+                                         tail=train_tail, stepper=stepper, stats=stats, ema=ema)
             _log_throughput(env, chief, world, phase="fine-tune", epoch=epoch, model=model_name, batch_size=ft_batch,
                             accum_steps=accum_steps, **stats)
             scheduler.step()
             res = evaluate(model, val_dl, device, criterion, val_tail)
             console.print(f"[bold cyan]epoch {epoch}[/] | train_loss={train_loss:.4f} | val_loss={res.loss:.4f} | "
                           f"val_acc={res.acc:.4f} ({res.correct}/{res.total}) | lr={scheduler.get_last_lr()[0]:.2e}")
-            improved = res.acc > best_val_acc + 1e-4
+            acc = res.acc
+            if ema is not None:
+                res_ema = evaluate(ema.module, val_dl, device, criterion, val_tail)
+                console.print(f"[bold cyan]epoch {epoch} EMA[/] | val_loss={res_ema.loss:.4f} | "
+                              f"val_acc={res_ema.acc:.4f} ({res_ema.correct}/{res_ema.total}) | updates={ema.updates}")
+                if ema_cfg.select:
+                    acc = res_ema.acc
+            improved = acc > best_val_acc + 1e-4
             if improved:
-                best_val_acc, best_epoch, epochs_no_improve = res.acc, epoch, 0
+                best_val_acc, best_epoch, epochs_no_improve = acc, epoch, 0
             else:
                 epochs_no_improve += 1
             if chief:
                 state = save_latest_checkpoint(env, model=model, optimizer=opt, scheduler=scheduler, epoch=epoch,
                                                best_val_acc=best_val_acc, best_epoch=best_epoch,
-                                               extra={"warmup_done": warmup_done})
+                                               extra={"warmup_done": warmup_done, **ema_checkpoint_extra(ema)})
                 if improved:
-                    save_best_checkpoint(env, state)
+                    save_best_checkpoint(env, state, weights_key="model_ema" if ema is not None and ema_cfg.select else "model")
                     console.print(f"[bold green]new best[/] val_acc={best_val_acc:.4f} (epoch {best_epoch}) → saved "
                                   f"{env.best_weights_path.name}")
             if not improved and epochs_no_improve >= patience:

@@ -80,7 +80,8 @@ typedef void* dfd_stream;          /* a hipStream_t */
  * 133 = dfd_attn_scores / dfd_attn_apply; 134 = dfd_act_bn_bwd_se, dfd_sum_batch_end_deferred, dfd_sum_passengers_flush / _discard;
  * 135 = dfd_tune keys 8-13 (grids of the vector-unit depthwise kernels — their default changed, so partial-row counts did — and of the
  * tiled weight gradient); immediate partial-row sums of 33..256 rows in one launch (same order, same bits);
- * 136 = Grad-CAM: dfd_gradcam_map, dfd_cam_render / dfd_cam_render_ws. */
+ * 136 = Grad-CAM: dfd_gradcam_map, dfd_cam_render / dfd_cam_render_ws;
+ * 137 = dfd_ema_update (exponential moving average of the weights). */
 int dfd_version(void);
 
 /* Planner knobs (A/B switches and sizes the host-side kernel selection reads).  Process-wide plain ints: set them once at
@@ -467,6 +468,14 @@ int dfd_image_prep(const unsigned char* src, float* dst, int N, int H, int W, co
 #define DFD_ADAMW_TABLE_COLS 5
 #define DFD_ADAMW_HP_LEN 8
 int dfd_adamw_step(const int64_t* table, int nchunks, const float* hp, dfd_stream stream);
+/* Exponential moving average of the weights over a chunk table: int64 rows {src, dst, count, kind}, count <= 4096.
+ * kind DFD_EMA_LERP: f32 dst = dst + w * (src - dst), rounded as d = src - dst, t = w * d, dst + t (no FMA);
+ * kind DFD_EMA_COPY: count 8-byte words copied from src to dst (integer buffers).  w: one f32 in device memory
+ * (so a captured graph sees each step's weight).  NULL table / w or nchunks < 1: DFD_EINVAL before any launch.  */
+#define DFD_EMA_TABLE_COLS 4
+#define DFD_EMA_LERP 0
+#define DFD_EMA_COPY 1
+int dfd_ema_update(const int64_t* table, int nchunks, const float* w, dfd_stream stream);
 
 /* ------------------------------------------------------------ token mixers ---
  * What the EfficientFormerV2 (timm 1.0.20 efficientformer_v2.py: Attention2d, Attention2dDownsample,

@@ -1,10 +1,11 @@
 """Throughput of the drop-in trainer loop (`trainers.efficientnet.train_one_epoch`), eager dispatch vs hipGraph replay.
 
-    python scripts/bench_trainer.py [--model efficientnet_b0] [--steps 60]
+    python scripts/bench_trainer.py [--model efficientnet_b0] [--steps 60] [--ema DECAY] [--cases 32x4,256x1]
 
 Runs the real loop body on synthetic pinned batches (so the loader's H2D copy is in, PIL decode is not) at the
 reference's fine-tune configuration (micro-batch 32 x 4 accumulation steps, trainers/efficientnet.py:84-86) and at
 batch 256 x 1, once with GRAPH_STEP off and once on, and prints one JSON line per case.  Numbers quoted in DESIGN.md.
+--ema DECAY adds the weight EMA (ema.ModelEma, one dfd_ema_update launch per optimizer step) to the loop.
 """
 
 from __future__ import annotations
@@ -44,33 +45,40 @@ def main() -> None:
     ap.add_argument("--model", default="efficientnet_b0")
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--size", type=int, default=224)
+    ap.add_argument("--ema", type=float, default=0.0, help="weight EMA decay (0: off)")
+    ap.add_argument("--cases", default="32x4,256x1", help="micro-batch x accumulation steps, comma separated")
     args = ap.parse_args()
+    from deepfakedetection_amd.ema import ModelEma
     from deepfakedetection_amd.graph_step import GraphedTrainStep
     from deepfakedetection_amd.optim import HipAdamW, HipCrossEntropyLoss
     from deepfakedetection_amd.orchestration.model_registry import get_model_spec
     from deepfakedetection_amd.trainers.efficientnet import train_one_epoch
 
-    for batch, accum in ((32, 4), (256, 1)):
+    cases = [tuple(int(v) for v in c.split("x")) for c in args.cases.split(",")]
+    for batch, accum in cases:
         for graph in (False, True):
             torch.manual_seed(0)
-            model = get_model_spec(args.model).builder(args.model, 2).cuda()
+            build = get_model_spec(args.model).builder
+            model = build(args.model, 2).cuda()
+            ema = ModelEma(model, build(args.model, 2).cuda(), decay=args.ema) if args.ema else None
             opt = HipAdamW(model.parameters(), lr=1e-4, weight_decay=5e-2)
             crit = HipCrossEntropyLoss(0.1)
             scaler = torch.amp.GradScaler(enabled=False)
-            stepper = GraphedTrainStep(model, crit, opt, accum_steps=accum) if graph else None
+            stepper = GraphedTrainStep(model, crit, opt, accum_steps=accum, ema=ema) if graph else None
             steps = args.steps * accum
             with Progress(disable=True) as progress:
                 warm = FakeLoader(batch, args.size, 3 * accum, 2)
                 train_one_epoch(model, warm, opt, scaler, crit, "cuda", use_cuda_amp=True, progress=progress,
-                                task=progress.add_task("w", total=len(warm)), accum_steps=accum, stepper=stepper)
+                                task=progress.add_task("w", total=len(warm)), accum_steps=accum, stepper=stepper, ema=ema)
                 dl = FakeLoader(batch, args.size, steps, 2)
                 stats: dict = {}
                 loss = train_one_epoch(model, dl, opt, scaler, crit, "cuda", use_cuda_amp=True, progress=progress,
-                                       task=progress.add_task("t", total=len(dl)), accum_steps=accum, stepper=stepper, stats=stats)
-            print(json.dumps({"model": args.model, "micro_batch": batch, "accum_steps": accum, "requested": "hipgraph" if graph else "eager",
+                                       task=progress.add_task("t", total=len(dl)), accum_steps=accum, stepper=stepper, stats=stats, ema=ema)
+            print(json.dumps({"model": args.model, "micro_batch": batch, "accum_steps": accum, "ema": args.ema,
+                              "requested": "hipgraph" if graph else "eager",
                               "launch": stats["launch"], "images_per_sec": round(stats["images_per_sec"], 1),
                               "ms_per_micro_batch": round(1e3 * stats["seconds"] / steps, 3), "mean_loss": round(loss, 4)}), flush=True)
-            del model, opt, stepper
+            del model, opt, stepper, ema
             torch.cuda.empty_cache()
 
 
