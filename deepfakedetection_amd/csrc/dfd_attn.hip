@@ -1,4 +1,4 @@
-// dfd_attn.hip — fused window attention on the bf16 matrix cores (FasterViT WindowAttention, head_dim 32, <= 64 tokens:
+// dfd_attn.hip — fused window attention on the bf16 matrix cores (FasterViT-0 WindowAttention, head_dim 32, <= 64 tokens:
 // 49 + 4 carrier tokens in level 2, 49 in level 3, 16 carrier tokens; BASELINE config 5 "hierarchical attention on CDNA4
 // ... MFMA"; the arithmetic of the third-party module's forward at trainers/fastervit.py:271 and backward at :274).
 //
@@ -25,7 +25,7 @@
 #include "dfd_common.h"
 #include "dfd_pw.h"
 
-#define AT_HD 32                 // head dimension (all FasterViT variants)
+#define AT_HD 32                 // head dimension (FasterViT-0; -1/-2/-3 have 40/48/64 and take the bgemm + softmax path)
 #define AT_LDS_ROW 72            // bytes per token row of a staged [token][32] bf16 tile (64 + 8: 8-byte aligned, rows 18 banks apart)
 
 typedef __attribute__((address_space(3))) short4_t lds_short4;

@@ -374,8 +374,14 @@ def variant_of(name: str) -> str:
 
 
 def build_efficientformer_v2(name: str, num_classes: int, img_size: int = 224) -> HipEfficientFormerV2:
-    """'efficientformerv2_s1' (the reference's MODEL_NAME, trainers/efficientformer_v2.py:54) and its siblings s0 / s2 / l."""
-    return HipEfficientFormerV2(variant_of(name), num_classes, img_size)
+    """'efficientformerv2_s1' (the reference's MODEL_NAME, trainers/efficientformer_v2.py:54) and its siblings s0 / s2.
+    EfficientFormerV2-L is refused loudly: its stem's first convolution has 20 output channels (and the second 20 input
+    channels), and the stem and dense-convolution kernels take multiples of 8 only."""
+    variant = variant_of(name)
+    if variant == "l":
+        raise NotImplementedError(f"EfficientFormerV2-L ('{name}') does not run on the HIP kernels: its 20-channel stem is not a "
+                                  "multiple of 8 channels (there is no ATen fallback)")
+    return HipEfficientFormerV2(variant, num_classes, img_size)
 
 
 __all__ = ["HipEfficientFormerV2", "build_efficientformer_v2", "variant_of"]

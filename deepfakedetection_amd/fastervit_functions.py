@@ -202,29 +202,69 @@ class AttnSpec:
     idx: torch.Tensor       # int32 [n_local^2] relative position index
 
 
+def window_attention_fwd(qkv, bias, H: int):
+    """softmax(q k^T * scale + bias) v on qkv [n, T, 1, 3C] (q | k | v per token, read in place) -> (O [n, T, 1, C], saved).
+    The fused MFMA kernel (csrc/dfd_attn.hip) where kernels.wattn_supported (saved = the log-sum-exp rows), else batched
+    GEMM -> softmax rows -> batched GEMM (saved = P, f32 [n, H, T, T])."""
+    n, T, _, C3 = qkv.shape
+    C = C3 // 3
+    hd = C // H
+    if K.wattn_supported(qkv.dtype, T, hd):
+        # fused MFMA attention: S and P stay in registers; the backward recomputes P from L
+        return K.wattn_fwd(qkv, bias, H, hd ** -0.5)
+    S = torch.empty((n, H, T, T), dtype=torch.float32, device=qkv.device)
+    q, k, v = qkv.view(n * T, 3 * C)[:, 0:C], qkv.view(n * T, 3 * C)[:, C:2 * C], qkv.view(n * T, 3 * C)[:, 2 * C:]
+    K.bgemm(q, (T * 3 * C, hd, 3 * C, 1), k, (T * 3 * C, hd, 1, 3 * C), S, (H * T * T, T * T, T, 1), n, H, T, T, hd,
+            alpha=hd ** -0.5, bias=bias)
+    Pm, _ = K.attn_softmax_fwd(S, None)
+    O = torch.empty((n, T, 1, C), dtype=qkv.dtype, device=qkv.device)
+    K.bgemm(Pm, (H * T * T, T * T, T, 1), v, (T * 3 * C, hd, 3 * C, 1), O, (T * C, hd, C, 1), n, H, T, hd, T)
+    return O, Pm
+
+
+def window_attention_bwd(qkv, dO, saved, bias, H: int, need_bias: bool):
+    """-> (dqkv [n, T, 1, 3C], dbias [H*T*T] f32 or None) of window_attention_fwd; dO [n, T, 1, C]."""
+    n, T, _, C3 = qkv.shape
+    C = C3 // 3
+    hd = C // H
+    dev = qkv.device
+    L = T * T
+    if K.wattn_supported(qkv.dtype, T, hd):
+        return K.wattn_bwd(qkv, dO, saved, bias, H, hd ** -0.5, need_bias)            # saved holds the log-sum-exp rows here
+    Pm = saved
+    q, k, v = qkv.view(n * T, 3 * C)[:, 0:C], qkv.view(n * T, 3 * C)[:, C:2 * C], qkv.view(n * T, 3 * C)[:, 2 * C:]
+    dT2 = torch.empty((n, H, T, T), dtype=torch.float32, device=dev)
+    K.bgemm(dO, (T * C, hd, C, 1), v, (T * 3 * C, hd, 1, 3 * C), dT2, (H * L, L, T, 1), n, H, T, T, hd)
+    dqkv = torch.empty_like(qkv)
+    dq, dk, dv = dqkv.view(n * T, 3 * C)[:, 0:C], dqkv.view(n * T, 3 * C)[:, C:2 * C], dqkv.view(n * T, 3 * C)[:, 2 * C:]
+    K.bgemm(Pm, (H * L, L, 1, T), dO, (T * C, hd, C, 1), dv, (T * 3 * C, hd, 3 * C, 1), n, H, T, hd, T)
+    dS_buf = torch.empty((_partial_rows(n), H, T, T), dtype=torch.float32, device=dev)
+    from ._lib import check
+
+    check(K._L().dfd_attn_softmax_bwd(dT2.data_ptr(), Pm.data_ptr(), None, None, None, dS_buf.data_ptr(), n, H, T, T, K._stream()),
+          "dfd_attn_softmax_bwd")
+    dS = dS_buf[:n]
+    scale = hd ** -0.5
+    K.bgemm(dS, (H * L, L, T, 1), k, (T * 3 * C, hd, 3 * C, 1), dq, (T * 3 * C, hd, 3 * C, 1), n, H, T, hd, T, alpha=scale)
+    K.bgemm(dS, (H * L, L, 1, T), q, (T * 3 * C, hd, 3 * C, 1), dk, (T * 3 * C, hd, 3 * C, 1), n, H, T, hd, T, alpha=scale)
+    dfull = None
+    if need_bias:
+        dfull = torch.empty(H * L, dtype=torch.float32, device=dev)
+        K.sum_rows(dS_buf.view(-1), n, H * L, dfull)
+    return dqkv, dfull
+
+
 def attn_sub_fwd(x, P, spec: AttnSpec, ls, row_scale):
     """x + [rs *] [ls *] proj(softmax(q k^T * scale + bias) v) with q, k, v = qkv(LN(x)).
     P: dict of tensors (ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b, bias); bias = the [H, T, T] relative-position bias of
     CoordTablesFunction."""
-    n, T, _, C = x.shape
     H = spec.heads
-    hd = C // H
     dt = x.dtype
     xn, lnst = K.layernorm_fwd(x, P["ln_w"], P["ln_b"], 1e-5)
     wq_nk, wq_kn = _prep(P["qkv_w"], dt)
     qkv, yq, stq = lin_fwd(xn, wq_nk, P["qkv_b"])
     bias_full = P["bias"]
-    if K.wattn_supported(dt, T, hd):
-        # fused MFMA attention (csrc/dfd_attn.hip): S and P stay in registers; the backward recomputes P from L
-        O, Pm = K.wattn_fwd(qkv, bias_full, H, hd ** -0.5)
-    else:
-        S = torch.empty((n, H, T, T), dtype=torch.float32, device=x.device)
-        q, k, v = qkv.view(n * T, 3 * C)[:, 0:C], qkv.view(n * T, 3 * C)[:, C:2 * C], qkv.view(n * T, 3 * C)[:, 2 * C:]
-        K.bgemm(q, (T * 3 * C, hd, 3 * C, 1), k, (T * 3 * C, hd, 1, 3 * C), S, (H * T * T, T * T, T, 1), n, H, T, T, hd,
-                alpha=hd ** -0.5, bias=bias_full)
-        Pm, _ = K.attn_softmax_fwd(S, None)
-        O = torch.empty((n, T, 1, C), dtype=dt, device=x.device)
-        K.bgemm(Pm, (H * T * T, T * T, T, 1), v, (T * 3 * C, hd, 3 * C, 1), O, (T * C, hd, C, 1), n, H, T, hd, T)
+    O, Pm = window_attention_fwd(qkv, bias_full, H)
     wp_nk, wp_kn = _prep(P["proj_w"], dt)
     out, yp, stp = lin_fwd(O, wp_nk, P["proj_b"], ACT_NONE, ls, x, row_scale)
     return out, (x, xn, lnst, qkv, yq, stq, Pm, O, yp, stp, wq_kn, wp_kn, bias_full)
@@ -233,10 +273,8 @@ def attn_sub_fwd(x, P, spec: AttnSpec, ls, row_scale):
 def attn_sub_bwd(g, saved, P, spec: AttnSpec, ls, row_scale, need: dict, need_dx: bool):
     """-> (dx, grads dict).  need: name -> bool for the entries of P and 'ls'."""
     x, xn, lnst, qkv, yq, stq, Pm, O, yp, stp, wq_kn, wp_kn, bias_full = saved
-    n, T, _, C = x.shape
+    T = x.shape[1]
     H = spec.heads
-    hd = C // H
-    dev = x.device
     grads = {}
     upstream = need_dx or any(need[k] for k in ("ln_w", "ln_b", "qkv_w", "qkv_b", "bias"))
     dO, grads["proj_w"], grads["proj_b"], grads["ls"] = lin_bwd(g, O, yp, stp, wp_kn, P["proj_w"], P["proj_b"], ls, ACT_NONE, upstream,
@@ -244,29 +282,7 @@ def attn_sub_bwd(g, saved, P, spec: AttnSpec, ls, row_scale, need: dict, need_dx
     if not upstream:
         return None, grads
     need_cpb = need["bias"]
-    L = T * T
-    if K.wattn_supported(x.dtype, T, hd):
-        dqkv, dfull = K.wattn_bwd(qkv, dO, Pm, bias_full, H, hd ** -0.5, need_cpb)       # Pm holds the log-sum-exp rows here
-    else:
-        q, k, v = qkv.view(n * T, 3 * C)[:, 0:C], qkv.view(n * T, 3 * C)[:, C:2 * C], qkv.view(n * T, 3 * C)[:, 2 * C:]
-        dT2 = torch.empty((n, H, T, T), dtype=torch.float32, device=dev)
-        K.bgemm(dO, (T * C, hd, C, 1), v, (T * 3 * C, hd, 1, 3 * C), dT2, (H * L, L, T, 1), n, H, T, T, hd)
-        dqkv = torch.empty_like(qkv)
-        dq, dk, dv = dqkv.view(n * T, 3 * C)[:, 0:C], dqkv.view(n * T, 3 * C)[:, C:2 * C], dqkv.view(n * T, 3 * C)[:, 2 * C:]
-        K.bgemm(Pm, (H * L, L, 1, T), dO, (T * C, hd, C, 1), dv, (T * 3 * C, hd, 3 * C, 1), n, H, T, hd, T)
-        dS_buf = torch.empty((_partial_rows(n), H, T, T), dtype=torch.float32, device=dev)
-        from ._lib import check
-
-        check(K._L().dfd_attn_softmax_bwd(dT2.data_ptr(), Pm.data_ptr(), None, None, None, dS_buf.data_ptr(), n, H, T, T, K._stream()),
-              "dfd_attn_softmax_bwd")
-        dS = dS_buf[:n]
-        scale = hd ** -0.5
-        K.bgemm(dS, (H * L, L, T, 1), k, (T * 3 * C, hd, 3 * C, 1), dq, (T * 3 * C, hd, 3 * C, 1), n, H, T, hd, T, alpha=scale)
-        K.bgemm(dS, (H * L, L, 1, T), q, (T * 3 * C, hd, 3 * C, 1), dk, (T * 3 * C, hd, 3 * C, 1), n, H, T, hd, T, alpha=scale)
-        dfull = None
-        if need_cpb:
-            dfull = torch.empty(H * L, dtype=torch.float32, device=dev)
-            K.sum_rows(dS_buf.view(-1), n, H * L, dfull)
+    dqkv, dfull = window_attention_bwd(qkv, dO, Pm, bias_full, H, need_cpb)
     if need_cpb:
         grads["bias"] = dfull.view(H, T, T)
     need_xn = need_dx or need["ln_w"] or need["ln_b"]

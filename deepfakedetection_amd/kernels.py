@@ -1384,7 +1384,9 @@ def attn_apply(f: torch.Tensor, x: torch.Tensor, out_shape, H: int, alpha: float
 
 
 def wattn_supported(dtype: torch.dtype, T: int, hd: int) -> bool:
-    """The fused MFMA window attention (csrc/dfd_attn.hip) covers bf16, head_dim 32, at most 64 tokens per window."""
+    """The fused MFMA window attention (csrc/dfd_attn.hip) covers bf16, head_dim 32, at most 64 tokens per window: FasterViT-0
+    under bf16 autocast.  f32, and the head dims 40 / 48 / 64 of FasterViT-1 / -2 / -3, take the batched-GEMM + softmax-rows
+    path of fastervit_functions.window_attention_fwd / _bwd."""
     return dtype == torch.bfloat16 and hd == 32 and 1 <= T <= 64
 
 

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import json
 import os
+import sys
 from pathlib import Path
 
 import pytest
@@ -211,3 +212,61 @@ def test_threshold_sweep_matches_sklearn_loop():
         if bal > best:
             best, chosen = float(bal), float(thr)
     assert orch.best_balanced_accuracy_threshold(scores, truth) == chosen
+
+
+def _parametrized(fn, arg: str) -> set:
+    """The values `fn`'s @pytest.mark.parametrize marks give the argument `arg`."""
+    out = set()
+    for mark in getattr(fn, "pytestmark", []):
+        if mark.name != "parametrize":
+            continue
+        names = [a.strip() for a in mark.args[0].split(",")] if isinstance(mark.args[0], str) else list(mark.args[0])
+        if arg in names:
+            i = names.index(arg)
+            out |= {(v.values if hasattr(v, "values") else v if len(names) > 1 else (v,))[i] for v in mark.args[1]}
+    return out
+
+
+def test_every_registered_variant_runs_in_a_network_level_gpu_test():
+    """Each model name the registry and the builders accept runs, against its oracle, in the variant parametrization of the
+    network-level GPU tests (f32 eval logits and f32 all-parameter train step), so that a variant the engine builds cannot go
+    untested on the GPU again.  CPU only: reads the tests' parametrize marks."""
+    from deepfakedetection_amd import efficientformer_v2 as efv2
+    from deepfakedetection_amd import fastervit as fv
+    from tests import test_efformer_gpu as te_gpu
+    from tests import test_fastervit_gpu as tf_gpu
+    from tests import test_model_gpu as tm_gpu
+
+    names = [f"faster_vit_{v}_224" for v in "0123"] + [f"efficientformerv2_{v}" for v in ("s0", "s1", "s2")] + \
+        ["efficientnet_b0", "efficientnet_b3"]
+    with pytest.raises(NotImplementedError, match="20-channel stem"):           # EfficientFormerV2-L: refused, not half-run
+        reg.get_model_spec("efficientformerv2_l").builder("efficientformerv2_l", 2)
+    assert set(fv._CONFIGS) == set("0123") and set(efv2._WIDTHS) == {"s0", "s1", "s2", "l"}      # nothing built beyond the list
+    assert {n for n in reg._exact if n.startswith("efficientnet")} == {"efficientnet_b0", "efficientnet_b3"}
+    # per family: the checks every variant must meet, each a group of tests whose runs together cover the variants — a test
+    # written for one variant before the others were added is listed with that variant, the rest by their parametrization
+    network_tests = {
+        "faster_vit": (fv.variant_of, [
+            [(tf_gpu.test_eval_logits_f32, "0"), (tf_gpu.test_eval_logits_f32_of_each_variant, None)],
+            [(tf_gpu.test_train_step_f32_all_parameters, "0"), (tf_gpu.test_train_step_f32_all_parameters_of_each_variant, None)],
+            [(tf_gpu.test_hat_block, "0"), (tf_gpu.test_hat_block_of_each_variant, None)],
+            [(tf_gpu.test_conv_block_and_downsample, "0"), (tf_gpu.test_conv_block_and_downsample_of_each_variant, None)]]),
+        "efficientformer": (efv2.variant_of, [
+            [(te_gpu.test_eval_logits_f32, None)],
+            [(te_gpu.test_train_step_f32_all_parameters, "s1"), (te_gpu.test_train_step_f32_all_parameters_of_each_variant, None)]]),
+        "efficientnet": (lambda n: n.rsplit("_", 1)[1], [[(tm_gpu.test_eval_logits_f32, None)], [(tm_gpu.test_train_step_f32, None)]]),
+    }
+    for name in names:
+        spec = reg.get_model_spec(name)
+        assert spec.name == name and spec.default_image_size == 224
+        prefix = next(p for p in network_tests if name.startswith(p))
+        variant_of, checks = network_tests[prefix]
+        variant = variant_of(name)
+        for group in checks:
+            covered = set()
+            for fn, fixed in group:
+                assert sys.modules[fn.__module__].pytestmark.name == "gpu", fn.__module__
+                vals = _parametrized(fn, "variant")
+                assert (fixed is None) == bool(vals), fn.__name__
+                covered |= {fixed} if fixed is not None else vals
+            assert variant in covered, f"{name}: variant {variant!r} is not run by {[fn.__name__ for fn, _ in group]}"

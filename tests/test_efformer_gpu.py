@@ -56,9 +56,10 @@ def randomise(model: torch.nn.Module, seed: int) -> None:
 def make_pair(variant="s1", nc=2, img=224, seed=0):
     Hip, Ref, _, _ = _imports()
     torch.manual_seed(seed)
-    ref = Ref(variant, nc, img)
+    # S2 / L train with DropPath (0.02 / 0.1): off on both sides, the masks come from different generators (S0 / S1 have none)
+    ref = Ref(variant, nc, img, drop_path_rate=0.0)
     randomise(ref, seed + 1)
-    hip = Hip(variant, nc, img)
+    hip = Hip(variant, nc, img, drop_path_rate=0.0)
     hip.load_state_dict(ref.state_dict(), strict=True)
     return ref, hip.cuda()
 
@@ -102,11 +103,27 @@ def check_param_grads(ref_mod, hip_mod, tol, skip=(), train=True):
 @pytest.mark.parametrize("train", [True, False])
 @pytest.mark.parametrize("stage,block", [(0, 0), (2, 3), (2, 7), (3, 5)])
 def test_block_matches_oracle(stage, block, train):
-    """(0,0): ConvMlp at 56x56; (2,3): ConvMlp with 3x expansion; (2,7): stride-2 attention + upsample; (3,5): 7x7 attention."""
-    ref, hip = make_pair()
+    _block_matches_oracle("s1", stage, block, train)
+
+
+@pytest.mark.parametrize("train", [True, False])
+@pytest.mark.parametrize("variant,stage,block", [("s2", 1, 3), ("s2", 2, 8), ("s2", 3, 7), ("l", 0, 4), ("l", 2, 9), ("l", 3, 9)])
+def test_block_of_s2_and_l_matches_oracle(variant, stage, block, train):
+    _block_matches_oracle(variant, stage, block, train)
+
+
+def _block_matches_oracle(variant, stage, block, train):
+    """S1 (0,0): ConvMlp at 56x56; (2,3): ConvMlp with 3x expansion; (2,7): stride-2 attention + upsample; (3,5): 7x7 attention.
+    S2 (widths 32 / 64 / 144 / 288, four attention blocks per stage) and L (40 / 80 / 192 / 384, six): a ConvMlp block, the first
+    stride-2 attention block of stage 2 and the last 7x7 attention block.  (The L network as a whole is refused by the builder:
+    its 20-channel stem is not served by the stem kernels.)"""
+    from oracle.efformer_ref import WIDTHS
+
+    ref, hip = make_pair(variant)
     rb, hb = ref.stages[stage].blocks[block], hip.stages[stage].blocks[block]
+    assert (getattr(rb, "token_mixer", None) is not None) == (stage >= 2 and (variant, stage, block) != ("s1", 2, 3))
     rb.train(train); hb.train(train)
-    dim = (32, 48, 120, 224)[stage]
+    dim = WIDTHS[variant][stage]
     res = (56, 28, 14, 7)[stage]
     g = torch.Generator().manual_seed(5)
     x = torch.randn(4, dim, res, res, generator=g).requires_grad_()
@@ -156,7 +173,7 @@ def calibrated_pair(variant="s1", nc=2, img=224, n=8):
     return ref, hip, x, y
 
 
-@pytest.mark.parametrize("variant,img", [("s1", 224), ("s0", 160)])
+@pytest.mark.parametrize("variant,img", [("s1", 224), ("s0", 160), ("s2", 224)])
 def test_eval_logits_f32(variant, img):
     ref, hip, x, _ = calibrated_pair(variant, 10, img)
     ref.eval(); hip.eval()
@@ -170,8 +187,17 @@ def test_eval_logits_f32(variant, img):
 
 
 def test_train_step_f32_all_parameters():
+    _train_step_f32_all_parameters("s1", 8)
+
+
+@pytest.mark.parametrize("variant", ["s0", "s2"])
+def test_train_step_f32_all_parameters_of_each_variant(variant):
+    _train_step_f32_all_parameters(variant, 4)
+
+
+def _train_step_f32_all_parameters(variant, n):
     _, _, _, HipCE = _imports()
-    ref, hip, x, y = calibrated_pair("s1", 2, 224)
+    ref, hip, x, y = calibrated_pair(variant, 2, 224, n=n)
     ref.train(); hip.train()
     loss_ref = F.cross_entropy(ref(x), y, label_smoothing=0.1)
     loss_ref.backward()

@@ -39,6 +39,8 @@ def randomise(model, seed):
                 p.copy_(0.6 + 0.8 * torch.rand(p.shape, generator=g) if last == "weight" else torch.randn(p.shape, generator=g) * 0.2)
             elif last == "bias":
                 p.copy_(torch.randn(p.shape, generator=g) * 0.1)
+            elif last.startswith("gamma"):                   # FasterViT-3's layer scale: 1e-5 at init would hide its branches
+                p.copy_(0.2 + 0.3 * torch.rand(p.shape, generator=g))
             elif "cpb_mlp" in name:
                 p.copy_(torch.randn(p.shape, generator=g) * (0.5 if p.shape[-1] == 2 else 0.05))
         for name, b in model.named_buffers():
@@ -82,15 +84,38 @@ def check_param_grads(ref_mod, hip_mod, tol, train=True):
     return worst
 
 
+VARIANTS = ["0", "1", "2", "3"]
+WIDER = ["1", "2", "3"]                 # the variants the tests written for FasterViT-0 also run for
+
+
+def _dim(variant, level):
+    from oracle.fastervit_ref import CONFIGS
+
+    return CONFIGS[variant][2] << level
+
+
 @pytest.mark.parametrize("train", [True, False])
 def test_conv_block_and_downsample(train):
-    ref, hip = make_pair()
-    rb, hb = ref.levels[0].blocks[1], hip.levels[0].blocks[1]
-    rd_, hd = ref.levels[0].downsample, hip.levels[0].downsample
+    _conv_block_and_downsample("0", 0, train)
+
+
+@pytest.mark.parametrize("train", [True, False])
+@pytest.mark.parametrize("variant,level", [(v, lv) for v in VARIANTS for lv in (0, 1) if (v, lv) != ("0", 0)])
+def test_conv_block_and_downsample_of_each_variant(variant, level, train):
+    _conv_block_and_downsample(variant, level, train)
+
+
+def _conv_block_and_downsample(variant, level, train):
+    """The last ConvBlock of level 0 / 1 and the Downsample behind it: 64 / 128 (FasterViT-0), 80 / 160 (-1), 96 / 192 (-2),
+    128 / 256 (-3, with the ConvBlock's layer scale `gamma`) at 56 / 28 px."""
+    ref, hip = make_pair(variant)
+    rb, hb = ref.levels[level].blocks[-1], hip.levels[level].blocks[-1]
+    rd_, hd = ref.levels[level].downsample, hip.levels[level].downsample
     for m in (rb, hb, rd_, hd):
         m.train(train)
     g = torch.Generator().manual_seed(3)
-    x = torch.randn(3, 64, 56, 56, generator=g).requires_grad_()
+    res = 56 >> level
+    x = torch.randn(3, _dim(variant, level), res, res, generator=g).requires_grad_()
     mid = rb(x)
     out = rd_(mid)
     gout = torch.randn(out.shape, generator=g)
@@ -125,15 +150,29 @@ def test_token_initializer():
 
 @pytest.mark.parametrize("level,with_masks", [(2, False), (2, True), (3, False)])
 def test_hat_block(level, with_masks):
+    _hat_block("0", level, with_masks)
+
+
+@pytest.mark.parametrize("variant", WIDER)
+@pytest.mark.parametrize("level,with_masks", [(2, False), (2, True), (3, False)])
+def test_hat_block_of_each_variant(variant, level, with_masks):
+    _hat_block(variant, level, with_masks)
+
+
+def _hat_block(variant, level, with_masks):
     """level 2: carrier tokens attend globally, join their windows (sequence 53) and are split off again;
-    level 3: one plain 49-token window.  with_masks: DropPath scales on both streams."""
+    level 3: one plain 49-token window.  with_masks: DropPath scales on both streams.  Widths 256 / 512 (FasterViT-0, head
+    dim 32: the fused attention under bf16), 320 / 640 (-1), 384 / 768 (-2), 512 / 1024 (-3, with the layer scales gamma1..4)."""
     from oracle.fastervit_ref import ct_dewindow, ct_window
     from deepfakedetection_amd.fastervit import _window_maps
 
-    ref, hip = make_pair(dpr=0.3 if with_masks else 0.0)
+    ref, hip = make_pair(variant, dpr=0.3 if with_masks else 0.0)
     rb, hb = ref.levels[level].blocks[1], hip.levels[level].blocks[1]
     rb.train(); hb.train()
-    dim = 256 if level == 2 else 512
+    dim = _dim(variant, level)
+    if variant == "3":
+        assert {n for n, _ in rb.named_parameters() if n.startswith("gamma")} == ({"gamma1", "gamma2", "gamma3", "gamma4"} if level == 2
+                                                                                  else {"gamma3", "gamma4"})
     B = 3
     nW = B * (4 if level == 2 else 1)
     g = torch.Generator().manual_seed(5)
@@ -179,7 +218,16 @@ def calibrated_pair(variant="0", nc=2, n=4):
 
 
 def test_eval_logits_f32():
-    ref, hip, x, _ = calibrated_pair("0", 10, n=4)
+    _eval_logits_f32("0")
+
+
+@pytest.mark.parametrize("variant", WIDER)
+def test_eval_logits_f32_of_each_variant(variant):
+    _eval_logits_f32(variant)
+
+
+def _eval_logits_f32(variant):
+    ref, hip, x, _ = calibrated_pair(variant, 10, n=4)
     ref.eval(); hip.eval()
     with torch.no_grad():
         want = ref(x)
@@ -191,8 +239,17 @@ def test_eval_logits_f32():
 
 
 def test_train_step_f32_all_parameters():
+    _train_step_f32_all_parameters("0")
+
+
+@pytest.mark.parametrize("variant", WIDER)
+def test_train_step_f32_all_parameters_of_each_variant(variant):
+    _train_step_f32_all_parameters(variant)
+
+
+def _train_step_f32_all_parameters(variant):
     _, _, HipAdamW, HipCE = _imports()
-    ref, hip, x, y = calibrated_pair("0", 2, n=4)
+    ref, hip, x, y = calibrated_pair(variant, 2, n=4)
     ref.train(); hip.train()
     loss_ref = F.cross_entropy(ref(x), y, label_smoothing=0.1)
     loss_ref.backward()
@@ -234,6 +291,72 @@ def test_bf16_autocast_step_with_drop_path_and_reproducibility():
             HipCE(0.1)(logits, y).backward()
         outs.append((logits.detach().clone(), hip2.levels[2].blocks[0].attn.qkv.weight.grad.clone()))
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+def test_attention_path_of_each_variant_under_bf16_autocast(monkeypatch, variant):
+    """Head dim 32 at levels 2 and 3 (FasterViT-0) runs the fused MFMA attention, 40 / 48 / 64 (-1 / -2 / -3) the batched
+    GEMM + softmax-rows path, in forward and backward: the network-level bf16 tests below judge the path they think they judge."""
+    from deepfakedetection_amd import kernels as K
+    from tests.test_vit_ops_gpu import _PathSpy
+
+    Hip, _, _, HipCE = _imports()
+    torch.manual_seed(0)
+    hip = Hip(variant, 2, drop_path_rate=0.0).cuda().train()
+    x = torch.randn(2, 3, 224, 224, generator=torch.Generator().manual_seed(2)).cuda()
+    spy = _PathSpy(monkeypatch, K)
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        loss = HipCE(0.1)(hip(x), torch.tensor([0, 1]).cuda())
+    fwd = dict(spy.calls)
+    loss.backward()
+    torch.cuda.synchronize()
+    bwd = {k: spy.calls[k] - fwd[k] for k in fwd}
+    from deepfakedetection_amd.fastervit import WindowAttention
+
+    n_attn = sum(isinstance(m, WindowAttention) for m in hip.modules())       # window and carrier-token attention
+    print(f"FasterViT-{variant}: forward {fwd}, backward {bwd}, {n_attn} attention layers")
+    if variant == "0":
+        assert fwd["wattn_fwd"] == n_attn and bwd["wattn_bwd"] == n_attn and fwd["bgemm"] == 0
+    else:
+        assert fwd["wattn_fwd"] == 0 and bwd["wattn_bwd"] == 0
+        assert fwd["bgemm"] == 2 * n_attn and bwd["bgemm"] == 4 * n_attn
+
+
+def test_bf16_autocast_fastervit_2_every_tensor_against_the_oracles_own_bf16_yardstick():
+    """FasterViT-2 (the reference's default model; head dim 48: the bf16 batched-GEMM attention end to end) at batch 4, bf16
+    autocast, against the f32 oracle.  The yardstick is the oracle under torch's CPU bf16 autocast against its f32 self, per
+    tensor: every gradient with signal within 3x the yardstick's relative L2 error (floor 2e-2), logits within the yardstick."""
+    import copy
+
+    from tests._grad_signal import rel_l2, report, signal_names
+
+    _, _, _, HipCE = _imports()
+    ref, hip, x, y = calibrated_pair("2", 2, n=4)
+    ref.train(); hip.train()
+    auto = copy.deepcopy(ref)
+    with torch.autocast("cpu", dtype=torch.bfloat16):
+        auto_logits = auto(x)
+        F.cross_entropy(auto_logits, y, label_smoothing=0.1).backward()
+    ref_logits = ref(x)
+    F.cross_entropy(ref_logits, y, label_smoothing=0.1).backward()
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        logits = hip(x.cuda())
+        loss = HipCE(0.1)(logits, y.cuda())
+    loss.backward()
+    torch.cuda.synchronize()
+    yl, el = rel_err(auto_logits, ref_logits), rel_err(logits, ref_logits)
+    print(f"logits rel err {el:.4f} (oracle's own bf16 autocast {yl:.4f})")
+    assert el <= max(yl, 2e-2), (el, yl)
+    rg = {n: p.grad for n, p in ref.named_parameters()}
+    ag, hg = dict(auto.named_parameters()), dict(hip.named_parameters())
+    names = signal_names(rg)
+    yard = {n: rel_l2(ag[n].grad, rg[n]) for n in names}
+    errs = {n: rel_l2(hg[n].grad, rg[n]) for n in names}
+    print(report({n: errs[n] / max(yard[n], 2e-2 / 3) for n in names}, None), "(ratio to the bound / 3)")
+    print(report(errs, yard))
+    bad = [(n, errs[n], yard[n]) for n in names if errs[n] > max(3 * yard[n], 2e-2)]
+    assert not bad, bad[:8]
+    assert len(names) >= 0.5 * len(rg), (len(names), len(rg))             # measured: 288 of 447
 
 
 def test_refuses_cpu():

@@ -67,13 +67,13 @@ def test_rowpasses_at_baseline_rows():
 
 
 # ------------------------------------------------------------------ the whole step at N = 256
-def _pair(seed=5):
+def _pair(seed=5, variant="b0", flavour="timm"):
     from oracle.effnet_ref import EfficientNetRef
 
     Hip, _, _ = _hip()
     torch.manual_seed(seed)
-    ref = EfficientNetRef("b0", "timm", 2)
-    hip = Hip("b0", "timm", 2)
+    ref = EfficientNetRef(variant, flavour, 2)
+    hip = Hip(variant, flavour, 2)
     hip.load_state_dict(ref.state_dict())
     return ref, hip.cuda()
 
@@ -84,12 +84,32 @@ def rel_err(got, want):
 
 
 def test_full_training_step_at_the_benchmark_configuration():
+    _full_step(_pair(), N_BASE, ("bn1", "blocks.0.0.bn1", "blocks.0.0.bn2", "blocks.1.0.bn1", "blocks.1.0.bn2", "blocks.1.0.bn3",
+                                 "blocks.1.1.bn1", "blocks.1.1.bn2", "blocks.2.0.bn1"))
+
+
+def test_b3_training_step_at_the_reference_configuration():
+    """The reference's own model, efficientnet_b3 (efficientnet_pytorch flavour: static TF-SAME padding from the nominal 300 px,
+    BN eps 1e-3), at its batch 64 and 224 px (config/train.yaml): 1x1 layers of 3 k .. 50 k rows and widths 136 / 232 / 816 /
+    1392, where the ring-kernel planner and the depthwise occupancy classes choose differently from B0 at 256.  On top of the
+    global cosine every gradient with signal is judged on its own, against the oracle's own bf16 autocast gradient of the same
+    tensor (the yardstick): relative L2 error <= 2 x the yardstick's + 0.02.  Measured at this seed: 315 tensors carry
+    signal; the engine's worst is 0.69 for _blocks.0._bn2.bias (yardstick 0.64), its largest ratio 1.44 (_blocks.1._bn2.weight);
+    gradient cosine 0.978 against the yardstick's 0.965 — 26 random-init blocks amplify bf16 rounding further
+    than B0's 16, so the global cosine is bounded by min(0.98, the yardstick's)."""
+    _full_step(_pair(variant="b3", flavour="lukemelas"), 64, ("_bn0", "_blocks.0._bn1", "_blocks.0._bn2", "_blocks.2._bn0",
+                                                              "_blocks.2._bn1", "_blocks.2._bn2", "_blocks.3._bn0"), per_tensor=True)
+
+
+def _full_step(pair, n, bn_names, per_tensor=False):
+    from tests._grad_signal import rel_l2, report, signal_names
+
     _, _, HipCE = _hip()
-    ref, hip = _pair()
+    ref, hip = pair
     ref.train(); hip.train()
     g = torch.Generator().manual_seed(1)                                  # bench.py's generator seed
-    x = torch.randn(N_BASE, 3, 224, 224, generator=g).contiguous(memory_format=torch.channels_last)
-    y = torch.randint(0, 2, (N_BASE,), generator=g)
+    x = torch.randn(n, 3, 224, 224, generator=g).contiguous(memory_format=torch.channels_last)
+    y = torch.randint(0, 2, (n,), generator=g)
     ref_logits = ref(x)
     ref_loss = F.cross_entropy(ref_logits, y, label_smoothing=0.1)
     with torch.autocast("cuda", dtype=BF):
@@ -121,8 +141,7 @@ def test_full_training_step_at_the_benchmark_configuration():
     assert abs(float(loss) - float(ref_loss)) <= 2e-2 * max(1.0, abs(float(ref_loss)))
     # BatchNorm running statistics of the large early layers: f32 sums over 3.2 M bf16 values per channel
     rb, hb = dict(ref.named_buffers()), dict(hip.named_buffers())
-    for name in ("bn1", "blocks.0.0.bn1", "blocks.0.0.bn2", "blocks.1.0.bn1", "blocks.1.0.bn2", "blocks.1.0.bn3", "blocks.1.1.bn1",
-                 "blocks.1.1.bn2", "blocks.2.0.bn1"):
+    for name in bn_names:
         for stat in ("running_mean", "running_var"):
             a, b = hb[f"{name}.{stat}"].float().cpu(), rb[f"{name}.{stat}"]
             scale = float(b.abs().max())
@@ -135,8 +154,29 @@ def test_full_training_step_at_the_benchmark_configuration():
     rp = dict(ref.named_parameters())
     gb = torch.cat([rp[n].grad.flatten() for n, _ in hip.named_parameters()])
     cos = float(torch.dot(ga, gb) / (ga.norm() * gb.norm()))
-    print(f"gradient cosine vs f32 oracle at N=256: {cos:.4f}")
-    assert cos >= 0.98, cos
+    print(f"gradient cosine vs f32 oracle at N={n}: {cos:.4f}")
+    cos_floor = 0.98
+    if per_tensor:
+        rg = {name: p.grad for name, p in ref.named_parameters()}
+        hg = dict(hip.named_parameters())
+        auto = copy.deepcopy(ref)
+        auto.zero_grad(set_to_none=True)
+        with torch.autocast("cpu", dtype=BF):
+            F.cross_entropy(auto(x), y, label_smoothing=0.1).backward()
+        ag = dict(auto.named_parameters())
+        gc = torch.cat([ag[nm].grad.float().flatten() for nm, _ in hip.named_parameters()]).double()
+        cos_yard = float(torch.dot(gc, gb.double()) / (gc.norm() * gb.double().norm()))
+        print(f"the oracle's own bf16 autocast: gradient cosine {cos_yard:.4f}")
+        cos_floor = min(cos_floor, cos_yard)
+        names = signal_names(rg)
+        errs = {name: rel_l2(hg[name].grad, rg[name]) for name in names}
+        yard = {name: rel_l2(ag[name].grad, rg[name]) for name in names}
+        print(report(errs, yard, top=30))
+        print("largest ratios to the yardstick:", sorted(((round(errs[k] / yard[k], 3), k) for k in names), reverse=True)[:8])
+        assert len(names) >= 0.5 * len(rg), (len(names), len(rg))
+        bad = sorted(((errs[k], yard[k], k) for k in names if errs[k] > 2 * yard[k] + 0.02), reverse=True)
+        assert not bad, bad[:8]
+    assert cos >= cos_floor, (cos, cos_floor)
 
 
 def test_twenty_step_loss_curve_f32():
@@ -176,60 +216,93 @@ def test_twenty_step_loss_curve_f32():
 def _block_ref_bf16(blk, x, eps):
     """MBConv forward (training-mode BN, no drop-connect) with a rounding to bf16 wherever the kernels store or
     stage a value: raw conv outputs, the activated tensor staged in LDS / loaded into MFMA fragments, the gated
-    project operand, the block output.  Statistics are f32 sums over the ROUNDED raw tensors, as in the kernels."""
+    project operand, the block output.  Statistics are f32 sums over the ROUNDED raw tensors, as in the kernels.
+    Both flavours: timm (symmetric k // 2 padding) and efficientnet_pytorch (the block's static TF-SAME padding, which may be
+    asymmetric: (0, 1) for the 3x3 stride-2 layers of B3); eps is the flavour's BatchNorm eps."""
     rd = BF
     c = blk.c
+    lm = hasattr(blk, "_depthwise_conv")
 
     def st_of(y, bn):
         return R.bn_state(y, bn.weight.detach(), bn.bias.detach(), eps)
 
     N, H, W, _ = x.shape
-    names = dict(blk.named_children())
+    if lm:
+        expand, expand_bn, dw, dw_bn, proj, proj_bn = (getattr(blk, n, None) for n in ("_expand_conv", "_bn0", "_depthwise_conv", "_bn1",
+                                                                                        "_project_conv", "_bn2"))
+        se_r, se_e = blk._se_reduce, blk._se_expand
+        pl, pr, pt, pb = c.pad_dw
+    else:
+        if c.expand != 1:
+            expand, expand_bn, dw, dw_bn, proj, proj_bn = blk.conv_pw, blk.bn1, blk.conv_dw, blk.bn2, blk.conv_pwl, blk.bn3
+        else:
+            expand, expand_bn, dw, dw_bn, proj, proj_bn = None, None, blk.conv_dw, blk.bn1, blk.conv_pw, blk.bn2
+        se_r, se_e = blk.se.conv_reduce, blk.se.conv_expand
+        pl = pr = pt = pb = c.k // 2
     if c.expand != 1:
-        w = blk.conv_pw.weight.detach().flatten(1)
+        w = expand.weight.detach().flatten(1)
         y1 = R.rnd(x @ R.rnd(w, rd).t(), rd)
-        st1 = st_of(y1, blk.bn1)
-        dw_bn, proj, proj_bn = blk.bn2, blk.conv_pwl, blk.bn3
+        st1 = st_of(y1, expand_bn)
         dw_in, dw_st, dw_act = y1, st1, R.ACT_SILU
     else:
-        dw_bn, proj, proj_bn = blk.bn1, blk.conv_pw, blk.bn2
         dw_in, dw_st, dw_act = x, None, 0
     k, s = c.k, c.stride
-    Ho = (H + 2 * (k // 2) - k) // s + 1
-    y2 = R.dwconv_fwd(dw_in, dw_st, dw_act, blk.conv_dw.weight.detach(), k, s, k // 2, k // 2, Ho, Ho, rd)
+    Ho, Wo = (H + pt + pb - k) // s + 1, (W + pl + pr - k) // s + 1
+    y2 = R.dwconv_fwd(dw_in, dw_st, dw_act, dw.weight.detach(), k, s, pt, pl, Ho, Wo, rd)
     st2 = st_of(y2, dw_bn)
     a2 = R.rnd(R.act_fwd(st2[0] * y2 + st2[1], R.ACT_SILU), rd)
     pooled = a2.mean((1, 2))
-    se = blk.se
-    _, gate = R.se_fc(pooled, se.conv_reduce.weight.detach().flatten(1), se.conv_reduce.bias.detach(),
-                      se.conv_expand.weight.detach().flatten(1), se.conv_expand.bias.detach(), R.ACT_SILU)
+    _, gate = R.se_fc(pooled, se_r.weight.detach().flatten(1), se_r.bias.detach(),
+                      se_e.weight.detach().flatten(1), se_e.bias.detach(), R.ACT_SILU)
     A = R.rnd(a2 * gate[:, None, None, :], rd)
     y3 = R.rnd(A @ R.rnd(proj.weight.detach().flatten(1), rd).t(), rd)
     st3 = st_of(y3, proj_bn)
     out = st3[0] * y3 + st3[1]
     if c.stride == 1 and c.cin == c.cout:
         out = out + x
-    assert "se" in names
     return R.rnd(out, rd)
 
 
 @pytest.mark.parametrize("index", list(range(16)))
 def test_every_b0_block_in_bf16_within_two_ulps_of_the_rounding_emulation(index):
-    ref, hip = _pair(seed=21)
+    res = {0: 56, 1: 56, 2: 28, 3: 28, 4: 14, 5: 14, 6: 14, 7: 14, 8: 14, 9: 14, 10: 14, 11: 14, 12: 7, 13: 7, 14: 7, 15: 7}[index]
+    _block_in_bf16(_pair(seed=21), index, res, 1e-5)
+
+
+def _b3_block_inputs():
+    """Input side of each B3 block at half the 224-px map size (as the B0 cases use), at least 7: 56 for stage 0 ... 7."""
+    from oracle.effnet_ref import build_cfg
+
+    size, out = 112, []
+    for c in build_cfg("b3", "lukemelas")[2]:
+        out.append(max(size // 2, 7))
+        size = -(-size // c.stride)
+    return out
+
+
+@pytest.mark.parametrize("index", list(range(26)))
+def test_every_b3_block_in_bf16_within_two_ulps_of_the_rounding_emulation(index):
+    """The reference's model: efficientnet_pytorch B3 blocks (static TF-SAME padding computed for 300 px, asymmetric (0, 1) on
+    the 3x3 stride-2 layers; BN eps 1e-3; SE widths 6 .. 96; widths 24 .. 2304)."""
+    _block_in_bf16(_pair(seed=22, variant="b3", flavour="lukemelas"), index, _b3_block_inputs()[index], 1e-3)
+
+
+def _block_in_bf16(pair, index, res, eps):
+    ref, hip = pair
     rblk, hblk = ref.block_list()[index], hip.block_list()[index]
     c = rblk.c
-    res = {0: 56, 1: 56, 2: 28, 3: 28, 4: 14, 5: 14, 6: 14, 7: 14, 8: 14, 9: 14, 10: 14, 11: 14, 12: 7, 13: 7, 14: 7, 15: 7}[index]
     g = torch.Generator().manual_seed(100 + index)
     x = torch.randn(8, res, res, c.cin, generator=g).to(BF)
     # non-trivial BN affine parameters on both sides
     with torch.no_grad():
         hp = dict(hblk.named_parameters())
         for n1, p1 in rblk.named_parameters():
-            if ".bn" in n1 or n1.startswith("bn"):
+            if ".bn" in n1 or n1.startswith("bn") or n1.startswith("_bn"):
                 v = 0.6 + 0.8 * torch.rand(p1.shape, generator=g) if n1.endswith("weight") else torch.randn(p1.shape, generator=g) * 0.2
                 p1.copy_(v); hp[n1].copy_(v.cuda())
     rblk.train(); hblk.train()
-    want = _block_ref_bf16(rblk, x.float(), 1e-5)
+    assert all(m.eps == eps for m in rblk.modules() if isinstance(m, torch.nn.BatchNorm2d))
+    want = _block_ref_bf16(rblk, x.float(), eps)
     got = hblk.run(x.cuda(), None, None)
     assert got.dtype == BF
     scale = float(want.abs().max())

@@ -347,7 +347,8 @@ def test_conv_weight_perm_roundtrip_and_dense_conv_through_gemm():
 
 # ------------------------------------------------------------------ LayerNorm
 @pytest.mark.parametrize("rd", DT)
-@pytest.mark.parametrize("C", [64, 256, 512, 1024, 2048])      # 1, 1, 1 | 2, 2 | 0 (streaming) vectors per lane
+@pytest.mark.parametrize("C", [64, 256, 512, 1024, 2048,        # 1, 1, 1 | 2, 2 | 0 (streaming) vectors per lane
+                               80, 96, 160, 192, 320, 384, 640, 768])  # FasterViT-1/2/3 widths: partial-lane rows, other fill levels
 def test_layernorm_fwd_bwd(rd, C):
     K = _k()
     x = (gen((37, C), 1, rd).float() * 1.5 + 0.2).to(rd)
@@ -570,9 +571,21 @@ def test_wave_autonomous_wgrad_with_bn_act_prologue(act):
     close(got, want.float(), 4e-3, "wgrad affine2 x bn_act")
 
 
+# the dense 3x3 layers of FasterViT-1 / -2 / -3 at their real map sizes (k, s, p, C, Cout, H, N): the level-0 / level-1 ConvBlock
+# convolutions (80 and 160 never run the direct kernel; 96 -> 96 has Cout % 64 != 0; 192 and 256 run the implicit GEMM forward but
+# the direct weight gradient), the Downsample convolutions, and the second patch-embed convolutions (in_dim -> dim; the first,
+# 3 -> in_dim, runs the stem kernel)
+FASTERVIT_CONV3 = [(3, 1, 1, 80, 80, 56, 2), (3, 1, 1, 96, 96, 56, 2), (3, 1, 1, 160, 160, 28, 2), (3, 1, 1, 192, 192, 28, 2),
+                   (3, 1, 1, 256, 256, 28, 2),
+                   (3, 2, 1, 80, 160, 56, 2), (3, 2, 1, 96, 192, 56, 2), (3, 2, 1, 160, 320, 28, 2), (3, 2, 1, 192, 384, 28, 2),
+                   (3, 2, 1, 256, 512, 28, 2),
+                   (3, 2, 1, 32, 80, 112, 2), (3, 2, 1, 64, 96, 112, 2), (3, 2, 1, 64, 128, 112, 2)]
+
+
 @pytest.mark.parametrize("rd", DT)
 @pytest.mark.parametrize("cfg", [(3, 1, 1, 64, 64, 28, 6), (3, 2, 1, 24, 48, 15, 3), (3, 1, 1, 128, 128, 9, 5), (3, 2, 1, 96, 192, 14, 2),
-                                 (3, 1, 1, 96, 64, 14, 3), (3, 1, 1, 64, 128, 56, 2), (3, 1, 1, 128, 192, 17, 1), (3, 1, 1, 64, 48, 12, 2)])
+                                 (3, 1, 1, 96, 64, 14, 3), (3, 1, 1, 64, 128, 56, 2), (3, 1, 1, 128, 192, 17, 1), (3, 1, 1, 64, 48, 12, 2)]
+                         + FASTERVIT_CONV3)
 def test_dense_conv_as_implicit_gemm(rd, cfg):
     """dfd_conv_fwd against the im2col + GEMM pair it replaces and against torch's conv2d; with and without the producer's
     BN + GELU, with BN statistics.  Two kernels serve it: the implicit GEMM (the GEMM kernel gathers its A operand from the
@@ -609,7 +622,8 @@ def test_dense_conv_as_implicit_gemm(rd, cfg):
 
 @pytest.mark.parametrize("rd", DT)
 @pytest.mark.parametrize("cfg", [(3, 1, 1, 64, 64, 28, 6), (3, 2, 1, 24, 48, 15, 3), (3, 1, 1, 128, 128, 9, 5), (3, 2, 1, 96, 192, 14, 2),
-                                 (3, 1, 1, 64, 128, 56, 3), (3, 1, 1, 128, 64, 33, 2), (3, 1, 1, 192, 64, 7, 40), (3, 1, 1, 96, 64, 14, 3)])
+                                 (3, 1, 1, 64, 128, 56, 3), (3, 1, 1, 128, 64, 33, 2), (3, 1, 1, 192, 64, 7, 40), (3, 1, 1, 96, 64, 14, 3)]
+                         + FASTERVIT_CONV3)
 def test_dense_conv_weight_gradient_as_implicit_gemm(rd, cfg):
     """dfd_conv_wgrad against im2col + dfd_pwconv_wgrad; with the BN-backward map on the gradient operand and the producer's
     BN + GELU on the gathered one.  The TN kernel that gathers the im2col operand: same kernel, same split of the rows, same
@@ -654,6 +668,70 @@ def test_stride1_conv_data_gradient_is_a_forward_conv_with_the_flipped_weight(rd
     dcol, _, _ = K.pwconv(g.cuda(), None, w_kn, None, stats=False)
     old = K.col2im(dcol, (N, H, H, C), k, 1, p)
     close(got, old.float().cpu(), tol(rd), "dgrad: implicit GEMM vs column matrix + col2im")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# window attention at the head dims of FasterViT-1 / -2 / -3 (40, 48, 64 at levels 2 and 3): the batched-GEMM + softmax-rows path
+class _PathSpy:
+    """Counts the calls of the fused attention kernels and of the batched GEMM while installed on the kernels module."""
+
+    def __init__(self, monkeypatch, K):
+        self.calls = {"wattn_fwd": 0, "wattn_bwd": 0, "bgemm": 0}
+        for name in self.calls:
+            monkeypatch.setattr(K, name, self._wrap(name, getattr(K, name)))
+
+    def _wrap(self, name, fn):
+        def spy(*args, **kwargs):
+            self.calls[name] += 1
+            return fn(*args, **kwargs)
+        return spy
+
+
+@pytest.mark.parametrize("rd", DT)
+@pytest.mark.parametrize("hd,H,T,n", [(40, 8, 53, 5), (40, 16, 49, 3), (40, 8, 49, 7), (40, 16, 53, 2),
+                                      (48, 8, 53, 6), (48, 16, 49, 1), (48, 8, 49, 9), (48, 16, 53, 3),
+                                      (64, 8, 53, 3), (64, 16, 49, 5), (64, 8, 49, 2), (64, 16, 53, 7),
+                                      (32, 8, 53, 5), (32, 16, 49, 3)])
+def test_window_attention_at_every_fastervit_head_dim(monkeypatch, rd, hd, H, T, n):
+    """fastervit_functions.window_attention_fwd / _bwd — what the HAT blocks run — on qkv [n, T, 1, 3C] as the qkv projection
+    leaves it (q, k, v read in place with the 3C row pitch), T = 49 (level 3) or 53 (49 + 4 carrier tokens, level 2), ragged
+    window counts, against float64 attention on the same (bf16-exact) operands: o, dq, dk, dv and the bias gradient summed over
+    the windows.  A spy asserts which path ran: the fused MFMA kernel only for bf16 at head dim 32 (FasterViT-0), the
+    dfd_bgemm + dfd_attn_softmax path everywhere else."""
+    K = _k()
+    from deepfakedetection_amd import fastervit_functions as FF
+
+    C = H * hd
+    g = torch.Generator().manual_seed(hd * 1000 + H * 100 + T + n)
+    qkv = (torch.randn(n, T, 3 * C, generator=g) * 1.5).to(rd)
+    bias = torch.randn(H, T, T, generator=g)
+    dO = torch.randn(n, T, C, generator=g).to(rd)
+    scale = hd ** -0.5
+    q, k, v = [t.double().view(n, T, H, hd).permute(0, 2, 1, 3).requires_grad_() for t in qkv.split(C, dim=-1)]
+    bref = bias.double().requires_grad_()
+    o_ref = ((q @ k.transpose(-1, -2) * scale + bref).softmax(-1) @ v).permute(0, 2, 1, 3).reshape(n, T, C)
+    o_ref.backward(dO.double())
+
+    spy = _PathSpy(monkeypatch, K)
+    qd = qkv.cuda().view(n, T, 1, 3 * C)
+    o, saved = FF.window_attention_fwd(qd, bias.cuda(), H)
+    dqkv, dbias = FF.window_attention_bwd(qd, dO.cuda().view(n, T, 1, C), saved, bias.cuda(), H, True)
+    torch.cuda.synchronize()
+    fused = rd == BF and hd == 32
+    assert fused == K.wattn_supported(rd, T, hd)
+    if fused:
+        assert spy.calls == {"wattn_fwd": 1, "wattn_bwd": 1, "bgemm": 0}, spy.calls
+    else:
+        assert spy.calls == {"wattn_fwd": 0, "wattn_bwd": 0, "bgemm": 6}, spy.calls
+    assert o.dtype == rd and dqkv.dtype == rd and tuple(dqkv.shape) == (n, T, 1, 3 * C)
+    t = tol(rd)
+    close(o.view(n, T, C), o_ref, t, "o")
+    for name, sl, ref in (("dq", slice(0, C), q), ("dk", slice(C, 2 * C), k), ("dv", slice(2 * C, 3 * C), v)):
+        close(dqkv.view(n, T, 3 * C)[..., sl], ref.grad.permute(0, 2, 1, 3).reshape(n, T, C), t, name)
+    close(dbias.view(H, T, T), bref.grad, t, "dbias")
+    # without the bias gradient: the same dqkv, no dbias
+    dqkv2, dbias2 = FF.window_attention_bwd(qd, dO.cuda().view(n, T, 1, C), saved, bias.cuda(), H, False)
+    assert dbias2 is None and torch.equal(dqkv, dqkv2)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
