@@ -25,6 +25,9 @@ ADAMW_TABLE_COLS = 5
 ADAMW_HP_LEN = 8
 EMA_TABLE_COLS = 4
 EMA_LERP, EMA_COPY = 0, 1
+MIX_JOB_WORDS = 8
+MIX_KEEP, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2
+MIX_NHWC, MIX_NCHW = 0, 1
 
 
 class DwShape(Structure):
@@ -102,6 +105,9 @@ SIGNATURES: dict[str, tuple] = {
     "dfd_adamw_step": (c_int, [P, c_int, P, P]),
     # ---- ABI 137
     "dfd_ema_update": (c_int, [P, c_int, P, P]),
+    # ---- ABI 138
+    "dfd_mix_batch": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
+    "dfd_ce_loss_soft": (c_int, [P, P, c_int, c_int, c_float, c_float, P, P, P, P]),
     # ---- ABI 111
     "dfd_bn_eval_coeffs_multi": (c_int, [P, c_int, P]),
     "dfd_sum_batch_begin": (c_int, []),
@@ -247,6 +253,6 @@ def check(code: int, op: str, detail: str = "") -> None:
 
 __all__ = [
     "ACT_GELU", "ACT_NONE", "ACT_RELU", "ACT_SILU", "ADAMW_HP_LEN", "ADAMW_TABLE_COLS", "BF16", "EMA_COPY", "EMA_LERP", "EMA_TABLE_COLS", "F32",
-    "MAX_PARTIALS", "Mat", "PRO_AFFINE2", "PRO_BN_ACT", "PRO_BN_ACT_GATE", "PRO_NONE", "DwShape", "Prologue",
+    "MAX_PARTIALS", "MIX_CUTMIX", "MIX_JOB_WORDS", "MIX_KEEP", "MIX_MIXUP", "MIX_NCHW", "MIX_NHWC", "Mat", "PRO_AFFINE2", "PRO_BN_ACT", "PRO_BN_ACT_GATE", "PRO_NONE", "DwShape", "Prologue",
     "StemShape", "SIGNATURES", "check", "load", "c_int64",
 ]

@@ -864,6 +864,45 @@ extern "C" int dfd_ce_loss(const float* logits, const int64_t* targets, int N, i
     hipLaunchKernelGGL(k_mean_rows, dim3(1), dim3(DFD_THREADS), 0, st, row_loss, N, loss);
     return DFD_CHECK_LAUNCH();
 }
+// probability targets [N][J] (mix.BatchMixer): q = targets * (1 - eps) + eps / J; the rows need not sum to one
+__global__ void __launch_bounds__(DFD_THREADS)
+k_ce_rows_soft(const float* __restrict__ logits, const float* __restrict__ targets, int N, int J, float eps, float gscale,
+               float* __restrict__ row_loss, float* __restrict__ dlogits) {
+    __shared__ float sm[4];
+    const int n = blockIdx.x, t = threadIdx.x;
+    const float* lr = logits + (long)n * J;
+    const float* tr = targets + (long)n * J;
+    float mx = -INFINITY;
+    for (int j = t; j < J; j += DFD_THREADS) mx = fmaxf(mx, lr[j]);
+    mx = block_reduce(mx, sm, true);
+    const float keep = 1.f - eps, floor_q = eps / (float)J;
+    float se = 0.f, sq = 0.f, sqd = 0.f;
+    for (int j = t; j < J; j += DFD_THREADS) {
+        const float d = lr[j] - mx, q = tr[j] * keep + floor_q;
+        se += __expf(d); sq += q; sqd += q * d;
+    }
+    se = block_reduce(se, sm, false);
+    sq = block_reduce(sq, sm, false);
+    sqd = block_reduce(sqd, sm, false);
+    // -sum_j q_j * logp_j with logp_j = d_j - lse
+    if (t == 0) row_loss[n] = __logf(se) * sq - sqd;
+    if (dlogits) {
+        const float inv = 1.f / se, sc = gscale / (float)N;
+        for (int j = t; j < J; j += DFD_THREADS) {
+            const float p = __expf(lr[j] - mx) * inv, q = tr[j] * keep + floor_q;
+            dlogits[(long)n * J + j] = (p * sq - q) * sc;
+        }
+    }
+}
+extern "C" int dfd_ce_loss_soft(const float* logits, const float* targets, int N, int J, float label_smoothing,
+                                float grad_scale, float* row_loss, float* loss, float* dlogits, dfd_stream stream) {
+    if (!logits || !targets || !row_loss || !loss || N < 1 || J < 1) return DFD_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_ce_rows_soft, dim3(N), dim3(DFD_THREADS), 0, st, logits, targets, N, J, label_smoothing, grad_scale,
+                       row_loss, dlogits);
+    hipLaunchKernelGGL(k_mean_rows, dim3(1), dim3(DFD_THREADS), 0, st, row_loss, N, loss);
+    return DFD_CHECK_LAUNCH();
+}
 
 __global__ void __launch_bounds__(DFD_THREADS)
 k_softmax_argmax(const float* __restrict__ logits, int J, float* __restrict__ probs, int64_t* __restrict__ preds) {

@@ -453,11 +453,17 @@ class HeadTailEvalFunction(torch.autograd.Function):
 
 # =========================================================================== loss
 class CrossEntropyFunction(torch.autograd.Function):
-    """Mean label-smoothed cross entropy of f32 logits (trainers/efficientnet.py:412)."""
+    """Mean label-smoothed cross entropy of f32 logits (trainers/efficientnet.py:412).  Like torch's, it takes class
+    indices (int64 [N]) or class probabilities (floating [N, J], what mix.BatchMixer produces)."""
 
     @staticmethod
     def forward(ctx, logits, targets, label_smoothing: float):
-        loss, dlogits = K.ce_loss(_c(logits), targets, label_smoothing, 1.0, ctx.needs_input_grad[0])
+        if targets.is_floating_point():
+            if targets.shape != logits.shape:
+                raise ValueError(f"probability targets must have the logits' shape {tuple(logits.shape)}, got {tuple(targets.shape)}")
+            loss, dlogits = K.ce_loss_soft(_c(logits), _c(targets.float()), label_smoothing, 1.0, ctx.needs_input_grad[0])
+        else:
+            loss, dlogits = K.ce_loss(_c(logits), targets, label_smoothing, 1.0, ctx.needs_input_grad[0])
         ctx.save_for_backward(dlogits)
         return loss
 

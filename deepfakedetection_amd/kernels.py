@@ -21,8 +21,8 @@ import torch
 
 from . import _lib
 from ._lib import (
-    ACT_NONE, ACT_SILU, BF16, F32, MAX_PARTIALS, PRO_AFFINE2, PRO_BN_ACT, PRO_BN_ACT_GATE, PRO_NONE,
-    DwShape, Prologue, StemShape, check,
+    ACT_NONE, ACT_SILU, BF16, F32, MAX_PARTIALS, MIX_CUTMIX, MIX_JOB_WORDS, MIX_KEEP, MIX_NCHW, MIX_NHWC, PRO_AFFINE2, PRO_BN_ACT,
+    PRO_BN_ACT_GATE, PRO_NONE, DwShape, Prologue, StemShape, check,
 )
 
 _scratch: dict[tuple[int, int, str], torch.Tensor] = {}
@@ -1186,6 +1186,21 @@ def ce_loss(logits: torch.Tensor, targets: torch.Tensor, label_smoothing: float,
     return loss, dlogits
 
 
+def ce_loss_soft(logits: torch.Tensor, targets: torch.Tensor, label_smoothing: float, grad_scale: float = 1.0,
+                 want_grad: bool = True):
+    """ce_loss with probability targets, f32 [N, J] (torch's cross_entropy with a floating target; ABI 138)."""
+    if targets.dtype != torch.float32 or targets.shape != logits.shape:
+        raise ValueError(f"ce_loss_soft: targets must be f32 {tuple(logits.shape)}, got {targets.dtype} {tuple(targets.shape)}")
+    N, J = logits.shape
+    dev = logits.device
+    row_loss = torch.empty(N, dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    dlogits = torch.empty_like(logits) if want_grad else None
+    check(_L().dfd_ce_loss_soft(_p(logits), _p(targets), N, J, label_smoothing, grad_scale, _p(row_loss), _p(loss),
+                                _p(dlogits), _stream()), "dfd_ce_loss_soft")
+    return loss, dlogits
+
+
 def softmax_argmax(logits: torch.Tensor, want_probs: bool = True):
     N, J = logits.shape
     probs = torch.empty_like(logits) if want_probs else None
@@ -1238,6 +1253,56 @@ def adamw_step(table: torch.Tensor, hp: torch.Tensor) -> None:
 def ema_update(table: torch.Tensor, w: torch.Tensor) -> None:
     """One dfd_ema_update launch over a device int64 table [nchunks][EMA_TABLE_COLS]; `w` is the f32 weight in device memory."""
     check(_L().dfd_ema_update(_p(table), table.shape[0], _p(w), _stream()), "dfd_ema_update")
+
+
+# ------------------------------------------------------------------ Mixup / CutMix (ABI 138)
+def check_mix_jobs(jobs: torch.Tensor, N: int, H: int, W: int) -> None:
+    """The host job table int32 [N, MIX_JOB_WORDS] {mode, w0, w1, y0, y1, x0, x1, 0}: known modes, every box inside the
+    H x W picture, and the middle sample of an odd N kept."""
+    if jobs.is_cuda or jobs.dtype != torch.int32 or tuple(jobs.shape) != (N, MIX_JOB_WORDS):
+        raise ValueError(f"mix_batch: the job table must be a host int32 [{N}, {MIX_JOB_WORDS}] tensor, got "
+                         f"{jobs.dtype} {tuple(jobs.shape)} on {jobs.device}")
+    mode, y0, y1, x0, x1 = (jobs[:, c] for c in (0, 3, 4, 5, 6))
+    if bool(((mode < MIX_KEEP) | (mode > MIX_CUTMIX)).any()):
+        raise ValueError("mix_batch: unknown mode in the job table")
+    bad = (y0 < 0) | (y0 > y1) | (y1 > H) | (x0 < 0) | (x0 > x1) | (x1 > W)
+    if bool(bad.any()):
+        n = int(bad.nonzero()[0])
+        raise ValueError(f"mix_batch: job {n}: box rows [{int(y0[n])}, {int(y1[n])}) columns [{int(x0[n])}, {int(x1[n])}) "
+                         f"leaves the {H} x {W} picture")
+    if N % 2 == 1 and int(mode[N // 2]) != MIX_KEEP:
+        raise ValueError("mix_batch: the middle sample of an odd batch is its own partner and must be kept")
+
+
+def mix_batch(x: torch.Tensor, labels: torch.Tensor, jobs: torch.Tensor, num_classes: int) -> torch.Tensor:
+    """One dfd_mix_batch launch: mixes the f32 batch `x` [N, 3, H, W] (channels_last or contiguous) IN PLACE with the partner
+    N - 1 - i of every sample as the HOST job table says, and returns the soft targets f32 [N, num_classes].  The table is
+    checked here (check_mix_jobs) and uploaded without blocking when it is pinned.  Host labels are checked against
+    [0, num_classes) and uploaded; labels that already live on the device are not read back (a label out of range matches
+    no class: its share of the target row is dropped, nothing is written out of bounds)."""
+    if not x.is_cuda:
+        raise RuntimeError("mix_batch needs the batch on a HIP device (no CPU fallback)")
+    if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32:
+        raise ValueError(f"mix_batch: x must be f32 [N, 3, H, W], got {x.dtype} {tuple(x.shape)}")
+    N, _, H, W = x.shape
+    if x.is_contiguous():
+        layout, flat = MIX_NCHW, x
+    elif x.is_contiguous(memory_format=torch.channels_last):
+        layout, flat = MIX_NHWC, x.permute(0, 2, 3, 1)
+    else:
+        raise ValueError(f"mix_batch: x must be dense NCHW or channels_last, got strides {x.stride()}")
+    if num_classes < 1 or labels.dtype != torch.int64 or tuple(labels.shape) != (N,):
+        raise ValueError(f"mix_batch: labels must be int64 [{N}] and num_classes >= 1, got {labels.dtype} {tuple(labels.shape)}")
+    check_mix_jobs(jobs, N, H, W)
+    if not labels.is_cuda:
+        if bool(((labels < 0) | (labels >= num_classes)).any()):
+            raise ValueError(f"mix_batch: a label lies outside [0, {num_classes})")
+        labels = labels.to(x.device, non_blocking=True)
+    table = jobs.to(x.device, non_blocking=True)
+    y = torch.empty((N, num_classes), dtype=torch.float32, device=x.device)
+    check(_L().dfd_mix_batch(_p(flat), _p(labels), _p(table), _p(y), N, H, W, num_classes, layout, _stream()), "dfd_mix_batch",
+          f"{tuple(x.shape)}")
+    return y
 
 
 # ------------------------------------------------------------------ token-mixer set (ABI 110)

@@ -28,6 +28,9 @@ class HipCrossEntropyLoss(nn.Module):
     def forward(self, logits: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
         if not logits.is_cuda:
             raise RuntimeError("HipCrossEntropyLoss needs logits on a HIP device (no CPU fallback)")
+        # like nn.CrossEntropyLoss: integer targets are class indices [N], floating targets are class probabilities [N, J]
+        if targets.is_floating_point() and targets.shape != logits.shape:
+            raise ValueError(f"probability targets must have the logits' shape {tuple(logits.shape)}, got {tuple(targets.shape)}")
         return CrossEntropyFunction.apply(logits.float(), targets, self.label_smoothing)
 
 

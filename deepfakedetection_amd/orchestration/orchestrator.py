@@ -164,7 +164,9 @@ _TRAIN_ENV = (("batch_size", "BATCH_SIZE"), ("epochs", "EPOCHS"), ("num_workers"
               ("early_stop_patience", "EARLY_STOP_PATIENCE"))
 _EXTRA_TRAIN_ENV = (("ft_batch_size", "FT_BATCH_SIZE"), ("pretrained", "PRETRAINED"), ("gpu_input_tail", "GPU_INPUT_TAIL"),
                     ("graph_step", "GRAPH_STEP"), ("fp8_weights", "FP8_WEIGHTS"), ("gpu_resize", "GPU_RESIZE"),
-                    ("ema_decay", "EMA_DECAY"), ("ema_warmup", "EMA_WARMUP"), ("ema_eval", "EMA_EVAL"))
+                    ("ema_decay", "EMA_DECAY"), ("ema_warmup", "EMA_WARMUP"), ("ema_eval", "EMA_EVAL"),
+                    ("mixup_alpha", "MIXUP_ALPHA"), ("cutmix_alpha", "CUTMIX_ALPHA"), ("mix_prob", "MIX_PROB"),
+                    ("mix_switch_prob", "MIX_SWITCH_PROB"), ("mix_mode", "MIX_MODE"))
 
 
 def _first_set(*values: Any) -> Any:

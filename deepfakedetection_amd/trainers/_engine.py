@@ -94,10 +94,10 @@ def evaluate(model: nn.Module, dl: DataLoader, device: str, tail=None) -> EvalRe
 def train_one_epoch(model: nn.Module, dl: DataLoader, opt: optim.Optimizer, scaler, criterion: nn.Module, device: str, *,
                     use_cuda_amp: bool, progress: Progress, task: TaskID, accum_steps: int = 1, zero_grad_first: bool = False,
                     reducer: GradAllReducer | None = None, tail=None, label: str = "train", ips_in_extra: bool = False,
-                    stepper=None, ema=None) -> dict:
+                    stepper=None, ema=None, mixer=None) -> dict:
     """One epoch (efficientformer_v2.py:222-257; fastervit.py:243-300 when accum_steps > 1).  Returns throughput
     figures for logs/throughput.jsonl.  `ema` (ema.ModelEma) is updated after every eager optimizer step; a `stepper`
-    updates its own."""
+    updates its own.  `mixer` (mix.BatchMixer) mixes every batch in place and turns its labels into probability rows."""
     model.train()
     start = perf_counter()
     if not zero_grad_first:
@@ -105,6 +105,8 @@ def train_one_epoch(model: nn.Module, dl: DataLoader, opt: optim.Optimizer, scal
     seen_total = pending = 0
     shown = float("nan")
     for i, (inputs, targets) in enumerate(_base.device_batches(dl, device, tail, prefetch=stepper is not None), 1):
+        if mixer is not None:
+            inputs, targets = mixer(inputs, targets)        # outside of the captured step: one launch on this stream
         if stepper is not None:
             # hipGraph replay of the same body; zero_grad belongs to the first micro-batch of a cycle either way
             loss = stepper.micro_batch(inputs, targets, first=pending == 0, last=pending + 1 == accum_steps)
@@ -230,6 +232,7 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
     model = model.to(device)
     broadcast_module_state(model)
     criterion, make_opt = _base._make_criterion_and_optimizer(use_cuda)
+    mixer = _base.make_mixer(_base.mix_settings(), num_classes, device)      # Mixup / CutMix ($MIXUP_ALPHA, $CUTMIX_ALPHA)
     scaler = torch.amp.GradScaler(enabled=False)
     opt_extra = {"grad_scale": 1.0 / world} if use_cuda else {}
 
@@ -254,7 +257,7 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
             # train_one_epoch with zero_grad first, no accumulation and the rate in the `extra` column
             stats = train_one_epoch(model, train_dl, warm_opt, scaler, criterion, device, use_cuda_amp=use_cuda, progress=progress,
                                     task=task, accum_steps=1, zero_grad_first=True, reducer=reducer, tail=train_tail,
-                                    label="warmup", ips_in_extra=True,
+                                    label="warmup", ips_in_extra=True, mixer=mixer,
                                     stepper=_base.make_stepper(model, criterion, warm_opt, accum_steps=1, use_cuda=use_cuda, world=world,
                                                                  reducer=reducer))
             log_throughput(env, chief, world, phase="warmup", epoch=0, model=model_name, batch_size=batch_size, **stats)
@@ -306,7 +309,7 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
             task = progress.add_task(f"epoch {epoch}", total=len(ft_dl), extra="")
             stats = train_one_epoch(model, ft_dl, opt, scaler, criterion, device, use_cuda_amp=use_cuda, progress=progress, task=task,
                                     accum_steps=accum, zero_grad_first=spec.zero_grad_first, reducer=reducer, tail=train_tail,
-                                    stepper=stepper, ema=ema)
+                                    stepper=stepper, ema=ema, mixer=mixer)
             log_throughput(env, chief, world, phase="fine-tune", epoch=epoch, model=model_name,
                            batch_size=ft_dl.batch_size, accum_steps=accum, **stats)
             scheduler.step()

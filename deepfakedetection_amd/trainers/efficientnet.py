@@ -354,12 +354,45 @@ def ema_checkpoint_extra(ema) -> dict:
     return {} if ema is None else {"model_ema": ema.module.state_dict(), "model_ema_updates": ema.updates}
 
 
+@dataclass(frozen=True)
+class MixSettings:
+    mixup_alpha: float
+    cutmix_alpha: float
+    prob: float
+    switch_prob: float
+    mode: str
+
+
+def mix_settings() -> MixSettings | None:
+    """$MIXUP_ALPHA, $CUTMIX_ALPHA (YAML training.mixup_alpha / cutmix_alpha; both absent or 0: off), $MIX_PROB (default 1),
+    $MIX_SWITCH_PROB (default 0.5), $MIX_MODE (batch | pair | elem, default batch)."""
+    mixup, cutmix = env_float("MIXUP_ALPHA", 0.0), env_float("CUTMIX_ALPHA", 0.0)
+    if not mixup and not cutmix:
+        return None
+    return MixSettings(mixup_alpha=mixup, cutmix_alpha=cutmix, prob=env_float("MIX_PROB", 1.0),
+                       switch_prob=env_float("MIX_SWITCH_PROB", 0.5), mode=env_str("MIX_MODE", "batch").lower())
+
+
+def make_mixer(settings: MixSettings | None, num_classes: int, device: str):
+    """mix.BatchMixer for the training batches of every phase (None when mixing is off); evaluation never mixes."""
+    if settings is None:
+        return None
+    if not str(device).startswith("cuda"):
+        raise RuntimeError("Mixup / CutMix (training.mixup_alpha, cutmix_alpha) run on a HIP device only (no CPU fallback)")
+    from ..mix import BatchMixer
+
+    return BatchMixer(mixup_alpha=settings.mixup_alpha, cutmix_alpha=settings.cutmix_alpha, prob=settings.prob,
+                      switch_prob=settings.switch_prob, mode=settings.mode, num_classes=num_classes)
+
+
 def train_one_epoch(model: nn.Module, dl: DataLoader, opt: optim.Optimizer, scaler, criterion: nn.Module, device: str, *,
                     use_cuda_amp: bool, progress: Progress, task: TaskID, accum_steps: int = 1,
-                    reducer: GradAllReducer | None = None, tail=None, stepper=None, stats: dict | None = None, ema=None) -> float:
+                    reducer: GradAllReducer | None = None, tail=None, stepper=None, stats: dict | None = None, ema=None,
+                    mixer=None) -> float:
     """One epoch; returns the mean training loss (reference :265-333).  `stepper` (graph_step.GraphedTrainStep)
     replays the captured loop body instead of dispatching it (and updates its own `ema`); `stats` receives throughput
-    figures; `ema` (ema.ModelEma) is updated after every eager optimizer step."""
+    figures; `ema` (ema.ModelEma) is updated after every eager optimizer step; `mixer` (mix.BatchMixer) mixes every batch
+    in place and turns its labels into probability rows before the step sees them."""
     model.train()
     start = perf_counter()
     opt.zero_grad(set_to_none=True)
@@ -367,6 +400,8 @@ def train_one_epoch(model: nn.Module, dl: DataLoader, opt: optim.Optimizer, scal
     seen_total = pending = 0
     shown = float("nan")
     for i, (inputs, targets) in enumerate(device_batches(dl, device, tail, prefetch=stepper is not None), 1):
+        if mixer is not None:
+            inputs, targets = mixer(inputs, targets)        # outside of the captured step: one launch on this stream
         if stepper is not None:
             # zero_grad is part of the "first" body; `last` lets an eager micro-batch overlap the DP exchange with its backward
             loss = stepper.micro_batch(inputs, targets, first=pending == 0, last=pending + 1 == accum_steps)
@@ -523,6 +558,7 @@ def main() -> None:  # noqa: PLR0915
     model = model.to(device)
     broadcast_module_state(model)
     criterion, make_opt = _make_criterion_and_optimizer(use_cuda)
+    mixer = make_mixer(mix_settings(), num_classes, device)      # Mixup / CutMix ($MIXUP_ALPHA, $CUTMIX_ALPHA)
     scaler = torch.amp.GradScaler(enabled=False)        # bf16 needs no loss scaling; calls kept for parity
     opt_extra = {"grad_scale": 1.0 / world} if use_cuda else {}
 
@@ -545,7 +581,7 @@ def main() -> None:  # noqa: PLR0915
             console.print("[bold]Warmup (head only)[/]")
             stats: dict = {}
             train_one_epoch(model, train_dl, warm_opt, scaler, criterion, device, use_cuda_amp=use_cuda, progress=progress,
-                            task=task, accum_steps=1, reducer=reducer, tail=train_tail, stats=stats,
+                            task=task, accum_steps=1, reducer=reducer, tail=train_tail, stats=stats, mixer=mixer,
                             stepper=make_stepper(model, criterion, warm_opt, accum_steps=1, use_cuda=use_cuda, world=world, reducer=reducer))
             _log_throughput(env, chief, world, phase="warmup", epoch=0, model=model_name, batch_size=batch_size, **stats)
             if reducer is not None:
@@ -591,7 +627,7 @@ def main() -> None:  # noqa: PLR0915
             stats = {}
             train_loss = train_one_epoch(model, train_dl_ft, opt, scaler, criterion, device, use_cuda_amp=use_cuda,
                                          progress=progress, task=task, accum_steps=accum_steps, reducer=reducer,
-                                         tail=train_tail, stepper=stepper, stats=stats, ema=ema)
+                                         tail=train_tail, stepper=stepper, stats=stats, ema=ema, mixer=mixer)
             _log_throughput(env, chief, world, phase="fine-tune", epoch=epoch, model=model_name, batch_size=ft_batch,
                             accum_steps=accum_steps, **stats)
             scheduler.step()

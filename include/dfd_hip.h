@@ -81,7 +81,9 @@ typedef void* dfd_stream;          /* a hipStream_t */
  * 135 = dfd_tune keys 8-13 (grids of the vector-unit depthwise kernels — their default changed, so partial-row counts did — and of the
  * tiled weight gradient); immediate partial-row sums of 33..256 rows in one launch (same order, same bits);
  * 136 = Grad-CAM: dfd_gradcam_map, dfd_cam_render / dfd_cam_render_ws;
- * 137 = dfd_ema_update (exponential moving average of the weights). */
+ * 137 = dfd_ema_update (exponential moving average of the weights);
+ * 138 = dfd_mix_batch (Mixup / CutMix of a batch in place, with its soft targets), dfd_ce_loss_soft (cross entropy with
+ * probability targets). */
 int dfd_version(void);
 
 /* Planner knobs (A/B switches and sizes the host-side kernel selection reads).  Process-wide plain ints: set them once at
@@ -418,6 +420,12 @@ int dfd_linear_bwd(const float* dout, const float* x, const float* w, float* dx,
 int dfd_ce_loss(const float* logits, const int64_t* targets, int N, int J,
                 float label_smoothing, float grad_scale, float* row_loss, float* loss,
                 float* dlogits, dfd_stream stream);
+/* The same with probability targets, f32 [N][J] (torch's cross_entropy with a floating target): q = targets * (1 - ls) + ls / J,
+ * row_loss[n] = -sum_j q[n][j] * logp[n][j], loss = mean, dlogits = (softmax * sum_j q[n][j] - q) * grad_scale / N.  The rows
+ * of `targets` need not sum to one.                                                  */
+int dfd_ce_loss_soft(const float* logits, const float* targets, int N, int J,
+                     float label_smoothing, float grad_scale, float* row_loss, float* loss,
+                     float* dlogits, dfd_stream stream);
 int dfd_softmax_argmax(const float* logits, int N, int J, float* probs, int64_t* preds,
                        dfd_stream stream);
 /* Resize + CenterCrop / RandomResizedCrop of decoded uint8 RGB images on the device, bit-exact with Pillow's bilinear
@@ -476,6 +484,24 @@ int dfd_adamw_step(const int64_t* table, int nchunks, const float* hp, dfd_strea
 #define DFD_EMA_LERP 0
 #define DFD_EMA_COPY 1
 int dfd_ema_update(const int64_t* table, int nchunks, const float* w, dfd_stream stream);
+/* Mixup / CutMix of an f32 image batch [N][3][H][W] in place (layout: DFD_MIX_NHWC = channels_last memory, DFD_MIX_NCHW =
+ * contiguous) and its soft targets y, f32 [N][J].  The partner of sample i is N - 1 - i.  jobs: one row of DFD_MIX_JOB_WORDS
+ * 32-bit words per sample in device memory, {mode, w0, w1, y0, y1, x0, x1, 0}; w0 and w1 are f32 bit patterns.
+ *   DFD_MIX_KEEP    picture untouched, y[i] = onehot(labels[i])
+ *   DFD_MIX_MIXUP   x[i] = x[i] * w0 + x[N-1-i] * w1, rounded as a = x_i * w0, b = x_j * w1, a + b (no FMA)
+ *   DFD_MIX_CUTMIX  pixels with y0 <= row < y1 and x0 <= col < x1 take the partner's value, all channels
+ * with x_i, x_j the values before the launch; the two jobs of a pair may differ.  Targets of the two mixing modes: zeros,
+ * y[i][labels[i]] = w0, then y[i][labels[N-1-i]] += w1.  The middle sample of an odd N is always kept.  Boxes are clamped to
+ * the picture and a label outside [0, J) matches no class.  NULL pointer, N < 1, J < 1, H < 1, W < 1 or an unknown layout:
+ * DFD_EINVAL before any launch.                                                      */
+#define DFD_MIX_JOB_WORDS 8
+#define DFD_MIX_KEEP 0
+#define DFD_MIX_MIXUP 1
+#define DFD_MIX_CUTMIX 2
+#define DFD_MIX_NHWC 0
+#define DFD_MIX_NCHW 1
+int dfd_mix_batch(float* x, const int64_t* labels, const int32_t* jobs, float* y, int N, int H, int W, int J, int layout,
+                  dfd_stream stream);
 
 /* ------------------------------------------------------------ token mixers ---
  * What the EfficientFormerV2 (timm 1.0.20 efficientformer_v2.py: Attention2d, Attention2dDownsample,
