@@ -1,23 +1,31 @@
-"""Shared body of the EfficientFormerV2 and FasterViT trainers on the MI355X engine.
+"""The one training engine of the EfficientNet, EfficientFormerV2 and FasterViT trainers on the MI355X.
 
-The reference keeps three near-identical scripts (trainers/efficientnet.py, efficientformer_v2.py, fastervit.py).
-`deepfakedetection_amd.trainers.efficientnet` mirrors the first one function by function; the other two differ
-from it only in the points SURVEY.md section 3.1 tabulates, captured here as a `TrainerSpec`:
+The reference keeps three near-identical scripts (trainers/efficientnet.py, efficientformer_v2.py, fastervit.py).  Here the
+epoch loop, the evaluation loop, the throughput log and the phase driver exist once; a trainer module is its constants, a
+`TrainerSpec` and `main()`.  The spec carries what differs — this table is the one list of it:
 
-  behaviour                  efficientformer_v2.py                           fastervit.py
-  warm-up trainable set      "classifier" or "head" in name (:351-352)       "head" in name (:400-402)
-  fine-tune trainable set    UNFREEZE_KEYS substrings (:66-74, :389-393)     all (:434-435)
-  fine-tune batch / accum    BATCH_SIZE, none (:419-430)                     32 x 4 hard-coded (:437-453)
-  zero_grad                  before the forward (:242)                       after the step (:278-283)
-  evaluate                   accuracy only (:206-219)                        accuracy only (:224-240)
-  early stop                 no                                              EARLY_STOP_PATIENCE (:322, :526)
-  transforms                 rotation / erasing off, jitter 0.1 (:105-165)   same (:119-180)
-  model                      timm.create_model(name, num_classes, img_size)  create_model(name); head = Linear(in, nc)
+  behaviour (spec field)                  efficientnet.py                     efficientformer_v2.py               fastervit.py
+  warm-up trainable set (warmup_keys)     "_fc" or "classifier" (:433-437)    "classifier" or "head" (:351-352)   "head" (:400-402)
+  fine-tune trainable set (unfreeze_keys) all (:479-480)                      UNFREEZE_KEYS (:66-74, :389-393)    all (:434-435)
+  fine-tune batch x accum (ft_*)          $FT_BATCH_SIZE 32 x $ACCUM_STEPS 4  BATCH_SIZE, none (:419-430)         32 x 4 hard-coded (:437-453)
+  zero_grad (zero_grad_first)             epoch start + after the step        before the forward (:242)           after the step (:278-283)
+  warm-up zero_grad (warmup_zero_grad_first)  epoch start + after the step    before the forward (:362-382)       before the forward (:408-428)
+  losses (report_loss)                    evaluate: accuracy + mean CE;       accuracy only (:206-219)            accuracy only (:224-240)
+                                          epoch: mean loss over ranks
+  early stop (early_stop)                 EARLY_STOP_PATIENCE                 no                                  EARLY_STOP_PATIENCE (:322, :526)
+  transforms (transform_kwargs)           build_transforms defaults           rotation / erasing off, jitter 0.1, rotation after flip (both)
+  model (pass_img_size)                   builder(name, classes)              builder(name, classes, img_size)    builder(name, classes)
+  console lines (warmup_line, epoch_line, with val_loss / train_loss, counts  bare val_acc; EMA with counts       val_acc, counts, lr; EMA with counts
+                 ema_line)                and lr
+  warm-up progress (warmup_task,          "warmup (head only)",               "warmup", rate in the extra column (both)
+                    warmup_label)         train | loss | img/s
 
-Everything else — env contract, phases, checkpoints, file names, console lines, SystemExit paths — is the
-reference's.  Deliberate differences are those of the EfficientNet trainer (bf16 autocast, disabled GradScaler
-kept for API parity, HIP loss / AdamW, one host sync per LOG_EVERY steps, local pretrained weights, DP over
-WORLD_SIZE ranks, `logs/throughput.jsonl`).
+Everything else — env contract, phases, checkpoints, file names, SystemExit paths — is the reference's.  Deliberate
+differences, all keeping the reference's defaults: the model is `get_model_spec($MODEL_NAME).builder`,
+pretrained weights come from $PRETRAINED / weights/<name>.pth if present (no network), else random init with a warning;
+bf16 autocast and a disabled GradScaler kept for API parity; HIP loss / AdamW on a cuda device; one host sync per LOG_EVERY
+steps instead of a `loss.item()` per iteration; `prefetch_factor` only with workers; WORLD_SIZE > 1 (torchrun) shards the
+minibatches over ranks, all-reduces gradients over RCCL, rank 0 logs and writes checkpoints; `logs/throughput.jsonl`.
 """
 
 from __future__ import annotations
@@ -38,10 +46,14 @@ from ..orchestration.train_env import (
     apply_seed, create_console, env_float, env_int, env_path, env_str, maybe_load_checkpoint, prepare_training_environment,
     save_best_checkpoint, save_latest_checkpoint,
 )
-from . import efficientnet as _base
+from ._inputs import device_batches, get_loaders, make_loader, policy_settings
 
 DATA_ROOT = Path.home() / "code" / "DeepfakeDetection" / "data" / "Dataset"
 LOG_EVERY = 10
+ACC = "val_acc={res.acc:.4f}"                           # pieces of the console lines below: str.format templates
+ACC_COUNTS = ACC + " ({res.correct}/{res.total})"
+
+console = create_console()      # re-bound by every run(): LOG_PATH differs per orchestrated run
 
 
 @dataclass(frozen=True)
@@ -52,9 +64,12 @@ class TrainerSpec:
     default_batch_size: int
     warmup_keys: tuple[str, ...]
     unfreeze_keys: tuple[str, ...] | None           # None: fine-tune everything
-    ft_batch_size: int | None = None                # None: BATCH_SIZE
+    ft_batch_size: int | None = None                # None: BATCH_SIZE batches, no `Fine-tune:` line
     ft_accum_steps: int = 1
+    ft_from_env: bool = False                       # the two above are the defaults of $FT_BATCH_SIZE / $ACCUM_STEPS
     zero_grad_first: bool = False
+    warmup_zero_grad_first: bool = True
+    report_loss: bool = False                       # evaluate() adds the mean CE loss, an epoch its mean training loss
     early_stop: bool = False
     default_patience: int = 4
     default_img_size: int = 224
@@ -64,8 +79,13 @@ class TrainerSpec:
     ft_lr: float = 1e-4
     ft_wd: float = 5e-2
     pass_img_size: bool = False                      # builder takes img_size (EfficientFormerV2 bias tables)
-    transform_kwargs: dict = field(default_factory=lambda: dict(rotation_default=False, erasing_default=False,
-                                                                jitter=(0.1, 0.1, 0.1, 0.05), rotation_after_flip=True))
+    transform_kwargs: dict | None = field(default_factory=lambda: dict(      # None: build_transforms' own defaults
+        rotation_default=False, erasing_default=False, jitter=(0.1, 0.1, 0.1, 0.05), rotation_after_flip=True))
+    warmup_task: str = "warmup"
+    warmup_label: str | None = "warmup"             # progress text `<label> | loss` + rate in the extra column; None: as training
+    warmup_line: str = ACC                          # formatted with res=EvalResult
+    epoch_line: str = ACC                           # res, train_loss (None without report_loss), lr
+    ema_line: str = ACC_COUNTS                      # res (of the EMA model)
 
 
 @dataclass(frozen=True)
@@ -73,42 +93,192 @@ class EvalResult:
     acc: float
     total: int
     correct: int
+    loss: float | None = None                       # mean CE loss when evaluate() got a criterion
 
 
-def evaluate(model: nn.Module, dl: DataLoader, device: str, tail=None) -> EvalResult:
-    """Top-1 accuracy; f32, no autocast (efficientformer_v2.py:206-219, fastervit.py:224-240).  The counter stays on
-    the device and is read once at the end (and summed over ranks)."""
+@dataclass(frozen=True)
+class EpochResult:
+    stats: dict                                     # throughput figures for logs/throughput.jsonl
+    loss: float | None = None                       # mean training loss over all ranks (with_loss)
+
+
+def eval_forward(model: nn.Module, device: str):
+    """The callable evaluate() runs per batch: the model itself, or — on a HIP device, unless GRAPH_STEP is off — a
+    graph_step.GraphedForward kept on the model, which replays the eval-mode forward per batch shape (bit-identical to
+    the eager forward; at the reference's validation batch sizes the eager forward is host-bound)."""
+    if not str(device).startswith("cuda") or env_str("GRAPH_STEP", "1").lower() in {"0", "false", "no", "off"}:
+        return model
+    fwd = model.__dict__.get("_graphed_eval")
+    if fwd is None:
+        from ..graph_step import GraphedForward
+
+        fwd = model.__dict__["_graphed_eval"] = GraphedForward(model)
+    return fwd
+
+
+def make_stepper(model: nn.Module, criterion: nn.Module, opt, *, accum_steps: int, use_cuda: bool, world: int, reducer=None,
+                 ema=None):
+    """hipGraph replay of the loop body ($GRAPH_STEP, YAML training.graph_step; default on) on a HIP device with the
+    HIP optimizer; with `world` > 1 the object also drives the gradient exchange (`reducer`): graph(zero_grad + forward +
+    backward) -> all-reduce of the flat gradient arena (RCCL, outside of capture) -> graph(AdamW [+ EMA update]).  Otherwise
+    None: the loop runs eagerly as the reference's does."""
+    if not use_cuda or getattr(opt, "arena", None) is None or (world > 1 and reducer is None):
+        return None
+    if env_str("GRAPH_STEP", "1").lower() in {"0", "false", "no", "off"}:
+        return None
+    from ..graph_step import GraphedTrainStep
+
+    return GraphedTrainStep(model, criterion, opt, accum_steps=accum_steps, use_amp=True, reducer=reducer, ema=ema)
+
+
+@dataclass(frozen=True)
+class EmaSettings:
+    decay: float
+    warmup: bool
+    select: bool            # best epoch / early stopping / best weights follow the EMA model
+
+
+def ema_settings() -> EmaSettings | None:
+    """$EMA_DECAY (YAML training.ema_decay; absent or 0: off), $EMA_WARMUP (default on), $EMA_EVAL (default on)."""
+    decay = env_float("EMA_DECAY", 0.0)
+    if not decay:
+        return None
+    on = lambda name: env_str(name, "1").lower() not in {"0", "false", "no", "off"}     # noqa: E731
+    return EmaSettings(decay=decay, warmup=on("EMA_WARMUP"), select=on("EMA_EVAL"))
+
+
+def make_model_ema(model: nn.Module, build, device: str, settings: EmaSettings):
+    """ema.ModelEma of `model` with a shadow from `build()` (the model's own registry builder) placed like the model."""
+    from ..ema import ModelEma
+
+    if not str(device).startswith("cuda"):
+        raise RuntimeError("the weight EMA (training.ema_decay) runs on a HIP device only (no CPU fallback)")
+    shadow = build()
+    shadow.to(memory_format=torch.channels_last)
+    shadow = shadow.to(device)
+    return ModelEma(model, shadow, decay=settings.decay, warmup=settings.warmup)
+
+
+def restore_model_ema(ema, state: dict | None) -> None:
+    """On resume: the checkpoint's `model_ema` (+ `model_ema_updates`); without one EMA starts over as a copy of the model."""
+    if ema is None or state is None:
+        return
+    if state.get("model_ema") is None:
+        console.print("[bold yellow]⚠️  The checkpoint holds no model_ema[/]; the EMA starts over as a copy of the model")
+        ema.reset()
+        return
+    ema.load_state_dict({"module": state["model_ema"], "updates": int(state.get("model_ema_updates", 0))})
+
+
+def ema_checkpoint_extra(ema) -> dict:
+    return {} if ema is None else {"model_ema": ema.module.state_dict(), "model_ema_updates": ema.updates}
+
+
+@dataclass(frozen=True)
+class MixSettings:
+    mixup_alpha: float
+    cutmix_alpha: float
+    prob: float
+    switch_prob: float
+    mode: str
+
+
+def mix_settings() -> MixSettings | None:
+    """$MIXUP_ALPHA, $CUTMIX_ALPHA (YAML training.mixup_alpha / cutmix_alpha; both absent or 0: off), $MIX_PROB (default 1),
+    $MIX_SWITCH_PROB (default 0.5), $MIX_MODE (batch | pair | elem, default batch)."""
+    mixup, cutmix = env_float("MIXUP_ALPHA", 0.0), env_float("CUTMIX_ALPHA", 0.0)
+    if not mixup and not cutmix:
+        return None
+    return MixSettings(mixup_alpha=mixup, cutmix_alpha=cutmix, prob=env_float("MIX_PROB", 1.0),
+                       switch_prob=env_float("MIX_SWITCH_PROB", 0.5), mode=env_str("MIX_MODE", "batch").lower())
+
+
+def make_mixer(settings: MixSettings | None, num_classes: int, device: str):
+    """mix.BatchMixer for the training batches of every phase (None when mixing is off); evaluation never mixes."""
+    if settings is None:
+        return None
+    if not str(device).startswith("cuda"):
+        raise RuntimeError("Mixup / CutMix (training.mixup_alpha, cutmix_alpha) run on a HIP device only (no CPU fallback)")
+    from ..mix import BatchMixer
+
+    return BatchMixer(mixup_alpha=settings.mixup_alpha, cutmix_alpha=settings.cutmix_alpha, prob=settings.prob,
+                      switch_prob=settings.switch_prob, mode=settings.mode, num_classes=num_classes)
+
+
+def _load_pretrained(model: nn.Module, name: str) -> None:
+    hint = env_str("PRETRAINED", "")
+    if hint.lower() in ("0", "false", "no", "none"):
+        return
+    candidates = [Path(hint)] if hint else [Path("weights") / f"{name}.pth", Path("weights") / f"{name}_v0.3.0.pth"]
+    for path in candidates:
+        if path.is_file():
+            state = torch.load(path, map_location="cpu")
+            if isinstance(state, dict) and "state_dict" in state:
+                state = state["state_dict"]
+            elif isinstance(state, dict) and "model" in state:
+                state = state["model"]
+            own = model.state_dict()
+            usable = {k: v for k, v in state.items() if k in own and v.shape == own[k].shape}   # head may differ in classes
+            model.load_state_dict(usable, strict=False)
+            console.print(f"[bold green]Loaded pretrained weights[/] {path} ({len(usable)}/{len(own)} tensors)")
+            return
+    console.print("[bold yellow]⚠️  No local pretrained weights[/] (set training.pretrained); starting from random init")
+
+
+def _make_criterion_and_optimizer(use_cuda: bool):
+    if use_cuda:
+        from ..optim import HipAdamW, HipCrossEntropyLoss
+
+        return HipCrossEntropyLoss(label_smoothing=0.1), HipAdamW
+    # device: cpu — the reference's own torch path; only non-HIP (plug-in) modules can run there
+    return nn.CrossEntropyLoss(label_smoothing=0.1), optim.AdamW
+
+
+def evaluate(model: nn.Module, dl: DataLoader, device: str, tail=None, criterion: nn.Module | None = None) -> EvalResult:
+    """Top-1 accuracy and, with a `criterion`, the mean loss; f32, no autocast (efficientnet.py:237-262,
+    efficientformer_v2.py:206-219, fastervit.py:224-240).  The counters stay on the device and are read once at the end
+    (and summed over ranks in one collective)."""
     model.eval()
     correct = torch.zeros((), dtype=torch.float64, device=device)
+    loss_sum = torch.zeros((), dtype=torch.float64, device=device) if criterion is not None else None
     total = 0
     with torch.inference_mode():
         # (large validation batches: the forward is GPU-bound and the in-stream copy would add ~40 % to it)
-        fwd = _base.eval_forward(model, device)
-        for inputs, targets in _base.device_batches(dl, device, tail, prefetch=(getattr(dl, "batch_size", 0) or 0) >= 128):
-            correct += (fwd(inputs).argmax(1) == targets).sum()
+        fwd = eval_forward(model, device)
+        for inputs, targets in device_batches(dl, device, tail, prefetch=(getattr(dl, "batch_size", 0) or 0) >= 128):
+            logits = fwd(inputs)
+            if criterion is not None:
+                loss_sum += criterion(logits, targets).double() * targets.size(0)
+            correct += (logits.argmax(1) == targets).sum()
             total += targets.numel()
-    n_correct, n_total = all_reduce_counts(float(correct), float(total), device=device)
-    return EvalResult(acc=n_correct / max(1, n_total), total=int(n_total), correct=int(n_correct))
+    sums = [float(correct), float(total)] + ([float(loss_sum)] if criterion is not None else [])
+    n_correct, n_total, *s_loss = all_reduce_counts(*sums, device=device)
+    return EvalResult(acc=n_correct / max(1, n_total), total=int(n_total), correct=int(n_correct),
+                      loss=s_loss[0] / max(1, n_total) if s_loss else None)
 
 
 def train_one_epoch(model: nn.Module, dl: DataLoader, opt: optim.Optimizer, scaler, criterion: nn.Module, device: str, *,
                     use_cuda_amp: bool, progress: Progress, task: TaskID, accum_steps: int = 1, zero_grad_first: bool = False,
-                    reducer: GradAllReducer | None = None, tail=None, label: str = "train", ips_in_extra: bool = False,
-                    stepper=None, ema=None, mixer=None) -> dict:
-    """One epoch (efficientformer_v2.py:222-257; fastervit.py:243-300 when accum_steps > 1).  Returns throughput
-    figures for logs/throughput.jsonl.  `ema` (ema.ModelEma) is updated after every eager optimizer step; a `stepper`
-    updates its own.  `mixer` (mix.BatchMixer) mixes every batch in place and turns its labels into probability rows."""
+                    reducer: GradAllReducer | None = None, tail=None, label: str | None = None, stepper=None, ema=None,
+                    mixer=None, with_loss: bool = False) -> EpochResult:
+    """One epoch (efficientnet.py:265-333; efficientformer_v2.py:222-257; fastervit.py:243-300).  `stepper`
+    (graph_step.GraphedTrainStep) replays the captured loop body instead of dispatching it and updates its own `ema`;
+    an eager optimizer step updates `ema` (ema.ModelEma) itself.  `mixer` (mix.BatchMixer) mixes every batch in place and
+    turns its labels into probability rows before the step sees them.  `with_loss` sums the loss on the device (one more
+    launch per micro-batch) for the mean training loss over all ranks.  `label`: progress text `<label> | loss` with the
+    rate in the extra column instead of `train | loss | img/s`."""
     model.train()
     start = perf_counter()
     if not zero_grad_first:
         opt.zero_grad(set_to_none=True)
+    loss_sum = torch.zeros((), dtype=torch.float64, device=device) if with_loss else None
     seen_total = pending = 0
     shown = float("nan")
-    for i, (inputs, targets) in enumerate(_base.device_batches(dl, device, tail, prefetch=stepper is not None), 1):
+    for i, (inputs, targets) in enumerate(device_batches(dl, device, tail, prefetch=stepper is not None), 1):
         if mixer is not None:
             inputs, targets = mixer(inputs, targets)        # outside of the captured step: one launch on this stream
         if stepper is not None:
-            # hipGraph replay of the same body; zero_grad belongs to the first micro-batch of a cycle either way
+            # zero_grad is part of the "first" body; `last` lets an eager micro-batch overlap the DP exchange with its backward
             loss = stepper.micro_batch(inputs, targets, first=pending == 0, last=pending + 1 == accum_steps)
             pending += 1
             if pending == accum_steps:
@@ -122,7 +292,7 @@ def train_one_epoch(model: nn.Module, dl: DataLoader, opt: optim.Optimizer, scal
                 if accum_steps > 1:
                     loss = loss / accum_steps
             if reducer is not None and pending + 1 == accum_steps:
-                reducer.arm()
+                reducer.arm()                   # this backward completes the step: buckets leave as they fill
             scaler.scale(loss).backward()
             pending += 1
             if pending == accum_steps:
@@ -137,14 +307,16 @@ def train_one_epoch(model: nn.Module, dl: DataLoader, opt: optim.Optimizer, scal
                 pending = 0
         bsz = targets.size(0)
         seen_total += bsz
+        if with_loss:
+            loss_sum += loss.detach().double() * (bsz * max(1, accum_steps))
         if i % LOG_EVERY == 0 or i == len(dl):
             shown = float(loss.detach()) * max(1, accum_steps)          # the only host sync of the loop
         seen = min(i * (dl.batch_size or bsz), len(dl.sampler) if dl.sampler is not None else len(dl.dataset))
         ips = seen / max(1e-6, perf_counter() - start)
-        if ips_in_extra:
+        if label is not None:
             progress.update(task, advance=1, description=f"{label} | loss={shown:.4f}", extra=f"{ips:.0f} img/s")
         else:
-            progress.update(task, advance=1, description=f"{label} | loss={shown:.4f} | {ips:.0f} img/s")
+            progress.update(task, advance=1, description=f"train | loss={shown:.4f} | {ips:.0f} img/s")
     if pending > 0:
         if stepper is not None:
             stepper.optimizer_step()
@@ -159,12 +331,18 @@ def train_one_epoch(model: nn.Module, dl: DataLoader, opt: optim.Optimizer, scal
     if str(device).startswith("cuda"):
         torch.cuda.synchronize()
     seconds = perf_counter() - start
-    return {"images": seen_total, "seconds": seconds, "images_per_sec": seen_total / max(1e-9, seconds),
-            "launch": "hipgraph" if (stepper is not None and stepper.replays > 0 and not stepper.failed) else "eager"}
+    stats = {"images": seen_total, "seconds": seconds, "images_per_sec": seen_total / max(1e-9, seconds),
+             "launch": "hipgraph" if (stepper is not None and stepper.replays > 0 and not stepper.failed) else "eager"}
+    if not with_loss:
+        return EpochResult(stats)
+    (total_loss,) = all_reduce_counts(float(loss_sum), device=device)
+    (total_seen,) = all_reduce_counts(float(seen_total), device=device)
+    return EpochResult(stats, total_loss / max(1.0, total_seen))
 
 
 def log_throughput(env, chief: bool, world: int, **record) -> None:
-    """One JSON line per phase in OUTPUT_DIR/logs/throughput.jsonl (machine-readable img/s)."""
+    """One JSON line per phase in OUTPUT_DIR/logs/throughput.jsonl: the machine-readable twin of the progress bar's
+    `img/s`."""
     if not chief:
         return
     path = Path(env.logs_dir) / "throughput.jsonl"
@@ -177,8 +355,8 @@ def log_throughput(env, chief: bool, world: int, **record) -> None:
 
 
 def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
+    global console
     console = create_console()
-    _base.console = console
     env = prepare_training_environment(weights_name=spec.best_weights_name, best_checkpoint_name="best.ckpt",
                                        latest_checkpoint_name="latest.ckpt")
     apply_seed(env.seed)
@@ -189,6 +367,9 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
     num_classes = env_int("NUM_CLASSES", 2)
     ft_lr, ft_wd = env_float("LR", spec.ft_lr), env_float("WEIGHT_DECAY", spec.ft_wd)
     patience = env_int("EARLY_STOP_PATIENCE", spec.default_patience)
+    ft_batch, accum = spec.ft_batch_size, spec.ft_accum_steps if spec.ft_batch_size is not None else 1
+    if spec.ft_from_env:
+        ft_batch, accum = env_int("FT_BATCH_SIZE", ft_batch), env_int("ACCUM_STEPS", accum)
     # the reference's trainers ignore the YAML's model name; this one honours MODEL_NAME when the
     # orchestrator exports it, so the registry's prefix entries (faster_vit_0_224, efficientformerv2_s0, ...) train too
     model_name = env_str("MODEL_NAME", spec.model_name)
@@ -211,13 +392,15 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
         console.print(f"[bold red]Dataset not found under[/] {data_root}")
         console.print(f"Expected: {data_root}/{train_split}/<class> and {data_root}/{val_split}/<class>")
         raise SystemExit(1)
-    _base.policy_settings()     # a bad training.rand_augment_* / trivial_augment is a ValueError here
+    policy_settings()       # a bad training.rand_augment_* / trivial_augment is a ValueError here, not a class-count message below
     try:
+        # $GPU_INPUT_TAIL (YAML training.gpu_input_tail): loaders ship uint8 batches, the device does
+        # flip / to-float / normalise / erasing
         gpu_tail = use_cuda and (env_str("GPU_INPUT_TAIL", "0").lower() in {"1", "true", "yes"}
                                  or env_str("GPU_RESIZE", "0").lower() in {"1", "true", "yes"})     # device resize implies the device tail
-        train_dl, val_dl, *tails = _base.get_loaders(data_root, train_split, val_split, img_size, batch_size, num_workers,
-                                                     expected_classes=num_classes, rank=rank, world=world, seed=env.seed or 0,
-                                                     gpu_tail=gpu_tail, transform_kwargs=spec.transform_kwargs)
+        train_dl, val_dl, *tails = get_loaders(data_root, train_split, val_split, img_size, batch_size, num_workers,
+                                               expected_classes=num_classes, rank=rank, world=world, seed=env.seed or 0,
+                                               gpu_tail=gpu_tail, transform_kwargs=spec.transform_kwargs)
         train_tail, val_tail = tails if tails else (None, None)
     except ValueError as exc:
         console.print("[bold red]Class configuration mismatch[/]", f"→ {exc}")
@@ -227,14 +410,16 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
                   f"steps/epoch={len(train_dl)}" + (f" | ranks={world}" if world > 1 else ""))
 
     builder = get_model_spec(model_name).builder
-    model = builder(model_name, num_classes, img_size) if spec.pass_img_size else builder(model_name, num_classes)
-    _base._load_pretrained(model, model_name)
+    build = lambda: builder(model_name, num_classes, img_size) if spec.pass_img_size else builder(model_name, num_classes)  # noqa: E731
+    model = build()
+    _load_pretrained(model, model_name)
     model.to(memory_format=torch.channels_last)
     model = model.to(device)
     broadcast_module_state(model)
-    criterion, make_opt = _base._make_criterion_and_optimizer(use_cuda)
-    mixer = _base.make_mixer(_base.mix_settings(), num_classes, device)      # Mixup / CutMix ($MIXUP_ALPHA, $CUTMIX_ALPHA)
-    scaler = torch.amp.GradScaler(enabled=False)
+    criterion, make_opt = _make_criterion_and_optimizer(use_cuda)
+    eval_criterion = criterion if spec.report_loss else None
+    mixer = make_mixer(mix_settings(), num_classes, device)      # Mixup / CutMix ($MIXUP_ALPHA, $CUTMIX_ALPHA)
+    scaler = torch.amp.GradScaler(enabled=False)        # bf16 needs no loss scaling; calls kept for parity
     opt_extra = {"grad_scale": 1.0 / world} if use_cuda else {}
 
     progress = Progress(TextColumn("[bold blue]{task.description}"), BarColumn(bar_width=None), MofNCompleteColumn(),
@@ -252,50 +437,44 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
             reducer = GradAllReducer(head, arena=getattr(warm_opt, "arena", None)) if world > 1 else None
             if reducer is not None:
                 reducer.attach()
-            task = progress.add_task("warmup", total=len(train_dl), extra="")
+            task = progress.add_task(spec.warmup_task, total=len(train_dl), extra="")
             console.print("[bold]Warmup (head only)[/]")
-            # the reference's inline warm-up loop (efficientformer_v2.py:362-382 / fastervit.py:408-428) is
+            # the reference's inline warm-up loops (efficientformer_v2.py:362-382 / fastervit.py:408-428) are
             # train_one_epoch with zero_grad first, no accumulation and the rate in the `extra` column
-            stats = train_one_epoch(model, train_dl, warm_opt, scaler, criterion, device, use_cuda_amp=use_cuda, progress=progress,
-                                    task=task, accum_steps=1, zero_grad_first=True, reducer=reducer, tail=train_tail,
-                                    label="warmup", ips_in_extra=True, mixer=mixer,
-                                    stepper=_base.make_stepper(model, criterion, warm_opt, accum_steps=1, use_cuda=use_cuda, world=world,
-                                                                 reducer=reducer))
-            log_throughput(env, chief, world, phase="warmup", epoch=0, model=model_name, batch_size=batch_size, **stats)
+            done = train_one_epoch(model, train_dl, warm_opt, scaler, criterion, device, use_cuda_amp=use_cuda, progress=progress,
+                                   task=task, accum_steps=1, zero_grad_first=spec.warmup_zero_grad_first, reducer=reducer,
+                                   tail=train_tail, label=spec.warmup_label, mixer=mixer, with_loss=spec.report_loss,
+                                   stepper=make_stepper(model, criterion, warm_opt, accum_steps=1, use_cuda=use_cuda, world=world,
+                                                        reducer=reducer))
+            log_throughput(env, chief, world, phase="warmup", epoch=0, model=model_name, batch_size=batch_size, **done.stats)
             if reducer is not None:
                 reducer.detach()
-            res = evaluate(model, val_dl, device, val_tail)
+            res = evaluate(model, val_dl, device, val_tail, eval_criterion)
             best_val_acc, best_epoch, warmup_done = res.acc, 0, True
-            console.print(f"[bold cyan]warmup[/] | val_acc={best_val_acc:.4f}")
+            console.print("[bold cyan]warmup[/] | " + spec.warmup_line.format(res=res))
             if getattr(warm_opt, "arena", None) is not None:
                 warm_opt.zero_grad()
                 warm_opt.arena.release()
 
         for name, p in model.named_parameters():
             p.requires_grad = spec.unfreeze_keys is None or any(key in name for key in spec.unfreeze_keys)
-        ft_dl, accum = train_dl, 1
-        if spec.ft_batch_size is not None:
-            accum = spec.ft_accum_steps
-            console.print(f"[bold]Fine-tune[/]: bs={spec.ft_batch_size}, accum_steps={accum} "
-                          f"(effective ≈ {spec.ft_batch_size * accum * world})")
-            ft_dl = _base.make_loader(train_dl.dataset, spec.ft_batch_size, num_workers, shuffle=True, rank=rank, world=world,
-                                      seed=env.seed or 0)
-        opt = make_opt([p for p in model.parameters() if p.requires_grad], lr=ft_lr, weight_decay=ft_wd, **opt_extra)
-        reducer = GradAllReducer([p for p in model.parameters() if p.requires_grad],
-                                 arena=getattr(opt, "arena", None)) if world > 1 else None
+        ft_dl = train_dl
+        if ft_batch is not None:
+            console.print(f"[bold]Fine-tune[/]: bs={ft_batch}, accum_steps={accum} (effective ≈ {ft_batch * accum * world})")
+            ft_dl = make_loader(train_dl.dataset, ft_batch, num_workers, shuffle=True, rank=rank, world=world, seed=env.seed or 0)
+        trainable = [p for p in model.parameters() if p.requires_grad]
+        opt = make_opt(trainable, lr=ft_lr, weight_decay=ft_wd, **opt_extra)
+        reducer = GradAllReducer(trainable, arena=getattr(opt, "arena", None)) if world > 1 else None
         if reducer is not None:
             reducer.attach()
         scheduler = optim.lr_scheduler.CosineAnnealingLR(opt, T_max=max(1, epochs - 1))
         # weight EMA ($EMA_DECAY): starts here as a copy of the warmed-up model, or from the checkpoint's model_ema
-        ema_cfg = _base.ema_settings()
-        ema = None if ema_cfg is None else _base.make_model_ema(
-            model, lambda: builder(model_name, num_classes, img_size) if spec.pass_img_size else builder(model_name, num_classes),
-            device, ema_cfg)
-        stepper = _base.make_stepper(model, criterion, opt, accum_steps=accum, use_cuda=use_cuda, world=world, reducer=reducer,
-                                     ema=ema)
+        ema_cfg = ema_settings()
+        ema = None if ema_cfg is None else make_model_ema(model, build, device, ema_cfg)
+        stepper = make_stepper(model, criterion, opt, accum_steps=accum, use_cuda=use_cuda, world=world, reducer=reducer, ema=ema)
         start_epoch = 0
         resume_state = maybe_load_checkpoint(env, model=model, optimizer=opt, scheduler=scheduler)
-        _base.restore_model_ema(ema, resume_state)
+        restore_model_ema(ema, resume_state)
         if resume_state is not None:
             start_epoch = int(resume_state.get("epoch", 0))
             best_val_acc = float(resume_state.get("best_val_acc", best_val_acc))
@@ -308,23 +487,19 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
             if hasattr(ft_dl.sampler, "set_epoch"):
                 ft_dl.sampler.set_epoch(epoch)
             task = progress.add_task(f"epoch {epoch}", total=len(ft_dl), extra="")
-            stats = train_one_epoch(model, ft_dl, opt, scaler, criterion, device, use_cuda_amp=use_cuda, progress=progress, task=task,
-                                    accum_steps=accum, zero_grad_first=spec.zero_grad_first, reducer=reducer, tail=train_tail,
-                                    stepper=stepper, ema=ema, mixer=mixer)
+            done = train_one_epoch(model, ft_dl, opt, scaler, criterion, device, use_cuda_amp=use_cuda, progress=progress, task=task,
+                                   accum_steps=accum, zero_grad_first=spec.zero_grad_first, reducer=reducer, tail=train_tail,
+                                   stepper=stepper, ema=ema, mixer=mixer, with_loss=spec.report_loss)
             log_throughput(env, chief, world, phase="fine-tune", epoch=epoch, model=model_name,
-                           batch_size=ft_dl.batch_size, accum_steps=accum, **stats)
+                           batch_size=ft_dl.batch_size, accum_steps=accum, **done.stats)
             scheduler.step()
-            res = evaluate(model, val_dl, device, val_tail)
-            if spec.early_stop:
-                console.print(f"[bold cyan]epoch {epoch}[/] | val_acc={res.acc:.4f} ({res.correct}/{res.total}) | "
-                              f"lr={scheduler.get_last_lr()[0]:.2e}")
-            else:
-                console.print(f"[bold cyan]epoch {epoch}[/] | val_acc={res.acc:.4f}")
+            res = evaluate(model, val_dl, device, val_tail, eval_criterion)
+            console.print(f"[bold cyan]epoch {epoch}[/] | "
+                          + spec.epoch_line.format(res=res, train_loss=done.loss, lr=scheduler.get_last_lr()[0]))
             acc = res.acc
             if ema is not None:
-                res_ema = evaluate(ema.module, val_dl, device, val_tail)
-                console.print(f"[bold cyan]epoch {epoch} EMA[/] | val_acc={res_ema.acc:.4f} ({res_ema.correct}/{res_ema.total}) | "
-                              f"updates={ema.updates}")
+                res_ema = evaluate(ema.module, val_dl, device, val_tail, eval_criterion)
+                console.print(f"[bold cyan]epoch {epoch} EMA[/] | " + spec.ema_line.format(res=res_ema) + f" | updates={ema.updates}")
                 if ema_cfg.select:
                     acc = res_ema.acc
             improved = acc > best_val_acc + 1e-4
@@ -335,7 +510,7 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
             if chief:
                 state = save_latest_checkpoint(env, model=model, optimizer=opt, scheduler=scheduler, epoch=epoch,
                                                best_val_acc=best_val_acc, best_epoch=best_epoch,
-                                               extra={"warmup_done": warmup_done, **_base.ema_checkpoint_extra(ema)})
+                                               extra={"warmup_done": warmup_done, **ema_checkpoint_extra(ema)})
                 if improved:
                     save_best_checkpoint(env, state, weights_key="model_ema" if ema is not None and ema_cfg.select else "model")
                     console.print(f"[bold green]new best[/] val_acc={best_val_acc:.4f} (epoch {best_epoch}) → saved "
@@ -347,6 +522,3 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
 
     console.print(f"[bold green]Best weights saved →[/] {env.best_weights_path.resolve()}")
     console.print(f"[bold green]Best checkpoint saved →[/] {env.best_checkpoint_path.resolve()}")
-
-
-__all__ = ["EvalResult", "TrainerSpec", "evaluate", "log_throughput", "run", "train_one_epoch"]

@@ -5,8 +5,7 @@ head-only warm-up epoch (names containing "classifier" or "head", :349-387 — t
 `talking_head1/2` and `head_dist`), then fine-tuning of the parameters whose names contain any of UNFREEZE_KEYS
 (:66-74, :389-393: the backward pass stops at the earliest such parameter, stages.2.blocks.3), BATCH_SIZE batches,
 no accumulation, no early stop, accuracy-only evaluation, `EfficientFormerV2_S1.pth` / latest.ckpt / best.ckpt.
-The loop body lives in trainers/_engine.py (shared with the FasterViT trainer); `TrainerSpec` below is the list of
-what this script does differently from the EfficientNet one.
+The loops live in trainers/_engine.py, shared by all three trainers; `SPEC` below is what this script does differently.
 """
 
 from __future__ import annotations

@@ -1,4 +1,5 @@
-"""Throughput of the drop-in trainer loop (`trainers.efficientnet.train_one_epoch`), eager dispatch vs hipGraph replay.
+"""Throughput of the drop-in trainer loop (`trainers._engine.train_one_epoch`, with the EfficientNet trainer's loss sum),
+eager dispatch vs hipGraph replay.
 
     python scripts/bench_trainer.py [--model efficientnet_b0] [--steps 60] [--ema DECAY] [--cases 32x4,256x1]
                                     [--mixup A] [--cutmix A] [--mix-mode batch|pair|elem]
@@ -58,7 +59,7 @@ def main() -> None:
     from deepfakedetection_amd.mix import BatchMixer
     from deepfakedetection_amd.optim import HipAdamW, HipCrossEntropyLoss
     from deepfakedetection_amd.orchestration.model_registry import get_model_spec
-    from deepfakedetection_amd.trainers.efficientnet import train_one_epoch
+    from deepfakedetection_amd.trainers._engine import train_one_epoch
 
     cases = [tuple(int(v) for v in c.split("x")) for c in args.cases.split(",")]
     for batch, accum in cases:
@@ -78,12 +79,12 @@ def main() -> None:
                 warm = FakeLoader(batch, args.size, 3 * accum, 2)
                 train_one_epoch(model, warm, opt, scaler, crit, "cuda", use_cuda_amp=True, progress=progress,
                                 task=progress.add_task("w", total=len(warm)), accum_steps=accum, stepper=stepper, ema=ema,
-                                mixer=mixer)
+                                mixer=mixer, with_loss=True)
                 dl = FakeLoader(batch, args.size, steps, 2)
-                stats: dict = {}
-                loss = train_one_epoch(model, dl, opt, scaler, crit, "cuda", use_cuda_amp=True, progress=progress,
-                                       task=progress.add_task("t", total=len(dl)), accum_steps=accum, stepper=stepper, stats=stats, ema=ema,
-                                       mixer=mixer)
+                done = train_one_epoch(model, dl, opt, scaler, crit, "cuda", use_cuda_amp=True, progress=progress,
+                                       task=progress.add_task("t", total=len(dl)), accum_steps=accum, stepper=stepper, ema=ema,
+                                       mixer=mixer, with_loss=True)
+            stats, loss = done.stats, done.loss
             print(json.dumps({"model": args.model, "micro_batch": batch, "accum_steps": accum, "ema": args.ema,
                               "mixup": args.mixup, "cutmix": args.cutmix,
                               "requested": "hipgraph" if graph else "eager",

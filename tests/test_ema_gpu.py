@@ -213,12 +213,10 @@ def test_orchestrated_training_with_ema_resume_and_inference(tmp_path, monkeypat
     state dict when the EMA accuracy selects the epoch (the shadow's accuracy is reported as 1.0 here so that the epoch is
     selected deterministically), inference serves it, and a resumed run restores the EMA and continues its count."""
     from deepfakedetection_amd.orchestration.orchestrator import RunPaths, orchestrate, run_training_job
-    from deepfakedetection_amd.trainers import _engine
-    from deepfakedetection_amd.trainers import efficientnet as TE
+    from deepfakedetection_amd.trainers import _engine as mod      # where run() looks its loops up, for every trainer
 
     monkeypatch.chdir(tmp_path)
     vit = not model_name.startswith("efficientnet")
-    mod = _engine if vit else TE
     real_eval = mod.evaluate
     shadow_evals = []
 
@@ -231,14 +229,14 @@ def test_orchestrated_training_with_ema_resume_and_inference(tmp_path, monkeypat
 
     monkeypatch.setattr(mod, "evaluate", fake_eval)
     restored = []
-    real_restore = TE.restore_model_ema
+    real_restore = mod.restore_model_ema
 
     def spy_restore(ema, state):
         real_restore(ema, state)
         if ema is not None and state is not None:
             restored.append(({k: v.detach().cpu().clone() for k, v in ema.module.state_dict().items()}, ema.updates))
 
-    monkeypatch.setattr(TE, "restore_model_ema", spy_restore)
+    monkeypatch.setattr(mod, "restore_model_ema", spy_restore)
 
     _make_dataset(tmp_path / "data", classes=("fake", "real"), per_class=8, size=img + 8)
     base = {"seed": 1, "device": "cuda",

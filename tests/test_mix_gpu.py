@@ -289,7 +289,7 @@ def test_graph_replay_behind_the_mixer_equals_eager(accum):
 # ------------------------------------------------------------------ the orchestrated path
 def _spies(monkeypatch):
     """Counts of K.mix_batch / K.ce_loss_soft calls, and what every criterion the trainers build receives."""
-    from deepfakedetection_amd.trainers import efficientnet as TE
+    from deepfakedetection_amd.trainers import _engine
 
     calls = {"mix_batch": 0, "ce_loss_soft": 0}
     for name in calls:
@@ -301,7 +301,7 @@ def _spies(monkeypatch):
 
         monkeypatch.setattr(K, name, spy)
     seen = []                                                # (grad enabled, target dtype, target shape, logits shape, loss)
-    real_make = TE._make_criterion_and_optimizer
+    real_make = _engine._make_criterion_and_optimizer
 
     def make(use_cuda):
         crit, make_opt = real_make(use_cuda)
@@ -309,7 +309,7 @@ def _spies(monkeypatch):
             (torch.is_grad_enabled(), args[1].dtype, tuple(args[1].shape), tuple(args[0].shape), out.detach())))
         return crit, make_opt
 
-    monkeypatch.setattr(TE, "_make_criterion_and_optimizer", make)
+    monkeypatch.setattr(_engine, "_make_criterion_and_optimizer", make)
     return calls, seen
 
 
@@ -330,12 +330,10 @@ def test_orchestrated_training_with_mixing_and_inference(tmp_path, monkeypatch, 
     accuracy on 16 random pictures decides nothing: every evaluation is reported a little better than the one before, so
     that each epoch is the best so far and the best-weights file is written deterministically.)"""
     from deepfakedetection_amd.orchestration.orchestrator import orchestrate
-    from deepfakedetection_amd.trainers import _engine
-    from deepfakedetection_amd.trainers import efficientnet as TE
+    from deepfakedetection_amd.trainers import _engine as mod      # where run() looks its loops up, for every trainer
 
     monkeypatch.chdir(tmp_path)
     vit = not model_name.startswith("efficientnet")
-    mod = _engine if vit else TE
     real_eval = mod.evaluate
     evals = []
 
@@ -347,15 +345,15 @@ def test_orchestrated_training_with_mixing_and_inference(tmp_path, monkeypatch, 
     monkeypatch.setattr(mod, "evaluate", rising_eval)
     calls, seen = _spies(monkeypatch)
     epoch_losses = []
-    real_epoch = TE.train_one_epoch
+    real_epoch = mod.train_one_epoch
 
     def spy_epoch(*a, **k):
         assert k.get("mixer") is not None                    # warm-up and fine-tune both mix
-        loss = real_epoch(*a, **k)
-        epoch_losses.append(loss)
-        return loss
+        done = real_epoch(*a, **k)
+        epoch_losses.append(done.loss)
+        return done
 
-    monkeypatch.setattr(TE, "train_one_epoch", spy_epoch)
+    monkeypatch.setattr(mod, "train_one_epoch", spy_epoch)
     _make_dataset(tmp_path / "data", classes=("fake", "real"), per_class=8, size=img + 8)
     training = {"epochs": 2, "batch_size": 8, "ft_batch_size": 8, "accum_steps": 2, "num_workers": 0, "resume": "auto",
                 "pretrained": False, "img_size": img, "mixup_alpha": 0.8, "cutmix_alpha": 1.0, "mix_mode": "elem"}

@@ -8,6 +8,7 @@ is the product code.
 from __future__ import annotations
 
 import json
+import re
 from pathlib import Path
 
 import numpy as np
@@ -152,6 +153,108 @@ def test_other_two_trainers_end_to_end_on_cpu(workspace, trainer, weights, img_a
         assert n_state == len(list(TinyHeadNet(3).parameters())) and rows[1]["batch_size"] == 32 and rows[1]["accum_steps"] == 4
         assert "Fine-tune" in log and "accum_steps=4" in log
     assert (run / "checkpoints" / "best.ckpt").exists() == (run / weights).exists()
+
+
+_STUBS = {"efficientnet": lambda _name, nc: TinyNet(nc), "efficientformer_v2": lambda _name, nc, img_size=None: TinyHeadNet(nc),
+          "fastervit": lambda _name, nc: TinyHeadNet(nc)}
+_NUM, _ACC, _LR = r"\d+\.\d{4}", r"\d\.\d{4}", r"\d\.\d{2}e[-+]\d{2}"
+# what may follow a console record in train.log: the head of another one (nothing else belongs to the record before it)
+_NEXT = r"(?= (?:Fine-tune:|epoch \d+ |new best |Early stopping|warmup \| loss=|train \| loss=|Best weights saved))"
+
+
+def _train_stub(workspace: Path, trainer: str, **training) -> str:
+    """Seeded CPU training of trainers/<trainer>.py on its stub; the whitespace-normalised logs/train.log (rich wraps long
+    lines at the log's width)."""
+    name = f"stub_{trainer}"
+    reg.register_model_spec(reg.ModelSpec(name, f"deepfakedetection_amd.trainers.{trainer}", name, 32, _STUBS[trainer]))
+    cfg = yaml.safe_load(_config(workspace, training={"batch_size": 6, "num_workers": 0, "pretrained": False, **training}).read_text())
+    cfg["models"] = {name: {**cfg["models"]["tinynet_stub"], "output_dir": str(workspace / "runs" / name)}}
+    cfg["selection"] = [name]
+    path = workspace / f"{trainer}.yaml"
+    path.write_text(yaml.safe_dump(cfg))
+    orchestrate(path, mode="training")
+    run = sorted((workspace / "runs" / name).iterdir())[0]
+    return " ".join((run / "logs" / "train.log").read_text().split())
+
+
+def _records(log: str, pattern: str) -> list[str]:
+    """Console records of `log` that match `pattern` as a whole: from the start of a word to the head of the next record."""
+    return re.findall(r"(?<![^ ])" + pattern + _NEXT, log)
+
+
+@pytest.mark.parametrize("trainer", ["efficientnet", "efficientformer_v2", "fastervit"])
+def test_console_lines_per_trainer(workspace, trainer):
+    """The warm-up, fine-tune and epoch lines of each trainer keep the reference's shapes through the one engine."""
+    log = _train_stub(workspace, trainer, epochs=2)
+    counts = r" \(\d+/18\)"
+    if trainer == "efficientnet":
+        warm = rf"warmup \| val_acc={_ACC} \| val_loss={_NUM}{counts}"
+        epoch = rf"epoch \d \| train_loss={_NUM} \| val_loss={_NUM} \| val_acc={_ACC}{counts} \| lr={_LR}"
+    elif trainer == "efficientformer_v2":
+        warm, epoch = rf"warmup \| val_acc={_ACC}", rf"epoch \d \| val_acc={_ACC}"
+    else:
+        warm, epoch = rf"warmup \| val_acc={_ACC}", rf"epoch \d \| val_acc={_ACC}{counts} \| lr={_LR}"
+    assert len(_records(log, warm)) == 1, log
+    assert len(_records(log, epoch)) == 2, log
+    if trainer == "efficientformer_v2":
+        assert "Fine-tune" not in log
+    else:
+        assert "Fine-tune: bs=32, accum_steps=4 (effective ≈ 128)" in log
+
+
+def test_specs_carry_the_reference_constants():
+    """One table over the three SPECs; and trainers/efficientnet.py owns no loop: its main / evaluate / train_one_epoch are
+    the engine's."""
+    import inspect
+
+    from deepfakedetection_amd.trainers import _engine, efficientformer_v2, efficientnet, fastervit
+
+    unfreeze = ("stages.3", "blocks.3", "layer4", "bneck", "features.6", "classifier", "head")
+    #        warm-up keys            fine-tune   ft batch, accum, from env   early  zg1st  img    weights file               epochs  batch
+    table = {
+        efficientnet: (("_fc", "classifier"), None, (32, 4, True), True, False, False, "EfficientNetModel.pth", 25, 64),
+        efficientformer_v2: (("classifier", "head"), unfreeze, (None, 1, False), False, True, True, "EfficientFormerV2_S1.pth", 5, 128),
+        fastervit: (("head",), None, (32, 4, False), True, False, False, "FasterVitModel.pth", 25, 64),
+    }
+    for mod, (warm, ft, (ft_bs, ft_accum, ft_env), early, zg_first, img, weights, epochs, batch) in table.items():
+        s = mod.SPEC
+        assert isinstance(s, _engine.TrainerSpec)
+        assert (s.warmup_keys, s.unfreeze_keys) == (warm, ft), mod.__name__
+        assert (s.ft_batch_size, s.ft_accum_steps, s.ft_from_env) == (ft_bs, ft_accum, ft_env), mod.__name__
+        assert (s.early_stop, s.zero_grad_first, s.pass_img_size) == (early, zg_first, img), mod.__name__
+        assert (s.best_weights_name, s.default_epochs, s.default_batch_size) == (weights, epochs, batch), mod.__name__
+        assert s.report_loss == (mod is efficientnet) and (s.transform_kwargs is None) == (mod is efficientnet)
+        assert mod.evaluate is _engine.evaluate and mod.train_one_epoch is _engine.train_one_epoch
+        source = inspect.getsource(mod)
+        assert "def train_one_epoch" not in source and "def evaluate" not in source and "device_batches(" not in source
+        assert inspect.getsource(mod.main).split(":", 1)[1].strip() == "run(SPEC)" and mod.run is _engine.run
+
+
+class _StubEma:
+    """What run() touches on an ema.ModelEma, for CPU modules (the product's EMA is a HIP kernel and refuses them)."""
+
+    def __init__(self, model: nn.Module, build, device: str, settings) -> None:
+        self.model, self.module, self.decay, self.updates = model, build().to(device), settings.decay, 0
+        self.module.load_state_dict(model.state_dict())
+        for p in self.module.parameters():
+            p.requires_grad = False
+
+    def step(self) -> None:
+        self.updates += 1
+        with torch.no_grad():
+            for shadow, p in zip(self.module.parameters(), self.model.parameters()):
+                shadow.lerp_(p, 1.0 - self.decay)
+
+
+@pytest.mark.parametrize("trainer", ["efficientnet", "fastervit"])
+def test_ema_console_line_per_trainer(workspace, monkeypatch, trainer):
+    from deepfakedetection_amd.trainers import _engine
+
+    monkeypatch.setattr(_engine, "make_model_ema", _StubEma)
+    log = _train_stub(workspace, trainer, epochs=1, ema_decay=0.9)
+    val_loss = rf"val_loss={_NUM} \| " if trainer == "efficientnet" else ""
+    assert len(_records(log, rf"epoch 1 EMA \| {val_loss}val_acc={_ACC} \(\d+/18\) \| updates=\d+")) == 1, log
+    assert ("EMA | val_loss=" in log) == (trainer == "efficientnet")
 
 
 def test_reference_train_yaml_fails_loudly_for_the_engine_that_is_not_built(workspace):
