@@ -25,6 +25,10 @@ ADAMW_TABLE_COLS = 5
 ADAMW_HP_LEN = 8
 EMA_TABLE_COLS = 4
 EMA_LERP, EMA_COPY = 0, 1
+CLIP_MODE_NORM, CLIP_MODE_VALUE = 0, 1
+CLIP_CFG_LEN = 2
+CLIP_STATE_LEN = 8
+(CLIP_NORM, CLIP_COEF, CLIP_SKIP, CLIP_STEPS, CLIP_CLIPPED, CLIP_SKIPPED, CLIP_NORM_SUM, CLIP_NORM_MAX) = range(8)
 MIX_JOB_WORDS = 8
 MIX_KEEP, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2
 MIX_NHWC, MIX_NCHW = 0, 1
@@ -112,6 +116,10 @@ SIGNATURES: dict[str, tuple] = {
     "dfd_ce_loss_soft": (c_int, [P, P, c_int, c_int, c_float, c_float, P, P, P, P]),
     # ---- ABI 139
     "dfd_augment_policy_u8": (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
+    # ---- ABI 140
+    "dfd_grad_sumsq": (c_int, [P, c_int, P, P]),
+    "dfd_grad_clip_finish": (c_int, [P, c_int, P, P, P, P]),
+    "dfd_adamw_step_clip": (c_int, [P, c_int, P, P, P, P]),
     # ---- ABI 111
     "dfd_bn_eval_coeffs_multi": (c_int, [P, c_int, P]),
     "dfd_sum_batch_begin": (c_int, []),
@@ -256,7 +264,8 @@ def check(code: int, op: str, detail: str = "") -> None:
 
 
 __all__ = [
-    "ACT_GELU", "ACT_NONE", "ACT_RELU", "ACT_SILU", "ADAMW_HP_LEN", "ADAMW_TABLE_COLS", "BF16", "EMA_COPY", "EMA_LERP", "EMA_TABLE_COLS", "F32",
+    "ACT_GELU", "ACT_NONE", "ACT_RELU", "ACT_SILU", "ADAMW_HP_LEN", "ADAMW_TABLE_COLS", "BF16", "CLIP_CFG_LEN", "CLIP_CLIPPED", "CLIP_COEF",
+    "CLIP_MODE_NORM", "CLIP_MODE_VALUE", "CLIP_NORM", "CLIP_NORM_MAX", "CLIP_NORM_SUM", "CLIP_SKIP", "CLIP_SKIPPED", "CLIP_STATE_LEN", "CLIP_STEPS", "EMA_COPY", "EMA_LERP", "EMA_TABLE_COLS", "F32",
     "MAX_PARTIALS", "MIX_CUTMIX", "MIX_JOB_WORDS", "MIX_KEEP", "MIX_MIXUP", "MIX_NCHW", "MIX_NHWC", "Mat", "PRO_AFFINE2", "PRO_BN_ACT", "PRO_BN_ACT_GATE", "PRO_NONE", "DwShape", "Prologue",
     "StemShape", "SIGNATURES", "check", "load", "c_int64",
 ]

@@ -948,8 +948,20 @@ extern "C" int dfd_softmax_argmax(const float* logits, int N, int J, float* prob
 // ===========================================================================
 // fused multi-tensor AdamW (torch.optim.AdamW semantics, decoupled weight decay)
 // ===========================================================================
+// CLIP: the dfd_adamw_step_clip instance.  cfg = {limit, mode}, state = the DFD_CLIP_* record dfd_grad_clip_finish wrote on
+// this stream just before.  The plain instance never touches either pointer and keeps its arithmetic.
+template <bool CLIP>
 __global__ void __launch_bounds__(DFD_THREADS)
-k_adamw(const int64_t* __restrict__ table, const float* __restrict__ hp) {
+k_adamw(const int64_t* __restrict__ table, const float* __restrict__ hp, const float* __restrict__ cfg,
+        const float* __restrict__ state) {
+    float coef = 1.f, lim = 0.f;
+    bool by_value = false;
+    if (CLIP) {
+        if (state[DFD_CLIP_SKIP] != 0.f) return;          // non-finite norm: the whole launch leaves p, exp_avg, exp_avg_sq alone
+        coef = state[DFD_CLIP_COEF];
+        lim = cfg[0];
+        by_value = cfg[1] != 0.f;
+    }
     const int64_t* row = table + (long)blockIdx.x * DFD_ADAMW_TABLE_COLS;
     float* p = reinterpret_cast<float*>(row[0]);
     const float* g = reinterpret_cast<const float*>(row[1]);
@@ -960,6 +972,7 @@ k_adamw(const int64_t* __restrict__ table, const float* __restrict__ hp) {
     const float step = lr / bc1, rs2 = 1.0f / sqrtf(bc2), decay = 1.f - lr * wd;
     auto upd = [&](float& pp, float gg, float& mm, float& vv) {
         gg *= gs;
+        if (CLIP) gg = by_value ? fminf(fmaxf(gg, -lim), lim) : gg * coef;
         mm = b1 * mm + (1.f - b1) * gg;
         vv = b2 * vv + (1.f - b2) * gg * gg;
         pp = pp * decay - step * (mm / (sqrtf(vv) * rs2 + eps));
@@ -976,7 +989,95 @@ k_adamw(const int64_t* __restrict__ table, const float* __restrict__ hp) {
 }
 extern "C" int dfd_adamw_step(const int64_t* table, int nchunks, const float* hp, dfd_stream stream) {
     if (!table || !hp || nchunks < 1) return DFD_EINVAL;
-    hipLaunchKernelGGL(k_adamw, dim3(nchunks), dim3(DFD_THREADS), 0, (hipStream_t)stream, table, hp);
+    hipLaunchKernelGGL(k_adamw<false>, dim3(nchunks), dim3(DFD_THREADS), 0, (hipStream_t)stream, table, hp, (const float*)nullptr,
+                       (const float*)nullptr);
+    return DFD_CHECK_LAUNCH();
+}
+extern "C" int dfd_adamw_step_clip(const int64_t* table, int nchunks, const float* hp, const float* cfg, const float* state,
+                                   dfd_stream stream) {
+    if (!table || !hp || !cfg || !state || nchunks < 1) return DFD_EINVAL;
+    hipLaunchKernelGGL(k_adamw<true>, dim3(nchunks), dim3(DFD_THREADS), 0, (hipStream_t)stream, table, hp, cfg, state);
+    return DFD_CHECK_LAUNCH();
+}
+
+// ===========================================================================
+// gradient clipping (optim.HipAdamW max_grad_norm): global L2 norm of the gradients behind an AdamW chunk table
+// ===========================================================================
+// Sum over one workgroup in a fixed order: xor butterfly inside each wave (every lane ends with the same bits, since each
+// level adds the same two values in either order), then the four wave sums as (w0 + w1) + (w2 + w3).  Valid in thread 0.
+__device__ __forceinline__ double clip_block_sum(double acc, double* sm) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    return (sm[0] + sm[1]) + (sm[2] + sm[3]);
+}
+// One workgroup per table row: partials[row] = sum of g^2 in f64 (the square of an f32 is exact there).  Quad q = elements
+// 4q .. 4q+3 belongs to thread q % DFD_THREADS, which adds its quads in rising order and x, y, z, w inside a quad; the 16-byte
+// path only fetches a whole quad in one load, so a chunk gives the same bits at any alignment.
+__global__ void __launch_bounds__(DFD_THREADS)
+k_grad_sumsq(const int64_t* __restrict__ table, double* __restrict__ partials) {
+    __shared__ double sm[DFD_THREADS / 64];
+    const int64_t* row = table + (long)blockIdx.x * DFD_ADAMW_TABLE_COLS;
+    const float* g = reinterpret_cast<const float*>(row[1]);
+    const int cnt = (int)row[4];
+    const bool vec = (row[1] & 15) == 0;
+    const int nq = (cnt + 3) / 4;
+    double acc = 0.0;
+    for (int q = threadIdx.x; q < nq; q += DFD_THREADS) {
+        const int e = q * 4;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);                  // + 0.0 leaves a non-negative sum unchanged
+        if (vec && e + 3 < cnt) {
+            v = reinterpret_cast<const float4*>(g)[q];
+        } else {
+            v.x = g[e];
+            if (e + 1 < cnt) v.y = g[e + 1];
+            if (e + 2 < cnt) v.z = g[e + 2];
+            if (e + 3 < cnt) v.w = g[e + 3];
+        }
+        acc += (double)v.x * (double)v.x;
+        acc += (double)v.y * (double)v.y;
+        acc += (double)v.z * (double)v.z;
+        acc += (double)v.w * (double)v.w;
+    }
+    const double s = clip_block_sum(acc, sm);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+extern "C" int dfd_grad_sumsq(const int64_t* table, int nchunks, double* partials, dfd_stream stream) {
+    if (!table || !partials || nchunks < 1) return DFD_EINVAL;
+    hipLaunchKernelGGL(k_grad_sumsq, dim3(nchunks), dim3(DFD_THREADS), 0, (hipStream_t)stream, table, partials);
+    return DFD_CHECK_LAUNCH();
+}
+// One workgroup: thread t adds partials[t], partials[t + DFD_THREADS], ... in that order, then the tree above; thread 0 turns
+// the sum into the norm, the coefficient and the skip flag (f32, torch.nn.utils.clip_grad_norm_'s formula) and keeps the
+// running record.
+__global__ void __launch_bounds__(DFD_THREADS)
+k_grad_clip_finish(const double* __restrict__ partials, int n, const float* __restrict__ hp, const float* __restrict__ cfg,
+                   float* __restrict__ state) {
+    __shared__ double sm[DFD_THREADS / 64];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += DFD_THREADS) acc += partials[i];
+    const double sum = clip_block_sum(acc, sm);
+    if (threadIdx.x != 0) return;
+    const float total = (float)sqrt(sum) * hp[7];
+    const bool skip = !isfinite(total);
+    const float coef = cfg[1] != 0.f ? 1.0f : fminf(cfg[0] / (total + 1e-6f), 1.0f);
+    state[DFD_CLIP_NORM] = total;
+    state[DFD_CLIP_COEF] = coef;
+    state[DFD_CLIP_SKIP] = skip ? 1.f : 0.f;
+    state[DFD_CLIP_STEPS] += 1.f;
+    if (skip) {
+        state[DFD_CLIP_SKIPPED] += 1.f;
+    } else {
+        if (coef < 1.0f) state[DFD_CLIP_CLIPPED] += 1.f;
+        state[DFD_CLIP_NORM_SUM] += total;
+        state[DFD_CLIP_NORM_MAX] = fmaxf(state[DFD_CLIP_NORM_MAX], total);
+    }
+}
+extern "C" int dfd_grad_clip_finish(const double* partials, int nchunks, const float* hp, const float* cfg, float* state,
+                                    dfd_stream stream) {
+    if (!partials || !hp || !cfg || !state || nchunks < 1) return DFD_EINVAL;
+    hipLaunchKernelGGL(k_grad_clip_finish, dim3(1), dim3(DFD_THREADS), 0, (hipStream_t)stream, partials, nchunks, hp, cfg, state);
     return DFD_CHECK_LAUNCH();
 }
 

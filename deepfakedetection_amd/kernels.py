@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import (
-    ACT_NONE, ACT_SILU, BF16, F32, MAX_PARTIALS, MIX_CUTMIX, MIX_JOB_WORDS, MIX_KEEP, MIX_NCHW, MIX_NHWC, PRO_AFFINE2, PRO_BN_ACT,
+    ACT_NONE, ACT_SILU, BF16, CLIP_CFG_LEN, CLIP_STATE_LEN, F32, MAX_PARTIALS, MIX_CUTMIX, MIX_JOB_WORDS, MIX_KEEP, MIX_NCHW, MIX_NHWC, PRO_AFFINE2, PRO_BN_ACT,
     PRO_BN_ACT_GATE, PRO_NONE, DwShape, Prologue, StemShape, check,
 )
 
@@ -1266,6 +1266,26 @@ def cam_render(cam: torch.Tensor, size: tuple[int, int], image: torch.Tensor | N
 
 def adamw_step(table: torch.Tensor, hp: torch.Tensor) -> None:
     check(_L().dfd_adamw_step(_p(table), table.shape[0], _p(hp), _stream()), "dfd_adamw_step")
+
+
+def grad_sumsq(table: torch.Tensor, partials: torch.Tensor) -> None:
+    """One dfd_grad_sumsq launch over an AdamW chunk table: partials[row] (f64, device) = sum of the squares of the row's gradients."""
+    if partials.dtype != torch.float64 or partials.numel() < table.shape[0]:
+        raise ValueError("grad_sumsq needs one f64 partial per table row")
+    check(_L().dfd_grad_sumsq(_p(table), table.shape[0], _p(partials), _stream()), "dfd_grad_sumsq")
+
+
+def grad_clip_finish(partials: torch.Tensor, hp: torch.Tensor, cfg: torch.Tensor, state: torch.Tensor) -> None:
+    """One dfd_grad_clip_finish launch: the f64 partials become the norm, the coefficient and the skip flag in `state` (f32,
+    CLIP_STATE_LEN); `hp` is the AdamW record (grad_scale), `cfg` = {limit, mode} in device memory."""
+    if partials.dtype != torch.float64 or state.numel() != CLIP_STATE_LEN or cfg.numel() != CLIP_CFG_LEN:
+        raise ValueError("grad_clip_finish needs f64 partials, a CLIP_CFG_LEN cfg and a CLIP_STATE_LEN state")
+    check(_L().dfd_grad_clip_finish(_p(partials), partials.numel(), _p(hp), _p(cfg), _p(state), _stream()), "dfd_grad_clip_finish")
+
+
+def adamw_step_clip(table: torch.Tensor, hp: torch.Tensor, cfg: torch.Tensor, state: torch.Tensor) -> None:
+    """dfd_adamw_step with the gradient clipped as `cfg` and `state` (written by grad_clip_finish on this stream) say."""
+    check(_L().dfd_adamw_step_clip(_p(table), table.shape[0], _p(hp), _p(cfg), _p(state), _stream()), "dfd_adamw_step_clip")
 
 
 def ema_update(table: torch.Tensor, w: torch.Tensor) -> None:

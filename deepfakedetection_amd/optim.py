@@ -9,15 +9,33 @@ checkpoints written by train_env.save_latest_checkpoint stay interchangeable.
 
 from __future__ import annotations
 
+import math
+
 import torch
 from torch import nn
 
 from . import kernels as K
-from ._lib import ADAMW_HP_LEN
+from ._lib import (
+    ADAMW_HP_LEN, CLIP_CFG_LEN, CLIP_CLIPPED, CLIP_MODE_NORM, CLIP_MODE_VALUE, CLIP_NORM, CLIP_NORM_MAX, CLIP_NORM_SUM, CLIP_SKIPPED,
+    CLIP_STATE_LEN, CLIP_STEPS,
+)
 from .arena import GradArena
 from .functions import CrossEntropyFunction
 
 _CHUNK = 4096          # elements per workgroup of the fused kernel (~1000 workgroups for EfficientNet-B0)
+_CLIP_MODES = {"norm": CLIP_MODE_NORM, "value": CLIP_MODE_VALUE}
+
+
+def check_clip(limit, mode: str) -> tuple[float | None, str]:
+    """(limit or None, mode) of a gradient-clipping request; ValueError for a limit <= 0, a non-finite limit or an unknown mode."""
+    if mode not in _CLIP_MODES:
+        raise ValueError(f"clip_mode must be one of {sorted(_CLIP_MODES)}, got {mode!r}")
+    if limit is None:
+        return None, mode
+    limit = float(limit)
+    if not math.isfinite(limit) or limit <= 0.0:
+        raise ValueError(f"max_grad_norm must be a finite number > 0 (or None for no clipping), got {limit!r}")
+    return limit, mode
 
 
 class HipCrossEntropyLoss(nn.Module):
@@ -35,12 +53,31 @@ class HipCrossEntropyLoss(nn.Module):
 
 
 class HipAdamW(torch.optim.Optimizer):
-    """AdamW (decoupled weight decay, bias correction) as one kernel launch per group."""
+    """AdamW (decoupled weight decay, bias correction) as one kernel launch per group.
+
+    `max_grad_norm` turns gradient clipping on (None: off, and then the launches are exactly the ones above).  With
+    `clip_mode="norm"` the gradients of ALL groups are scaled by min(1, limit / (norm + 1e-6)), norm being their global L2 norm
+    after `grad_scale`: torch.nn.utils.clip_grad_norm_'s formula, in f32, from an f64 sum of squares.  With "value" every
+    gradient element is clamped to [-limit, limit] (clip_grad_value_).  A step then is dfd_grad_sumsq per group, one
+    dfd_grad_clip_finish and dfd_adamw_step_clip per group, all capturable; the limit and the mode live in device memory and
+    are uploaded by prepare_step(), so set_clip() takes effect at the next replay of a captured step.
+
+    Unlike torch, a step whose norm is not finite (an inf or NaN gradient, in either mode) is SKIPPED: parameters and moments
+    stay as they are, which is what a GradScaler does for an overflowed step (clip_grad_norm_ would multiply by 0 or NaN).  The
+    host-side step counter still advances on a skipped step, so the bias corrections are one step ahead afterwards.
+    clip_stats() reports the norms and how many steps were clipped and skipped."""
 
     def __init__(self, params, lr: float = 1e-3, betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 1e-2, grad_scale: float = 1.0, use_arena: bool = True) -> None:
+                 weight_decay: float = 1e-2, grad_scale: float = 1.0, use_arena: bool = True,
+                 max_grad_norm: float | None = None, clip_mode: str = "norm") -> None:
+        limit, clip_mode = check_clip(max_grad_norm, clip_mode)
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale)
         super().__init__(params, defaults)
+        self._clip_limit, self._clip_mode = limit, clip_mode
+        self._clip_buffers: tuple[torch.Tensor, torch.Tensor, torch.Tensor] | None = None
+        if limit is not None:
+            self._check_clip_groups()
+            self._alloc_clip()
         self._tables: dict[int, tuple[tuple[int, ...], torch.Tensor, torch.Tensor]] = {}
         self._hp: dict[int, torch.Tensor] = {}
         self._shared_step: dict[int, torch.Tensor] = {}
@@ -50,6 +87,53 @@ class HipAdamW(torch.optim.Optimizer):
         trainable = [p for g in self.param_groups for p in g["params"] if p.requires_grad and p.is_cuda]
         if use_arena and trainable:
             self.arena = GradArena(trainable)
+
+    def _check_clip_groups(self) -> None:
+        scales = {float(g["grad_scale"]) for g in self.param_groups}
+        if len(scales) > 1:
+            raise ValueError(f"gradient clipping needs one grad_scale for all param groups (one global norm), got {sorted(scales)}")
+
+    def _alloc_clip(self) -> None:
+        """partials (one f64 per chunk of every parameter), cfg and the state record: allocated here, never under capture."""
+        if self._clip_buffers is not None:
+            return
+        params = [p for g in self.param_groups for p in g["params"]]
+        device = next((p.device for p in params if p.is_cuda), None)
+        if device is None:
+            return                              # nothing to step on a HIP device: step() raises like without clipping
+        nchunks = sum((p.numel() + _CHUNK - 1) // _CHUNK for p in params)
+        self._clip_buffers = (torch.zeros(max(1, nchunks), dtype=torch.float64, device=device),
+                              torch.zeros(CLIP_CFG_LEN, dtype=torch.float32, device=device),
+                              torch.zeros(CLIP_STATE_LEN, dtype=torch.float32, device=device))
+
+    def set_clip(self, limit: float | None, mode: str | None = None) -> None:
+        """Change the clipping limit (None: off) and, if given, the mode.  A captured step keeps its launches: switching
+        clipping on or off needs a new capture, a new limit or mode reaches the replay through prepare_step()."""
+        limit, mode = check_clip(limit, self._clip_mode if mode is None else mode)
+        if limit is not None:
+            self._check_clip_groups()
+        self._clip_limit, self._clip_mode = limit, mode
+        if limit is not None:
+            self._alloc_clip()
+
+    @property
+    def clip_state(self) -> torch.Tensor | None:
+        """The device record dfd_grad_clip_finish keeps (f32, CLIP_STATE_LEN; see include/dfd_hip.h), None without clipping."""
+        return None if self._clip_buffers is None else self._clip_buffers[2]
+
+    def clip_stats(self, reset: bool = True) -> dict | None:
+        """Norms and counts since the last reset, read with ONE host sync: {grad_norm_last, grad_norm_mean, grad_norm_max,
+        steps, clipped_steps, skipped_steps}; mean and max are over the steps with a finite norm.  None without clipping."""
+        if self._clip_limit is None or self._clip_buffers is None:
+            return None
+        state = self._clip_buffers[2]
+        rec = state.tolist()
+        if reset:
+            state.zero_()
+        steps, skipped = int(rec[CLIP_STEPS]), int(rec[CLIP_SKIPPED])
+        return {"grad_norm_last": rec[CLIP_NORM], "grad_norm_mean": rec[CLIP_NORM_SUM] / max(1, steps - skipped),
+                "grad_norm_max": rec[CLIP_NORM_MAX], "steps": steps, "clipped_steps": int(rec[CLIP_CLIPPED]),
+                "skipped_steps": skipped}
 
     def state_dict(self):
         """torch.optim.AdamW's format: every parameter gets its OWN `step` tensor.  Internally all parameters of a
@@ -131,6 +215,8 @@ class HipAdamW(torch.optim.Optimizer):
                 dev = torch.empty(ADAMW_HP_LEN, dtype=torch.float32, device=device)
                 self._hp[gi] = dev
             dev.copy_(torch.tensor(hp_vals, dtype=torch.float32))   # pageable source: host-synchronous staging
+        if self._clip_limit is not None and self._clip_buffers is not None:
+            self._clip_buffers[1].copy_(torch.tensor([self._clip_limit, float(_CLIP_MODES[self._clip_mode])], dtype=torch.float32))
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -141,6 +227,7 @@ class HipAdamW(torch.optim.Optimizer):
         capturing = torch.cuda.is_current_stream_capturing()
         if not capturing:
             self.prepare_step()
+        work = []
         for gi, group in enumerate(self.param_groups):
             entries = []
             for p in group["params"]:
@@ -158,7 +245,23 @@ class HipAdamW(torch.optim.Optimizer):
             if gi not in self._hp:
                 raise RuntimeError("HipAdamW.step() under stream capture needs prepare_step() before the capture")
             K.journal_note([t for e in entries for t in e])     # the table carries these addresses
-            K.adamw_step(self._table(gi, entries), self._hp[gi])
+            if self._clip_limit is None:
+                K.adamw_step(self._table(gi, entries), self._hp[gi])
+            else:
+                work.append((self._table(gi, entries), self._hp[gi]))
+        if work:
+            # one global norm over all groups: sum of squares per group into its slice of the partials, one finish, then the steps
+            if self._clip_buffers is None:
+                raise RuntimeError("HipAdamW clipping buffers are missing: the parameters were not on a HIP device at set_clip()")
+            partials, cfg, state = self._clip_buffers
+            K.journal_note([partials, cfg, state])
+            off = 0
+            for table, _ in work:
+                K.grad_sumsq(table, partials[off:off + table.shape[0]])
+                off += table.shape[0]
+            K.grad_clip_finish(partials[:off], work[0][1], cfg, state)
+            for table, hp in work:
+                K.adamw_step_clip(table, hp, cfg, state)
         return loss
 
 

@@ -31,6 +31,7 @@ minibatches over ranks, all-reduces gradients over RCCL, rank 0 logs and writes 
 from __future__ import annotations
 
 import json
+import math
 from dataclasses import dataclass, field
 from pathlib import Path
 from time import perf_counter, time
@@ -100,6 +101,7 @@ class EvalResult:
 class EpochResult:
     stats: dict                                     # throughput figures for logs/throughput.jsonl
     loss: float | None = None                       # mean training loss over all ranks (with_loss)
+    clip: dict | None = None                        # the epoch's gradient-clipping record (clip_settings() on)
 
 
 def eval_forward(model: nn.Module, device: str):
@@ -172,6 +174,66 @@ def restore_model_ema(ema, state: dict | None) -> None:
 
 def ema_checkpoint_extra(ema) -> dict:
     return {} if ema is None else {"model_ema": ema.module.state_dict(), "model_ema_updates": ema.updates}
+
+
+@dataclass(frozen=True)
+class ClipSettings:
+    limit: float
+    mode: str               # norm | value
+
+
+def clip_settings() -> ClipSettings | None:
+    """$CLIP_GRAD (YAML training.clip_grad, timm's --clip-grad; absent or 0: off) and $CLIP_MODE (training.clip_mode:
+    norm | value, default norm).  A negative or non-finite limit and an unknown mode are a ValueError."""
+    limit, mode = env_float("CLIP_GRAD", 0.0), env_str("CLIP_MODE", "norm").lower()
+    if mode not in {"norm", "value"}:
+        raise ValueError(f"training.clip_mode must be norm or value, got {mode!r}")
+    if not math.isfinite(limit) or limit < 0.0:
+        raise ValueError(f"training.clip_grad must be a finite number >= 0 (0: off), got {limit!r}")
+    return ClipSettings(limit=limit, mode=mode) if limit else None
+
+
+class TorchClipper:
+    """Gradient clipping in front of torch's AdamW (device: cpu): torch.nn.utils.clip_grad_norm_ / clip_grad_value_ over the
+    optimizer's parameters, with the record HipAdamW.clip_stats() keeps on the device.  Like HipAdamW it lets a step with a
+    non-finite gradient norm pass without an update."""
+
+    def __init__(self, opt: optim.Optimizer, settings: ClipSettings) -> None:
+        self.params = [p for g in opt.param_groups for p in g["params"]]
+        self.settings = settings
+        self.norms: list[float] = []
+        self.clipped = self.skipped = 0
+
+    def clip(self) -> bool:
+        """Clip the gradients in place; False when the step must be skipped."""
+        if self.settings.mode == "norm":
+            norm = float(torch.nn.utils.clip_grad_norm_(self.params, self.settings.limit))
+        else:
+            norm = float(torch.nn.utils.get_total_norm([p.grad for p in self.params if p.grad is not None]))
+            torch.nn.utils.clip_grad_value_(self.params, self.settings.limit)
+        if not math.isfinite(norm):
+            self.skipped += 1
+            return False
+        self.norms.append(norm)
+        self.clipped += self.settings.mode == "norm" and self.settings.limit / (norm + 1e-6) < 1.0
+        return True
+
+    def clip_stats(self, reset: bool = True) -> dict:
+        n = len(self.norms)
+        rec = {"grad_norm_last": self.norms[-1] if n else 0.0, "grad_norm_mean": sum(self.norms) / max(1, n),
+               "grad_norm_max": max(self.norms, default=0.0), "steps": n + self.skipped, "clipped_steps": int(self.clipped),
+               "skipped_steps": self.skipped}
+        if reset:
+            self.norms, self.clipped, self.skipped = [], 0, 0
+        return rec
+
+
+def clip_suffix(clip: dict | None) -> str:
+    """` | grad_norm=<mean> (clipped k/n[, skipped s])` of an epoch's console line; empty without clipping."""
+    if clip is None:
+        return ""
+    skipped = f", skipped {clip['skipped_steps']}" if clip["skipped_steps"] else ""
+    return f" | grad_norm={clip['grad_norm_mean']:.4g} (clipped {clip['clipped_steps']}/{clip['steps']}{skipped})"
 
 
 @dataclass(frozen=True)
@@ -260,13 +322,15 @@ def evaluate(model: nn.Module, dl: DataLoader, device: str, tail=None, criterion
 def train_one_epoch(model: nn.Module, dl: DataLoader, opt: optim.Optimizer, scaler, criterion: nn.Module, device: str, *,
                     use_cuda_amp: bool, progress: Progress, task: TaskID, accum_steps: int = 1, zero_grad_first: bool = False,
                     reducer: GradAllReducer | None = None, tail=None, label: str | None = None, stepper=None, ema=None,
-                    mixer=None, with_loss: bool = False) -> EpochResult:
+                    mixer=None, with_loss: bool = False, clipper: TorchClipper | None = None) -> EpochResult:
     """One epoch (efficientnet.py:265-333; efficientformer_v2.py:222-257; fastervit.py:243-300).  `stepper`
     (graph_step.GraphedTrainStep) replays the captured loop body instead of dispatching it and updates its own `ema`;
     an eager optimizer step updates `ema` (ema.ModelEma) itself.  `mixer` (mix.BatchMixer) mixes every batch in place and
     turns its labels into probability rows before the step sees them.  `with_loss` sums the loss on the device (one more
     launch per micro-batch) for the mean training loss over all ranks.  `label`: progress text `<label> | loss` with the
-    rate in the extra column instead of `train | loss | img/s`."""
+    rate in the extra column instead of `train | loss | img/s`.  Gradient clipping is part of HipAdamW's step (so of the
+    stepper's graph too); `clipper` clips for torch's AdamW right before its step.  Either way the epoch's norms and counts
+    are read once, after the loop."""
     model.train()
     start = perf_counter()
     if not zero_grad_first:
@@ -298,7 +362,8 @@ def train_one_epoch(model: nn.Module, dl: DataLoader, opt: optim.Optimizer, scal
             if pending == accum_steps:
                 if reducer is not None:
                     reducer.finish()
-                scaler.step(opt)
+                if clipper is None or clipper.clip():
+                    scaler.step(opt)
                 scaler.update()
                 if ema is not None:
                     ema.step()
@@ -323,7 +388,8 @@ def train_one_epoch(model: nn.Module, dl: DataLoader, opt: optim.Optimizer, scal
         else:
             if reducer is not None:
                 reducer.finish()
-            scaler.step(opt)
+            if clipper is None or clipper.clip():
+                scaler.step(opt)
             scaler.update()
             if ema is not None:
                 ema.step()
@@ -333,11 +399,15 @@ def train_one_epoch(model: nn.Module, dl: DataLoader, opt: optim.Optimizer, scal
     seconds = perf_counter() - start
     stats = {"images": seen_total, "seconds": seconds, "images_per_sec": seen_total / max(1e-9, seconds),
              "launch": "hipgraph" if (stepper is not None and stepper.replays > 0 and not stepper.failed) else "eager"}
+    # gradient clipping: the record of this epoch's optimizer steps, one host read (every rank holds the same one)
+    clip = clipper.clip_stats() if clipper is not None else opt.clip_stats() if hasattr(opt, "clip_stats") else None
+    if clip is not None:
+        stats.update({k: clip[k] for k in ("grad_norm_mean", "grad_norm_max", "clipped_steps", "skipped_steps")})
     if not with_loss:
-        return EpochResult(stats)
+        return EpochResult(stats, clip=clip)
     (total_loss,) = all_reduce_counts(float(loss_sum), device=device)
     (total_seen,) = all_reduce_counts(float(seen_total), device=device)
-    return EpochResult(stats, total_loss / max(1.0, total_seen))
+    return EpochResult(stats, total_loss / max(1.0, total_seen), clip=clip)
 
 
 def log_throughput(env, chief: bool, world: int, **record) -> None:
@@ -393,6 +463,7 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
         console.print(f"Expected: {data_root}/{train_split}/<class> and {data_root}/{val_split}/<class>")
         raise SystemExit(1)
     policy_settings()       # a bad training.rand_augment_* / trivial_augment is a ValueError here, not a class-count message below
+    clip_cfg = clip_settings()      # and so is a bad training.clip_grad / clip_mode
     try:
         # $GPU_INPUT_TAIL (YAML training.gpu_input_tail): loaders ship uint8 batches, the device does
         # flip / to-float / normalise / erasing
@@ -421,6 +492,9 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
     mixer = make_mixer(mix_settings(), num_classes, device)      # Mixup / CutMix ($MIXUP_ALPHA, $CUTMIX_ALPHA)
     scaler = torch.amp.GradScaler(enabled=False)        # bf16 needs no loss scaling; calls kept for parity
     opt_extra = {"grad_scale": 1.0 / world} if use_cuda else {}
+    if use_cuda and clip_cfg is not None:       # HipAdamW clips inside its step; torch's AdamW (device: cpu) gets a TorchClipper
+        opt_extra.update(max_grad_norm=clip_cfg.limit, clip_mode=clip_cfg.mode)
+    make_clipper = lambda o: TorchClipper(o, clip_cfg) if clip_cfg is not None and not use_cuda else None    # noqa: E731
 
     progress = Progress(TextColumn("[bold blue]{task.description}"), BarColumn(bar_width=None), MofNCompleteColumn(),
                         TimeElapsedColumn(), TimeRemainingColumn(), TextColumn("{task.fields[extra]}"), console=console,
@@ -444,6 +518,7 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
             done = train_one_epoch(model, train_dl, warm_opt, scaler, criterion, device, use_cuda_amp=use_cuda, progress=progress,
                                    task=task, accum_steps=1, zero_grad_first=spec.warmup_zero_grad_first, reducer=reducer,
                                    tail=train_tail, label=spec.warmup_label, mixer=mixer, with_loss=spec.report_loss,
+                                   clipper=make_clipper(warm_opt),
                                    stepper=make_stepper(model, criterion, warm_opt, accum_steps=1, use_cuda=use_cuda, world=world,
                                                         reducer=reducer))
             log_throughput(env, chief, world, phase="warmup", epoch=0, model=model_name, batch_size=batch_size, **done.stats)
@@ -451,7 +526,7 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
                 reducer.detach()
             res = evaluate(model, val_dl, device, val_tail, eval_criterion)
             best_val_acc, best_epoch, warmup_done = res.acc, 0, True
-            console.print("[bold cyan]warmup[/] | " + spec.warmup_line.format(res=res))
+            console.print("[bold cyan]warmup[/] | " + spec.warmup_line.format(res=res) + clip_suffix(done.clip))
             if getattr(warm_opt, "arena", None) is not None:
                 warm_opt.zero_grad()
                 warm_opt.arena.release()
@@ -472,6 +547,7 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
         ema_cfg = ema_settings()
         ema = None if ema_cfg is None else make_model_ema(model, build, device, ema_cfg)
         stepper = make_stepper(model, criterion, opt, accum_steps=accum, use_cuda=use_cuda, world=world, reducer=reducer, ema=ema)
+        clipper = make_clipper(opt)
         start_epoch = 0
         resume_state = maybe_load_checkpoint(env, model=model, optimizer=opt, scheduler=scheduler)
         restore_model_ema(ema, resume_state)
@@ -489,13 +565,14 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
             task = progress.add_task(f"epoch {epoch}", total=len(ft_dl), extra="")
             done = train_one_epoch(model, ft_dl, opt, scaler, criterion, device, use_cuda_amp=use_cuda, progress=progress, task=task,
                                    accum_steps=accum, zero_grad_first=spec.zero_grad_first, reducer=reducer, tail=train_tail,
-                                   stepper=stepper, ema=ema, mixer=mixer, with_loss=spec.report_loss)
+                                   stepper=stepper, ema=ema, mixer=mixer, with_loss=spec.report_loss, clipper=clipper)
             log_throughput(env, chief, world, phase="fine-tune", epoch=epoch, model=model_name,
                            batch_size=ft_dl.batch_size, accum_steps=accum, **done.stats)
             scheduler.step()
             res = evaluate(model, val_dl, device, val_tail, eval_criterion)
             console.print(f"[bold cyan]epoch {epoch}[/] | "
-                          + spec.epoch_line.format(res=res, train_loss=done.loss, lr=scheduler.get_last_lr()[0]))
+                          + spec.epoch_line.format(res=res, train_loss=done.loss, lr=scheduler.get_last_lr()[0])
+                          + clip_suffix(done.clip))
             acc = res.acc
             if ema is not None:
                 res_ema = evaluate(ema.module, val_dl, device, val_tail, eval_criterion)

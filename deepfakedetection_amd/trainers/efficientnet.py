@@ -14,7 +14,7 @@ here, are re-exported.
 from __future__ import annotations
 
 from ._engine import (  # noqa: F401  (re-exported)
-    ACC, ACC_COUNTS, DATA_ROOT, LOG_EVERY, EvalResult, TrainerSpec, ema_settings, eval_forward, evaluate, make_mixer, make_stepper,
+    ACC, ACC_COUNTS, DATA_ROOT, LOG_EVERY, EvalResult, TrainerSpec, clip_settings, ema_settings, eval_forward, evaluate, make_mixer, make_stepper,
     mix_settings, run, train_one_epoch,
 )
 from ._inputs import PolicySettings, build_transforms, device_batches, get_loaders, make_loader, policy_settings  # noqa: F401

@@ -84,7 +84,8 @@ typedef void* dfd_stream;          /* a hipStream_t */
  * 137 = dfd_ema_update (exponential moving average of the weights);
  * 138 = dfd_mix_batch (Mixup / CutMix of a batch in place, with its soft targets), dfd_ce_loss_soft (cross entropy with
  * probability targets);
- * 139 = dfd_augment_policy_u8 (RandAugment / TrivialAugmentWide behind rotation and ColorJitter, in dfd_augment_u8's launch shape). */
+ * 139 = dfd_augment_policy_u8 (RandAugment / TrivialAugmentWide behind rotation and ColorJitter, in dfd_augment_u8's launch shape);
+ * 140 = dfd_grad_sumsq, dfd_grad_clip_finish, dfd_adamw_step_clip (gradient clipping by global norm or by value in the AdamW step). */
 int dfd_version(void);
 
 /* Planner knobs (A/B switches and sizes the host-side kernel selection reads).  Process-wide plain ints: set them once at
@@ -519,6 +520,41 @@ int dfd_image_prep(const unsigned char* src, float* dst, int N, int H, int W, co
 #define DFD_ADAMW_TABLE_COLS 5
 #define DFD_ADAMW_HP_LEN 8
 int dfd_adamw_step(const int64_t* table, int nchunks, const float* hp, dfd_stream stream);
+/* Gradient clipping in front of the AdamW step (torch.nn.utils.clip_grad_norm_ / clip_grad_value_), three enqueue-only,
+ * capturable launches over the same chunk table; every buffer is the caller's.  NULL pointer or nchunks < 1: DFD_EINVAL before
+ * any launch.
+ *   dfd_grad_sumsq        one workgroup per table row (only the grad and count columns are read) writes partials[row], a double:
+ *                         the sum of the squares of the chunk's f32 gradients, squared and added in f64.  No atomics; the order
+ *                         is fixed (elements 4q..4q+3 belong to thread q % 256, a thread adds in rising order, then a wave
+ *                         butterfly and (w0 + w1) + (w2 + w3)) and is the same on the 16-byte path and the scalar path, so
+ *                         equal chunk contents give equal bits at any alignment and in every run.
+ *   dfd_grad_clip_finish  one workgroup adds partials[0 .. nchunks) in f64 (thread t takes t, t + 256, ..., then the same
+ *                         tree); one thread then computes in f32
+ *                           total = (float)sqrt(sum) * hp[7]           hp: the AdamW record, hp[7] = grad_scale
+ *                           coef  = fminf(cfg[0] / (total + 1e-6f), 1) cfg = {limit, mode} in device memory; 1 in value mode
+ *                           skip  = !isfinite(total)
+ *                         and updates state, DFD_CLIP_STATE_LEN f32 in device memory.  The counters and the norm sum / maximum
+ *                         accumulate over calls until the host zeroes the record; a skipped step counts as seen and as
+ *                         skipped only.
+ *   dfd_adamw_step_clip   dfd_adamw_step reading cfg and state: returns at once, leaving param, exp_avg and exp_avg_sq
+ *                         untouched, when state[DFD_CLIP_SKIP] is set; else the gradient is (g * grad_scale) * coef in
+ *                         DFD_CLIP_MODE_NORM and fminf(fmaxf(g * grad_scale, -limit), limit) in DFD_CLIP_MODE_VALUE, and
+ *                         the rest of the step is dfd_adamw_step's.                                                      */
+#define DFD_CLIP_MODE_NORM 0
+#define DFD_CLIP_MODE_VALUE 1
+#define DFD_CLIP_CFG_LEN 2
+#define DFD_CLIP_STATE_LEN 8
+#define DFD_CLIP_NORM 0      /* total norm of the last call                 */
+#define DFD_CLIP_COEF 1      /* coefficient of the last call                */
+#define DFD_CLIP_SKIP 2      /* 1 when the last call's norm was not finite  */
+#define DFD_CLIP_STEPS 3     /* calls seen                                  */
+#define DFD_CLIP_CLIPPED 4   /* of these: finite norm and coef < 1          */
+#define DFD_CLIP_SKIPPED 5   /* of these: norm not finite                   */
+#define DFD_CLIP_NORM_SUM 6  /* sum of the finite norms                     */
+#define DFD_CLIP_NORM_MAX 7  /* largest finite norm                         */
+int dfd_grad_sumsq(const int64_t* table, int nchunks, double* partials, dfd_stream stream);
+int dfd_grad_clip_finish(const double* partials, int nchunks, const float* hp, const float* cfg, float* state, dfd_stream stream);
+int dfd_adamw_step_clip(const int64_t* table, int nchunks, const float* hp, const float* cfg, const float* state, dfd_stream stream);
 /* Exponential moving average of the weights over a chunk table: int64 rows {src, dst, count, kind}, count <= 4096.
  * kind DFD_EMA_LERP: f32 dst = dst + w * (src - dst), rounded as d = src - dst, t = w * d, dst + t (no FMA);
  * kind DFD_EMA_COPY: count 8-byte words copied from src to dst (integer buffers).  w: one f32 in device memory
