@@ -212,7 +212,7 @@ static int dw_bwd_data_q_t(const void* dz, const void* y, const float* coef, con
     DwQGeom g; int tile_bytes;
     const int kk = s ? s->k * s->k : 0;
     const DwqOcc occ = dwq_occupancy(1, s);
-    if (!dfd_dwq_geom(s, V, 16, true, (size_t)(kk + 5) * 16 * V * 4, 0, 1, &g, &tile_bytes, 1, occ.lds_budget)) return DFD_EINVAL;
+    if (!dfd_dwq_geom(s, V, 16, true, (size_t)(kk + 5) * 16 * V * 4, 0, 1, &g, &tile_bytes, occ.lds_budget)) return DFD_EINVAL;
     const int cvb = 1 << g.cvb_log2, nchunks = (g.CV + cvb - 1) / cvb;
     // chunk-workgroups share cache lines unless both the pixel stride and the chunk width are whole lines
     g.remap = (s->stride == 1 && nchunks > 1 && ((s->C * (int)sizeof(T)) % 128 != 0 || (cvb * 16) % 128 != 0)) ? 1 : 0;
@@ -389,7 +389,7 @@ k_dw_bwd_weight_q(const T* __restrict__ dz, const T* __restrict__ yraw, const fl
 
 static bool dw_wgrad_q_geom(const dfd_dwconv_shape* s, int vec, DwQGeom* g, int* tile_bytes) {
     const int max_cvb = (s && s->k == 5) ? 8 : 16;          // needs 256/cvb >= K lanes per run
-    if (!dfd_dwq_geom(s, vec, max_cvb, false, (size_t)5 * 16 * vec * 4, 16, s ? s->k : 1, g, tile_bytes, 1, dwq_occupancy(2, s).lds_budget)) return false;
+    if (!dfd_dwq_geom(s, vec, max_cvb, false, (size_t)5 * 16 * vec * 4, 16, s ? s->k : 1, g, tile_bytes, dwq_occupancy(2, s).lds_budget)) return false;
     const int cvb = 1 << g->cvb_log2, nchunks = (g->CV + cvb - 1) / cvb, esz = vec == 8 ? 2 : 4;
     g->remap = (nchunks > 1 && ((s->C * esz) % 128 != 0 || (cvb * 16) % 128 != 0)) ? 1 : 0;
     return true;

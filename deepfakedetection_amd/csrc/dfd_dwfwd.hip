@@ -190,7 +190,7 @@ k_dw_fwd_q(const T* __restrict__ x, const float* __restrict__ bnstate, const flo
 static int ilog2p(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
 bool dfd_dwq_geom(const dfd_dwconv_shape* s, int vec, int max_cvb, bool centre_is_input, size_t extra_lds,
-                  int extra_centre, int lane_div, DwQGeom* g, int* tile_bytes, int halo_tiles, long lds_budget) {
+                  int extra_centre, int lane_div, DwQGeom* g, int* tile_bytes, long lds_budget) {
     if (!s || s->N <= 0 || s->H <= 0 || s->W <= 0 || s->Ho <= 0 || s->Wo <= 0 || s->C <= 0 || s->C % 8) return false;
     if (!(s->k == 3 || s->k == 5) || !(s->stride == 1 || s->stride == 2)) return false;
     if (s->pad_top < 0 || s->pad_left < 0 || s->pad_top >= s->k || s->pad_left >= s->k) return false;
@@ -229,7 +229,7 @@ bool dfd_dwq_geom(const dfd_dwconv_shape* s, int vec, int max_cvb, bool centre_i
             const int IH = ext(TH);
             const long px = (long)IH * IW;
             if (px >= 4096) break;
-            const long lds = px * cvb * 16 * halo_tiles + (long)extra_lds + (long)TH * TW * cvb * extra_centre;
+            const long lds = px * cvb * 16 + (long)extra_lds + (long)TH * TW * cvb * extra_centre;
             if (lds > lds_budget && !(TH == 1 && QW == 1)) break;
             const long tiles = (long)((CH + TH - 1) / TH) * ((CW + TW - 1) / TW);
             const long lanes = PL / lane_div > 0 ? PL / lane_div : 1;      // lanes that share the quads of a tile
@@ -293,7 +293,7 @@ static int dw_fwd_q_t(const void* x, const float* in_bnstate, int in_act, const 
     const bool pairs = DW_FWD_PAIRS && sizeof(T) == 2 && s && s->k == 3 && s->stride == 1;
     const size_t tables = (size_t)(s ? s->k * s->k + 2 : 0) * 16 * V * 4;
     const DwqOcc occ = dwq_occupancy(0, s);
-    if (!dfd_dwq_geom(s, V, 16, false, tables, 0, 1, &g, &tile_bytes, 1, pairs ? 31 * 1024 : occ.lds_budget)) return DFD_EINVAL;
+    if (!dfd_dwq_geom(s, V, 16, false, tables, 0, 1, &g, &tile_bytes, pairs ? 31 * 1024 : occ.lds_budget)) return DFD_EINVAL;
     const int cvb = 1 << g.cvb_log2, nchunks = (g.CV + cvb - 1) / cvb;
     // XCD-aware order (dwq_block): measured per layer — helps the forward kernel when an image spans
     // several tiles and the channel chunks share cache lines (block 2: 219 -> 201 us), hurts when one

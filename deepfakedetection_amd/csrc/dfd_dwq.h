@@ -6,7 +6,7 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 
 // workgroups a depthwise launch aims for (all channel chunks together); 1024 are co-resident at 4 per CU.  The training kernels
 // (forward, data gradient, weight gradient) read theirs from dfd_tune keys 8-10 (default 1024, dfd_dwmm.hip); this constant is what
-// the eval-form forward and the fused backward (off by default) still use.
+// the eval-form forward still uses.
 #ifndef DFD_DW_GRID
 #define DFD_DW_GRID 2048
 #endif
@@ -93,9 +93,8 @@ template <typename T> __device__ __forceinline__ f2 round2(f2 v) {
 // tile geometry chosen by a small cost model; centre_is_input selects the data-gradient form
 // extra_lds: fixed bytes; extra_centre: bytes per centre pixel per channel vector (second tile);
 // lane_div: pixel lanes are shared by this many roles (weight gradient: K kernel rows)
-// halo_tiles: staged tiles of the halo extent that live in LDS at once (the fused backward stages dy AND the activated input)
 bool dfd_dwq_geom(const dfd_dwconv_shape* s, int vec, int max_cvb, bool centre_is_input, size_t extra_lds,
-                  int extra_centre, int lane_div, DwQGeom* g, int* tile_bytes, int halo_tiles = 1, long lds_budget = 36 * 1024);
+                  int extra_centre, int lane_div, DwQGeom* g, int* tile_bytes, long lds_budget = 36 * 1024);
 
 // Occupancy class of a vector-unit depthwise launch (op: 0 forward, 1 data gradient, 2 weight gradient): FOUR workgroups per CU with
 // tile + tables within 39 KB and a grid of the launch's dfd_tune target (1024), or THREE per CU within 48 KB and 3/4 of the target (768).

@@ -21,7 +21,6 @@ without autocast: trainers/efficientnet.py:249-254, orchestrator.py:587-590).
 from __future__ import annotations
 
 import math
-import os
 import warnings
 
 import torch
@@ -32,8 +31,6 @@ from .arch import BlockPlan, NetPlan, efficientnet_plan
 from .functions import (BNRef, HeadConvFunction, HeadCtx, HeadFunction, HeadTailEvalFunction, MBConvCtx, MBConvFunction,
                         StemCtx, StemFunction)
 
-# A/B switch for experiments, read once at import: per-layer weight preparation instead of the batched launch
-_NO_DERIVED = os.environ.get("DFD_NO_DERIVED") == "1"
 _default_rng: dict = {}
 
 
@@ -256,8 +253,6 @@ class HipEfficientNet(nn.Module):
         from . import kernels as K
 
         _, _, blocks, head, _, _ = self._parts()
-        if _NO_DERIVED:                                        # A/B switch: per-layer preparation
-            return [None] * (len(blocks) + 1)
         items, layout = [], []
         for blk in blocks:
             p = blk.plan

@@ -83,8 +83,6 @@ def eval_fused_enabled(elems: int, dtype: torch.dtype) -> bool:
 
 
 EVAL_FUSED_MAX_ELEMS = 32 << 20
-# DFD_SE_PASSENGER=0: the squeeze-excite FC weight gradients as a launch of their own (A/B switch)
-SE_WGRAD_PASSENGER = os.environ.get("DFD_SE_PASSENGER", "1") != "0"
 
 
 @contextlib.contextmanager
@@ -288,15 +286,14 @@ class MBConvFunction(torch.autograd.Function):
         dw_proj = None
         if need[11]:
             pro_q = K.pro_bn_act_gate(st2, ACT_SILU, gate, Ho * Wo)
-            with K.side_stream(N * Ho * Wo):
-                dw_proj = K.pwconv_wgrad(gm3, None, y2, pro_q, _dest(ctx, 11, (Cout, Cmid))).view(Cout, Cmid, 1, 1)
+            dw_proj = K.pwconv_wgrad(gm3, None, y2, pro_q, _dest(ctx, 11, (Cout, Cmid))).view(Cout, Cmid, 1, 1)
         # ---- squeeze-excite backward
         want_se = need[7] or need[8] or need[9] or need[10]
         se_outs = (_dest(ctx, 7, (R, Cmid)), _dest(ctx, 8, (R,)), _dest(ctx, 9, (Cmid, R)), _dest(ctx, 10, (Cmid,)))
         # the FC weight gradients (read by the optimizer only) ride along with the next launch instead of being one of their own
-        se_res = K.se_bwd(D, y2, st2, ACT_SILU, gate, hpre, pooled, w1, w2t, ACT_SILU, want_se, se_outs, defer_wgrad=SE_WGRAD_PASSENGER)
+        se_res = K.se_bwd(D, y2, st2, ACT_SILU, gate, hpre, pooled, w1, w2t, ACT_SILU, want_se, se_outs, defer_wgrad=True)
         dpooled, dw1, db1, dw2, db2 = se_res[:5]
-        se_job = se_res[5] if SE_WGRAD_PASSENGER else None
+        se_job = se_res[5]
         # ---- SiLU' and depthwise BN backward
         dz2, parts, n = K.act_bn_bwd(D, y2, gate, dpooled, st2, ACT_SILU, se_job=se_job)
         if dw1 is not None:
@@ -306,14 +303,8 @@ class MBConvFunction(torch.autograd.Function):
         kk = geom.kernel
         dw_dw = dx = dw_exp = dg_exp = db_exp = None
         if cfg.expand:
-            fused = need[4] and K.dwconv_bwd_fused_ok(geom.kernel, geom.stride)
-            if fused:
-                # 3x3 stride 1: data and weight gradient from one staging of (dz2, y2, y1) — csrc/dfd_dwbwdf.hip
-                dz1, parts, n, dw_dw = K.dwconv_bwd_fused(dz2, y2, coef2, w_dw, y1, st1, ACT_SILU, geom.kernel, geom.stride,
-                                                          geom.pad_lead, geom.pad_lead, _dest(ctx, 4, (Cmid, 1, kk, kk)))
-            else:
-                dz1, parts, n = K.dwconv_bwd_data(dz2, y2, coef2, w_dw, y1, st1, ACT_SILU, y1.shape, geom.kernel,
-                                                  geom.stride, geom.pad_lead, geom.pad_lead)
+            dz1, parts, n = K.dwconv_bwd_data(dz2, y2, coef2, w_dw, y1, st1, ACT_SILU, y1.shape, geom.kernel,
+                                              geom.stride, geom.pad_lead, geom.pad_lead)
             coef1, dg_exp, db_exp = K.bn_bwd_finalize(parts, n, N * H * W, g_exp, st1, tr, need[2] or need[3],
                                                       _dest(ctx, 2, (Cmid,)), _dest(ctx, 3, (Cmid,)))
             pro_dy1 = K.pro_affine2(y1, coef1)
@@ -321,27 +312,24 @@ class MBConvFunction(torch.autograd.Function):
             # network (csrc/dfd_pwtnw.hip, DG) — bit-identical to the two kernels below
             both = K.pwconv_bwd_fused(dz1, y1, coef1, x, wexp_kn, g if cfg.skip else None, _dest(ctx, 1, (Cmid, Cin))) \
                 if (need[0] and need[1] and K.pwconv_bwd_fused_ok(dz1, x)) else None
-            with K.side_stream(N * Ho * Wo):
-                if need[4] and not fused:
-                    dw_dw = K.dwconv_bwd_weight(dz2, y2, coef2, y1, st1, ACT_SILU, geom.kernel, geom.stride,
-                                                geom.pad_lead, geom.pad_lead, _dest(ctx, 4, (Cmid, 1, kk, kk)))
-                if need[1] and both is None:
-                    dw_exp = K.pwconv_wgrad(dz1, pro_dy1, x, None, _dest(ctx, 1, (Cmid, Cin))).view(Cmid, Cin, 1, 1)
+            if need[4]:
+                dw_dw = K.dwconv_bwd_weight(dz2, y2, coef2, y1, st1, ACT_SILU, geom.kernel, geom.stride,
+                                            geom.pad_lead, geom.pad_lead, _dest(ctx, 4, (Cmid, 1, kk, kk)))
+            if need[1] and both is None:
+                dw_exp = K.pwconv_wgrad(dz1, pro_dy1, x, None, _dest(ctx, 1, (Cmid, Cin))).view(Cmid, Cin, 1, 1)
             if both is not None:
                 dx, dw_exp = both[0], both[1].view(Cmid, Cin, 1, 1)
             elif need[0]:
                 dx, _, _ = K.pwconv(dz1, pro_dy1, wexp_kn, g if cfg.skip else None, stats=False)
         else:
             if need[4]:
-                with K.side_stream(N * Ho * Wo):
-                    dw_dw = K.dwconv_bwd_weight(dz2, y2, coef2, x, None, ACT_NONE, geom.kernel, geom.stride,
-                                                geom.pad_lead, geom.pad_lead, _dest(ctx, 4, (Cmid, 1, kk, kk)))
+                dw_dw = K.dwconv_bwd_weight(dz2, y2, coef2, x, None, ACT_NONE, geom.kernel, geom.stride,
+                                            geom.pad_lead, geom.pad_lead, _dest(ctx, 4, (Cmid, 1, kk, kk)))
             if need[0]:
                 dx, _, _ = K.dwconv_bwd_data(dz2, y2, coef2, w_dw, None, None, ACT_NONE, ctx.in_shape, geom.kernel,
                                              geom.stride, geom.pad_lead, geom.pad_lead)
                 if cfg.skip:
                     dx = K.add(dx, g)
-        K.join_side()
         return (dx, dw_exp, dg_exp, db_exp, dw_dw, dg_dw, db_dw, dw1, db1, dw2, db2, dw_proj, dg_proj, db_proj,
                 None, None)
 

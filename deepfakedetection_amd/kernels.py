@@ -36,53 +36,6 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
-# ---- optional weight-gradient side stream (DFD_SIDE_STREAM=1; OFF by default).  Inside one block's
-# backward the weight-gradient kernels depend on the data-gradient chain but nothing in that chain
-# depends on them, so they can run on a second HIP stream — a parallel branch of the captured hipGraph —
-# joined before the block's backward returns (every tensor the side kernels read is then still
-# referenced: no record_stream; the shared wgrad scratch is never used by two blocks at once).
-# Measured on MI355X: 16.99 ms/step with it vs 16.48 without — every large kernel here is a persistent
-# grid sized for the whole chip, so two of them at once just take turns; kept for experiments only.
-_side_streams: dict[int, torch.cuda.Stream] = {}
-_side_enabled = os.environ.get("DFD_SIDE_STREAM", "0") == "1"
-_side_max_rows = int(os.environ.get("DFD_SIDE_MAXROWS", "0"))      # experiments: only layers with at most this many rows
-
-
-class side_stream:
-    """`with side_stream(rows): ...` enqueues the body on the side stream, ordered after everything already
-    enqueued on the current stream; pair with `join_side()` before the results are consumed."""
-
-    def __init__(self, rows: int = 0) -> None:
-        self.rows = rows
-
-    def __enter__(self):
-        self._ctx = None
-        if not _side_enabled or _profile_sink is not None:
-            return self
-        if _side_max_rows and self.rows > _side_max_rows:
-            return self
-        cur = torch.cuda.current_stream()
-        side = _side_streams.get(cur.device_index)
-        if side is None:
-            side = _side_streams[cur.device_index] = torch.cuda.Stream(device=cur.device)
-        side.wait_stream(cur)
-        self._ctx = torch.cuda.stream(side)
-        self._ctx.__enter__()
-        return self
-
-    def __exit__(self, *exc):
-        if self._ctx is not None:
-            self._ctx.__exit__(*exc)
-        return False
-
-
-def join_side() -> None:
-    cur = torch.cuda.current_stream()
-    side = _side_streams.get(cur.device_index)
-    if side is not None:
-        cur.wait_stream(side)
-
-
 def _dt(t: torch.Tensor) -> int:
     if t.dtype == torch.float32:
         return F32
@@ -229,8 +182,8 @@ def sum_batch():
     """Weight gradients computed inside the block leave their final partial-row summation to the block's exit, where
     one pair of launches adds them all (dfd_sum_batch_begin / _end): the returned gradient tensors are valid only after
     the block.  Nothing inside may read them, and nothing else that sums partial rows may run inside.  No-op when
-    nested or when the side stream is enabled (the sums would be launched on the wrong stream)."""
-    if _sum_batch.open or _side_enabled or not _DEFER_SUMS:
+    nested."""
+    if _sum_batch.open or not _DEFER_SUMS:
         yield
         return
     check(_L().dfd_sum_batch_begin(), "dfd_sum_batch_begin")
@@ -434,7 +387,7 @@ def gemm_bias_act(x: torch.Tensor, w_nk, state: torch.Tensor, act: int, residual
                   row_scale: torch.Tensor | None = None, want_raw: bool = False):
     """Linear layer without statistics in one kernel: act(scale * (x w^T) + shift) [* row_scale] [+ residual] -> (out, raw y or
     None), bit-identical to pwconv + bn_act_apply; None when the shape is not the fused kernel's (the caller runs the pair)."""
-    if x.dtype != torch.bfloat16 or isinstance(w_nk, MxWeight) or not _FUSE_LINEAR:
+    if x.dtype != torch.bfloat16 or isinstance(w_nk, MxWeight):
         return None
     _chk_nhwc(x)
     N_, H, W, Kd = x.shape
@@ -447,9 +400,6 @@ def gemm_bias_act(x: torch.Tensor, w_nk, state: torch.Tensor, act: int, residual
         return None
     check(rc, "dfd_gemm_bias_act", f"{tuple(x.shape)} -> {Nout}")
     return out, raw
-
-
-_FUSE_LINEAR = os.environ.get("DFD_FUSE_LINEAR", "1") != "0"      # A/B switch
 
 
 def bias_grad(g: torch.Tensor, row_scale: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -716,37 +666,6 @@ def dwconv_bwd_weight(dz: torch.Tensor, y: torch.Tensor | None, coef: torch.Tens
     check(_L().dfd_dwconv_bwd_weight(_dt(dz), _p(dz), _p(y), _p(coef), _p(xin), _p(in_state), in_act, _p(dw),
                                      ctypes.byref(shp), 0, _p(ws), ws.numel() * 4, _stream()), "dfd_dwconv_bwd_weight")
     return dw
-
-
-# measured on MI355X: the fused kernel takes 176 us where the two separate kernels take 73 + 91 us on
-# EfficientFormerV2-S1 (19.6 vs 19.3 ms/step) and is neutral on EfficientNet-B0: the two phases are issue-bound, not bandwidth-
-# bound, so sharing the staging buys less than the larger working set costs.  Kept (tested) behind DFD_FUSE_DW_BWD=1.
-_FUSE_DW_BWD = os.environ.get("DFD_FUSE_DW_BWD", "0") == "1"
-
-
-def dwconv_bwd_fused_ok(k: int, stride: int) -> bool:
-    """The one-kernel backward (csrc/dfd_dwbwdf.hip) covers 3x3 stride-1 layers."""
-    return _FUSE_DW_BWD and k == 3 and stride == 1
-
-
-def dwconv_bwd_fused(dz: torch.Tensor, y: torch.Tensor, coef: torch.Tensor, w: torch.Tensor, xin: torch.Tensor,
-                     in_state: torch.Tensor, in_act: int, k: int, stride: int, pad_top: int, pad_left: int,
-                     out_w: torch.Tensor | None = None):
-    """dwconv_bwd_data (with its epilogue) and dwconv_bwd_weight (with its prologue) from ONE staging of (dz, y, xin).
-    Returns (dzin, partials, nparts, dw)."""
-    N, H, W, C = xin.shape
-    Ho, Wo = dz.shape[1], dz.shape[2]
-    shp = _dw_shape(xin.shape, Ho, Wo, k, stride, pad_top, pad_left)
-    dzin = torch.empty((N, H, W, C), dtype=dz.dtype, device=dz.device)
-    parts = partials_buf(dz.device, C)
-    nbytes = _L().dfd_dwconv_bwd_weight_ws(ctypes.byref(shp))
-    ws = scratch(dz.device, "wgrad_ws", nbytes)
-    dw = _dst(out_w, (C, 1, k, k), dz.device)
-    n = ctypes.c_int(0)
-    check(_L().dfd_dwconv_bwd_fused(_dt(dz), _p(dz), _p(y), _p(coef), _p(w), _p(xin), _p(in_state), in_act, _p(dzin), _p(dw),
-                                    ctypes.byref(shp), _p(parts), MAX_PARTIALS, ctypes.byref(n), 0, _p(ws), ws.numel() * 4, _stream()),
-          "dfd_dwconv_bwd_fused", f"{tuple(xin.shape)} k{k}s{stride}")
-    return dzin, parts, n.value, dw
 
 
 # ------------------------------------------------------------------ pointwise
@@ -1095,22 +1014,14 @@ def pwconv_wgrad(p: torch.Tensor, pro_p: Prologue | None, q: torch.Tensor, pro_q
     return dw
 
 
-_FUSE_EXPAND_BWD = os.environ.get("DFD_FUSE_EXPAND_BWD", "1") != "0"      # A/B switch
-# the 192- / 240-wide instances need one workgroup per CU (a wave's accumulators are 144-180 registers) and measured a hair SLOWER
-# than the two kernels they replace: EfficientNet-B0 13.38 vs 13.33 ms/step, EfficientFormerV2-S1 18.01 vs 17.94 — off, kept for A/B
-_FUSE_EXPAND_WIDE = os.environ.get("DFD_FUSE_EXPAND_WIDE", "0") == "1"
-
-
 def pwconv_bwd_fused_ok(dz: torch.Tensor, x: torch.Tensor) -> bool:
     """Shapes dfd_pwconv_bwd_fused serves (include/dfd_hip.h).  Asked BEFORE the caller takes the weight gradient's arena slot:
     a slot handed to a call that then declines would be lost to the fallback (its gradient would land outside the arena)."""
     Cm, Cin = dz.shape[-1], x.shape[-1]
     M = dz.numel() // Cm
-    if not (_FUSE_EXPAND_BWD and dz.dtype == torch.bfloat16 and M >= 2048 * 32 * 3 and Cin <= Cm and Cin % 8 == 0 and Cm % 8 == 0):
+    if not (dz.dtype == torch.bfloat16 and M >= 2048 * 32 * 3 and Cin <= Cm and Cin % 8 == 0 and Cm % 8 == 0):
         return False
-    if Cin <= 32 and (Cm <= 128 or (Cm <= 144 and Cm % 16 == 0)):
-        return True
-    return _FUSE_EXPAND_WIDE and Cin <= 48 and 144 < Cm <= 240 and Cm % 16 == 0
+    return Cin <= 32 and (Cm <= 128 or (Cm <= 144 and Cm % 16 == 0))
 
 
 def pwconv_bwd_fused(dz: torch.Tensor, y: torch.Tensor, coef: torch.Tensor, x: torch.Tensor, w_kn: torch.Tensor,
@@ -1455,10 +1366,7 @@ def bgemm(A: torch.Tensor, sa: tuple, B: torch.Tensor, sb: tuple, C: torch.Tenso
 
 def attn_mfma_supported(dtype: torch.dtype, Nq: int, Nk: int, dk: int, dv: int) -> bool:
     """The one-wave-per-(image, head, 64-token block) attention products (csrc/dfd_attn.hip, dfd_attn_scores / dfd_attn_apply): bf16
-    activations, at most 256 tokens on either side, head dimensions that are multiples of 8 up to 128.  DFD_ATTN_MFMA=0 keeps
-    dfd_bgemm (A/B)."""
-    if os.environ.get("DFD_ATTN_MFMA", "1") == "0":
-        return False
+    activations, at most 256 tokens on either side, head dimensions that are multiples of 8 up to 128."""
     return dtype == torch.bfloat16 and 1 <= Nq <= 256 and 1 <= Nk <= 256 and all(d % 8 == 0 and 8 <= d <= 128 for d in (dk, dv))
 
 
@@ -1797,7 +1705,7 @@ class DeviceRng:
 # the DESIGN.md per-kernel figure, not counter traffic.
 _profile_sink: list | None = None
 _TIMED = ("bn_act_apply", "bn_bwd_reduce", "act_bn_bwd", "pool_act", "pool_bwd_reduce", "scale_rows", "dwconv_fwd",
-          "dwconv_bwd_data", "dwconv_bwd_weight", "dwconv_bwd_fused", "pwconv", "pwconv_wgrad", "pwconv_bwd_fused", "stem_conv_fwd", "stem_conv_wgrad",
+          "dwconv_bwd_data", "dwconv_bwd_weight", "pwconv", "pwconv_wgrad", "pwconv_bwd_fused", "stem_conv_fwd", "stem_conv_wgrad",
           "se_fc_fwd", "se_fc_bwd", "linear_fwd", "linear_bwd", "ce_loss", "adamw_step", "prep_weights", "bn_finalize",
           "bn_bwd_finalize", "bn_bwd_finalize_ex", "dropout", "bgemm", "attn_scores", "attn_apply", "attn_softmax_fwd", "attn_softmax_bwd", "im2col", "col2im",
           "wattn_fwd", "wattn_bwd", "mx_quant_rows", "mx_gemm",

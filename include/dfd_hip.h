@@ -72,7 +72,7 @@ typedef void* dfd_stream;          /* a hipStream_t */
  * 112 = the eval / inference form of the MBConv block: dfd_pwconv_fwd_eval, dfd_dwconv_fwd_eval(_tiles),
  * dfd_se_fwd_parts;
  * 120 = MX fp8 weights (dfd_mx_*), fused window attention on bf16 MFMA (dfd_wattn_*),
- * batched coordinate MLPs (dfd_coord_mlp_*_multi, dfd_relpos_bias_*_multi), dfd_dwconv_bwd_fused, dfd_resize_crop_u8;
+ * batched coordinate MLPs (dfd_coord_mlp_*_multi, dfd_relpos_bias_*_multi), dfd_resize_crop_u8;
  * 121 = dfd_bias_grad / dfd_bias_grad_ws; 122 = dfd_gemm_bias_act;
  * 130 = dfd_tune; the bf16 depthwise entry points run on the matrix cores where the shape allows (same signatures);
  * 131 = dfd_augment_u8, dfd_gemm_plan, dfd_dw_mm_plan, dfd_pwconv_bwd_fused;
@@ -85,7 +85,8 @@ typedef void* dfd_stream;          /* a hipStream_t */
  * 138 = dfd_mix_batch (Mixup / CutMix of a batch in place, with its soft targets), dfd_ce_loss_soft (cross entropy with
  * probability targets);
  * 139 = dfd_augment_policy_u8 (RandAugment / TrivialAugmentWide behind rotation and ColorJitter, in dfd_augment_u8's launch shape);
- * 140 = dfd_grad_sumsq, dfd_grad_clip_finish, dfd_adamw_step_clip (gradient clipping by global norm or by value in the AdamW step). */
+ * 140 = dfd_grad_sumsq, dfd_grad_clip_finish, dfd_adamw_step_clip (gradient clipping by global norm or by value in the AdamW step);
+ * 141 = the one-kernel depthwise backward export of 120 (3x3 stride 1, data and weight gradient together) removed. */
 int dfd_version(void);
 
 /* Planner knobs (A/B switches and sizes the host-side kernel selection reads).  Process-wide plain ints: set them once at
@@ -332,14 +333,6 @@ int dfd_se_fwd_parts(const float* parts, int splits, int N, int HW, int C, const
                      const float* w2, const float* b2, int R, int act, float* pooled, float* hpre, float* gate,
                      float* w2t, dfd_stream stream);
 size_t dfd_dwconv_bwd_weight_ws(const dfd_dwconv_shape* s);
-/* Data gradient AND weight gradient of a 3x3 stride-1 depthwise convolution in one kernel (dfd_dwconv_bwd_data with its
- * epilogue + dfd_dwconv_bwd_weight with its prologue, same arguments): dz / y / xin cross HBM once instead of twice.
- * ws as for dfd_dwconv_bwd_weight (dfd_dwconv_bwd_weight_ws bytes).  DFD_EUNSUPPORTED for other kernel sizes / strides:
- * callers then use the two separate entry points.                                                                      */
-int dfd_dwconv_bwd_fused(int dtype, const void* dz, const void* y, const float* coef, const float* w, const void* xin,
-                         const float* in_bnstate, int in_act, void* dzin, float* dw, const dfd_dwconv_shape* s,
-                         float* partials, int pcap, int* nparts, int accumulate, float* ws, size_t ws_bytes,
-                         dfd_stream stream);
 
 /* ----------------------------------------------------------- pointwise conv ---
  * 1x1 convolutions (_expand_conv, _project_conv, _conv_head; timm conv_pw/conv_pwl/
@@ -374,7 +367,7 @@ int dfd_pwconv_wgrad(int dtype, const void* p, const dfd_prologue* pro_p, int Ni
  * dz, y [M][Cm]; x [M][Cin]; w_kn = the layer's weight in the activation dtype as [Cin][Cm] (the [K][N] copy dfd_pw_prep_weights /
  * dfd_prep_weights_multi write); residual [M][Cin] or NULL; dx [M][Cin]; dw f32 [Cm][Cin]; ws as for dfd_pwconv_wgrad(M, Cm, Cin).
  * Bit-identical to dfd_pwconv_fwd(dz, AFFINE2, w_kn, residual) + dfd_pwconv_wgrad(dz, AFFINE2, x) — (dz, y) cross HBM once
- * instead of twice.  bf16, Cin <= 32, Cm <= 144, M >= 196,608 (EfficientNet blocks 1-3 at the benchmark batch); anything else:
+ * instead of twice.  bf16, Cin <= 32, Cm <= 128 or Cm = 144, M >= 196,608 (EfficientNet blocks 1-3 at the benchmark batch); anything else:
  * DFD_EUNSUPPORTED, the caller runs the two entry points. */
 int dfd_pwconv_bwd_fused(int dtype, const void* dz, const void* y, const float* coef, const void* x, const void* w_kn,
                          const void* residual, int M, int Cm, int Cin, void* dx, float* dw, int accumulate, float* ws,

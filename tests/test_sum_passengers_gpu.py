@@ -102,7 +102,7 @@ def _make_block(carriers, jobs, gen: torch.Generator):
 def _run(blocks):
     """blocks: (carriers, jobs) in BACKWARD order (the first entry's backward runs first).  Returns every job."""
     K = _K()
-    assert K.PASSENGER_SUMS and K.passenger_sums_enabled and K._DEFER_SUMS and not K._side_enabled
+    assert K.PASSENGER_SUMS and K.passenger_sums_enabled and K._DEFER_SUMS
     dev = torch.device("cuda")
     gen = torch.Generator().manual_seed(1234)
     jobs = []
