@@ -119,6 +119,9 @@ SIGNATURES: dict[str, tuple] = {
     "dfd_grad_sumsq": (c_int, [P, c_int, P, P]),
     "dfd_grad_clip_finish": (c_int, [P, c_int, P, P, P, P]),
     "dfd_adamw_step_clip": (c_int, [P, c_int, P, P, P, P]),
+    # ---- ABI 142
+    "dfd_jpeg_u8": (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
+    "dfd_jpeg_ws": (c_size_t, [c_int, c_int, c_int]),
     # ---- ABI 111
     "dfd_bn_eval_coeffs_multi": (c_int, [P, c_int, P]),
     "dfd_sum_batch_begin": (c_int, []),

@@ -8,7 +8,8 @@ the source of randomness (so `apply_seed` governs augmentation):
   Lambda, Resize(shorter side, bilinear), CenterCrop, RandomCrop,
   RandomResizedCrop(size, scale, ratio), RandomRotation(degrees), RandomHorizontalFlip(p),
   ColorJitter(brightness, contrast, saturation, hue), ToTensor, Normalize(mean, std),
-  RandomErasing(p, scale, ratio, value), Compose, RandAugment(num_ops, magnitude), TrivialAugmentWide().
+  RandomErasing(p, scale, ratio, value), Compose, RandAugment(num_ops, magnitude), TrivialAugmentWide(),
+  RandomJpeg(p, quality).
 
 Batches leave the loaders as float32 [N,3,H,W] + int64 [N] exactly like the reference's.
 """
@@ -16,6 +17,7 @@ Batches leave the loaders as float32 [N,3,H,W] + int64 [N] exactly like the refe
 from __future__ import annotations
 
 import functools
+import io
 import math
 import os
 from collections.abc import Callable, Sequence
@@ -294,6 +296,39 @@ class TrivialAugmentWide:
         return img
 
 
+def check_jpeg(p: float, lo: int, hi: int) -> tuple[float, int, int]:
+    if not 0.0 <= float(p) <= 1.0:
+        raise ValueError(f"RandomJpeg: p must be within 0..1, got {p}")
+    if int(lo) != lo or int(hi) != hi or not 1 <= int(lo) <= int(hi) <= 100:
+        raise ValueError(f"RandomJpeg: the quality range must satisfy 1 <= min <= max <= 100, got {lo}..{hi}")
+    return float(p), int(lo), int(hi)
+
+
+def _jpeg_draw(p: float, lo: int, hi: int) -> int:
+    """The quality RandomJpeg compresses this picture at, 0: it is left alone.  The quality is drawn only for a selected picture."""
+    if _rand() < p:
+        return int(torch.randint(lo, hi + 1, (1,)))
+    return 0
+
+
+class RandomJpeg:
+    """JPEG-compression augmentation on PIL images: with probability `p` the picture is replaced by its round trip through a
+    baseline JPEG (Pillow's defaults: 4:2:0 chroma, standard tables) at a quality drawn uniformly from the integers lo..hi."""
+
+    def __init__(self, p: float = 0.5, quality: tuple[int, int] = (60, 100)) -> None:
+        self.p, self.lo, self.hi = check_jpeg(p, *quality)
+
+    def __call__(self, img: Image.Image) -> Image.Image:
+        quality = _jpeg_draw(self.p, self.lo, self.hi)
+        if not quality:
+            return img
+        buf = io.BytesIO()
+        img.convert("RGB").save(buf, "JPEG", quality=quality)
+        buf.seek(0)
+        with Image.open(buf) as back:
+            return back.convert("RGB")
+
+
 class ToTensor:
     """PIL image (uint8) -> float32 CHW in [0, 1]."""
 
@@ -547,12 +582,19 @@ class GpuInputTail:
     (dfd_augment_policy_u8).  The geometric operations of a policy do not commute with the flip, so with a policy on the tail draws
     picture by picture in the PIL pipeline's order — angle, flip, jitter, policy — and the flip is applied inside that kernel,
     between rotation and ColorJitter where RandomHorizontalFlip stands; dfd_image_prep then gets no flip.  Without a policy
-    nothing changes: same draws, same two kernels."""
+    nothing changes: same draws, same two kernels.
+
+    jpeg=(p, quality_min, quality_max) adds RandomJpeg directly in front of ToTensor (dfd_jpeg_u8, byte-exact with Pillow).  With a
+    policy its draw follows the policy's, picture by picture.  Without one it is drawn for the whole batch after the flips and
+    before the erasing boxes; the flip does not commute with the round trip, so the flip flags then go to dfd_jpeg_u8, which mirrors
+    every picture — also those it only copies — before it compresses, and dfd_image_prep gets no flip.  With jpeg=None nothing
+    changes: same draws, same launches."""
 
     def __init__(self, mean: Sequence[float], std: Sequence[float], flip_p: float = 0.0, erase_p: float = 0.0,
                  erase_scale: tuple[float, float] = (0.02, 0.33), erase_ratio: tuple[float, float] = (0.3, 3.3),
                  rotate_degrees: float = 0.0, jitter: Sequence[float] | None = None,
-                 rand_augment: tuple[int, int] | None = None, trivial_augment: bool = False) -> None:
+                 rand_augment: tuple[int, int] | None = None, trivial_augment: bool = False,
+                 jpeg: tuple[float, int, int] | None = None) -> None:
         self.mean, self.std = [float(v) for v in mean], [float(v) for v in std]
         self.flip_p, self.erase_p, self.erase_scale, self.erase_ratio = flip_p, erase_p, erase_scale, erase_ratio
         self.rotate_degrees = float(rotate_degrees)
@@ -561,6 +603,7 @@ class GpuInputTail:
             raise ValueError("GpuInputTail: rand_augment and trivial_augment exclude each other")
         self.rand_augment = check_rand_augment(*rand_augment) if rand_augment is not None else None
         self.trivial_augment = bool(trivial_augment)
+        self.jpeg = check_jpeg(*jpeg) if jpeg is not None else None
 
     @property
     def augments(self) -> bool:
@@ -609,16 +652,31 @@ class GpuInputTail:
         ColorJitter -> RandAugment | TrivialAugmentWide draw for that picture, in that order: the EfficientNet trainer's PIL
         pipeline, seed for seed.  The other trainers' PIL pipelines flip BEFORE they rotate; against those the device path is
         equal in distribution (a uniform angle is symmetric about 0), not per seed — as it already is without a policy."""
+        return self._sample_policy(n, h, w)[0]
+
+    def _sample_policy(self, n: int, h: int, w: int) -> tuple[torch.Tensor, torch.Tensor | None]:
+        """sample_policy's jobs and, with jpeg on, the {quality, flip = 0} jobs of dfd_jpeg_u8, RandomJpeg's draw following the
+        policy's for each picture."""
         base = np.zeros((n, 16), dtype=np.int32)
         fl = base.view(np.float32)
-        flips, ops = [], []
+        flips, ops, qualities = [], [], []
         num_ops, magnitude = self.rand_augment if self.rand_augment is not None else (1, 0)
         for i in range(n):
             self._draw_rotation(base, i, h, w)
             flips.append(1 if self.flip_p > 0 and _rand() < self.flip_p else 0)
             self._draw_jitter(base, fl, i)
             ops.append(_aa_draw(self.policy, num_ops, magnitude, w, h))
-        return pack_policy_jobs(base, flips, ops, w, h)
+            if self.jpeg is not None:
+                qualities.append(_jpeg_draw(*self.jpeg))
+        return pack_policy_jobs(base, flips, ops, w, h), (self._jpeg_jobs(qualities, None) if self.jpeg is not None else None)
+
+    @staticmethod
+    def _jpeg_jobs(qualities: Sequence[int], flip: torch.Tensor | None) -> torch.Tensor:
+        jobs = torch.zeros((len(qualities), 2), dtype=torch.int32)
+        jobs[:, 0] = torch.tensor(qualities, dtype=torch.int32)
+        if flip is not None:
+            jobs[:, 1] = flip.to(torch.int32)
+        return jobs
 
     def sample(self, n: int, h: int, w: int) -> tuple[torch.Tensor | None, torch.Tensor | None]:
         flip = None
@@ -647,11 +705,18 @@ class GpuInputTail:
         return erase
 
     def _draw(self, n: int, h: int, w: int):
-        """(rotation / jitter jobs | None, policy jobs | None, flip | None, erase | None) for a batch."""
+        """(rotation / jitter jobs | None, policy jobs | None, flip | None, erase | None, jpeg jobs | None) for a batch."""
         if self.policy is not None:
-            return None, self.sample_policy(n, h, w), None, self._sample_erase(n, h, w)
+            policy, jpeg = self._sample_policy(n, h, w)
+            return None, policy, None, self._sample_erase(n, h, w), jpeg
         aug = self.sample_augment(n, h, w) if self.augments else None
-        return (aug, None, *self.sample(n, h, w))
+        if self.jpeg is None:
+            return (aug, None, *self.sample(n, h, w), None)
+        flip = None
+        if self.flip_p > 0:
+            flip = torch.tensor([1 if _rand() < self.flip_p else 0 for _ in range(n)], dtype=torch.uint8)
+        jpeg = self._jpeg_jobs([_jpeg_draw(*self.jpeg) for _ in range(n)], flip)          # the flip goes in front of the round trip
+        return aug, None, None, self._sample_erase(n, h, w), jpeg
 
     def __call__(self, batch_u8: torch.Tensor, device) -> torch.Tensor:
         from . import kernels as K
@@ -660,18 +725,20 @@ class GpuInputTail:
             flat, jobs, meta = batch_u8
             oh, ow, shrink = (int(v) for v in meta)
             n = jobs.numel() // _JOB_DTYPE.itemsize
-            aug, policy, flip, erase = self._draw(n, oh, ow)
+            aug, policy, flip, erase, jpeg = self._draw(n, oh, ow)
             dev = K.resize_crop_u8(flat.to(device, non_blocking=True), jobs.to(device, non_blocking=True), n, oh, ow, shrink)
         else:
             if batch_u8.dim() != 4 or batch_u8.shape[3] != 3 or batch_u8.dtype != torch.uint8:
                 raise ValueError("GpuInputTail expects a uint8 [N, H, W, 3] batch (ToUint8HWC at the end of the CPU pipeline)")
             n, h, w, _ = batch_u8.shape
-            aug, policy, flip, erase = self._draw(n, h, w)
+            aug, policy, flip, erase, jpeg = self._draw(n, h, w)
             dev = batch_u8.to(device, non_blocking=True).contiguous()
         if aug is not None:
             dev = K.augment_u8(dev, aug.to(device, non_blocking=True))
         if policy is not None:
             dev = K.augment_policy_u8(dev, policy)
+        if jpeg is not None:
+            dev = K.jpeg_u8(dev, jpeg)
         return K.image_prep(dev, self.mean, self.std,
                             flip.to(device, non_blocking=True) if flip is not None else None,
                             erase.to(device, non_blocking=True) if erase is not None else None)

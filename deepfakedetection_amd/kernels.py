@@ -518,6 +518,32 @@ def augment_policy_u8(src_u8: torch.Tensor, jobs_i32: torch.Tensor) -> torch.Ten
     return out
 
 
+def jpeg_u8(src_u8: torch.Tensor, jobs_i32: torch.Tensor, ws: torch.Tensor | None = None) -> torch.Tensor:
+    """uint8 [N, H, W, 3] on the device + one {quality, flip} pair per picture as a HOST int32 [N, 2] tensor -> each picture after
+    a baseline JPEG encode at its quality and a decode, byte-exact with Pillow (csrc/dfd_jpeg.hip, ABI 142).  Quality 0 copies the
+    picture through; flip 1 mirrors it in x first, copied or compressed.  `ws`: at least dfd_jpeg_ws bytes of uint8 scratch on the
+    device (allocated when None).  The jobs are checked here; the upload does not block when the tensor is pinned."""
+    if src_u8.dtype != torch.uint8 or src_u8.dim() != 4 or src_u8.shape[3] != 3 or not src_u8.is_contiguous():
+        raise ValueError("expected a contiguous uint8 [N, H, W, 3] tensor")
+    N, H, W, _ = src_u8.shape
+    if W < 5:
+        raise ValueError(f"jpeg_u8: pictures must be at least 5 pixels wide, got {W}")
+    if jobs_i32.is_cuda or jobs_i32.dtype != torch.int32 or tuple(jobs_i32.shape) != (N, 2) or not jobs_i32.is_contiguous():
+        raise ValueError(f"jpeg_u8: expected a host int32 [{N}, 2] job tensor of (quality, flip)")
+    if N and (int(jobs_i32[:, 0].min()) < 0 or int(jobs_i32[:, 0].max()) > 100 or int(jobs_i32[:, 1].min()) < 0
+              or int(jobs_i32[:, 1].max()) > 1):
+        raise ValueError("jpeg_u8: quality must be 0..100 and flip 0 or 1")
+    need = _L().dfd_jpeg_ws(N, H, W)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=src_u8.device)
+    elif ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need or ws.device != src_u8.device:
+        raise ValueError(f"jpeg_u8: ws must be a contiguous uint8 tensor of at least {need} bytes on {src_u8.device}")
+    out = torch.empty_like(src_u8)
+    jobs_dev = jobs_i32.to(src_u8.device, non_blocking=True)
+    check(_L().dfd_jpeg_u8(_p(src_u8), _p(jobs_dev), _p(ws), _p(out), N, H, W, _stream()), "dfd_jpeg_u8", f"{tuple(src_u8.shape)}")
+    return out
+
+
 def image_prep(src_u8: torch.Tensor, mean, std, flip: torch.Tensor | None, erase: torch.Tensor | None) -> torch.Tensor:
     """uint8 [N, H, W, 3] on the device -> f32, returned as an [N, 3, H, W] channels_last view of the
     NHWC result (zero-copy: exactly what HipEfficientNet.forward turns back into NHWC)."""

@@ -168,7 +168,8 @@ _EXTRA_TRAIN_ENV = (("ft_batch_size", "FT_BATCH_SIZE"), ("pretrained", "PRETRAIN
                     ("mixup_alpha", "MIXUP_ALPHA"), ("cutmix_alpha", "CUTMIX_ALPHA"), ("mix_prob", "MIX_PROB"),
                     ("mix_switch_prob", "MIX_SWITCH_PROB"), ("mix_mode", "MIX_MODE"),
                     ("rand_augment_ops", "RAND_AUGMENT_OPS"), ("rand_augment_magnitude", "RAND_AUGMENT_MAGNITUDE"),
-                    ("trivial_augment", "TRIVIAL_AUGMENT"), ("clip_grad", "CLIP_GRAD"), ("clip_mode", "CLIP_MODE"))
+                    ("trivial_augment", "TRIVIAL_AUGMENT"), ("clip_grad", "CLIP_GRAD"), ("clip_mode", "CLIP_MODE"),
+                    ("jpeg_p", "JPEG_P"), ("jpeg_quality_min", "JPEG_QUALITY_MIN"), ("jpeg_quality_max", "JPEG_QUALITY_MAX"))
 
 
 def _first_set(*values: Any) -> Any:

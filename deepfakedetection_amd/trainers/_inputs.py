@@ -14,7 +14,7 @@ from torch.utils.data import DataLoader
 
 from .. import data as D
 from ..dp import ShardedSampler
-from ..orchestration.train_env import env_int, env_str, load_transform_toggles, require_num_classes
+from ..orchestration.train_env import env_float, env_int, env_str, load_transform_toggles, require_num_classes
 
 
 def _rgb(image):
@@ -43,12 +43,23 @@ def policy_settings() -> PolicySettings | None:
     return PolicySettings(None, True) if trivial else None
 
 
+def jpeg_settings() -> tuple[float, int, int] | None:
+    """(p, quality_min, quality_max) of the JPEG-compression augmentation from $JPEG_P (YAML training.jpeg_p; absent or 0: off),
+    $JPEG_QUALITY_MIN (default 60) and $JPEG_QUALITY_MAX (default 100).  ValueError for p outside 0..1 or a quality range outside
+    1 <= min <= max <= 100."""
+    p = env_float("JPEG_P", 0.0)
+    if p == 0:
+        return None
+    return D.check_jpeg(p, env_int("JPEG_QUALITY_MIN", 60), env_int("JPEG_QUALITY_MAX", 100))
+
+
 _POLICY_FROM_ENV = object()
 
 
 def build_transforms(img_size: int, gpu_tail: bool = False, *, rotation_default: bool | None = None,
                      erasing_default: bool | None = None, jitter=(0.2, 0.2, 0.2, 0.05), rotation_after_flip: bool = False,
-                     gpu_resize: bool = False, policy: PolicySettings | None = _POLICY_FROM_ENV):
+                     gpu_resize: bool = False, policy: PolicySettings | None = _POLICY_FROM_ENV,
+                     jpeg: tuple[float, int, int] | None = _POLICY_FROM_ENV):
     """(train, val) pipelines from the toggle defaults of the reference + $TRANSFORMS.
     gpu_tail=True: the pipelines end in uint8 HWC tensors and (train, val, train_tail, val_tail) is
     returned, the tails being `D.GpuInputTail`s that do flip / to-float / normalise / erasing on the GPU.
@@ -64,9 +75,15 @@ def build_transforms(img_size: int, gpu_tail: bool = False, *, rotation_default:
     D.TrivialAugmentWide directly after ColorJitter's slot in the training pipeline, never in the validation one.  It follows
     rotation / jitter: on the device with them (D.GpuInputTail(rand_augment= | trivial_augment=), which then also applies the
     flip, before ColorJitter as the PIL pipeline does), else in the PIL workers — and then the flip stays in the workers too,
-    in front of it, because it does not commute with the policy's geometric operations."""
+    in front of it, because it does not commute with the policy's geometric operations.
+    jpeg (default: jpeg_settings(), i.e. $JPEG_P / $JPEG_QUALITY_MIN / $JPEG_QUALITY_MAX; None: off): (p, quality_min, quality_max) of
+    the JPEG-compression augmentation, the last operation on bytes of the training pipeline, never in the validation one:
+    D.RandomJpeg directly in front of ToTensor without gpu_tail; with gpu_tail always on the device (D.GpuInputTail(jpeg=),
+    csrc/dfd_jpeg.hip, byte-exact with Pillow) and never in the workers."""
     if policy is _POLICY_FROM_ENV:
         policy = policy_settings()
+    if jpeg is _POLICY_FROM_ENV:
+        jpeg = jpeg_settings()
     small = img_size <= 64
     toggles = load_transform_toggles(
         {
@@ -128,7 +145,7 @@ def build_transforms(img_size: int, gpu_tail: bool = False, *, rotation_default:
                                     erase_p=0.5 if on("train_random_erasing", False) else 0.0,
                                     rotate_degrees=10.0 if want_rot else 0.0, jitter=jitter if want_jit else None,
                                     rand_augment=policy.rand_augment if policy is not None else None,
-                                    trivial_augment=policy is not None and policy.trivial_augment)
+                                    trivial_augment=policy is not None and policy.trivial_augment, jpeg=jpeg)
     elif gpu_tail:
         # flip commutes with the per-pixel colour jitter, so it can move behind it onto the device — unless a policy follows
         worker_flip = policy is not None and on("train_random_horizontal_flip", True)
@@ -144,7 +161,7 @@ def build_transforms(img_size: int, gpu_tail: bool = False, *, rotation_default:
         train_tail = D.GpuInputTail(mean if on("train_normalize", True) else [0.0] * 3,
                                     std if on("train_normalize", True) else [1.0] * 3,
                                     flip_p=0.5 if on("train_random_horizontal_flip", True) and not worker_flip else 0.0,
-                                    erase_p=0.5 if on("train_random_erasing", False) else 0.0)
+                                    erase_p=0.5 if on("train_random_erasing", False) else 0.0, jpeg=jpeg)
     else:
         if not rotation_after_flip and on("train_random_horizontal_flip", True):
             train.append(D.RandomHorizontalFlip())
@@ -152,6 +169,8 @@ def build_transforms(img_size: int, gpu_tail: bool = False, *, rotation_default:
             train.append(D.ColorJitter(*jitter))
         if policy is not None:
             train.append(policy.transform())
+        if jpeg is not None:
+            train.append(D.RandomJpeg(jpeg[0], (jpeg[1], jpeg[2])))
         if on("train_to_tensor", True):
             train.append(D.ToTensor())
         if on("train_normalize", True):

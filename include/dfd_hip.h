@@ -86,7 +86,8 @@ typedef void* dfd_stream;          /* a hipStream_t */
  * probability targets);
  * 139 = dfd_augment_policy_u8 (RandAugment / TrivialAugmentWide behind rotation and ColorJitter, in dfd_augment_u8's launch shape);
  * 140 = dfd_grad_sumsq, dfd_grad_clip_finish, dfd_adamw_step_clip (gradient clipping by global norm or by value in the AdamW step);
- * 141 = the one-kernel depthwise backward export of 120 (3x3 stride 1, data and weight gradient together) removed. */
+ * 141 = the one-kernel depthwise backward export of 120 (3x3 stride 1, data and weight gradient together) removed;
+ * 142 = dfd_jpeg_u8, dfd_jpeg_ws (JPEG-compression augmentation: the pixels of a baseline JPEG round trip, byte-exact with Pillow). */
 int dfd_version(void);
 
 /* Planner knobs (A/B switches and sizes the host-side kernel selection reads).  Process-wide plain ints: set them once at
@@ -499,6 +500,16 @@ typedef struct {
 } dfd_augment_policy_job;   /* 216 bytes */
 int dfd_augment_policy_u8(const unsigned char* src, const dfd_augment_policy_job* jobs_host, const dfd_augment_policy_job* jobs_dev,
                           unsigned char* dst, int N, int H, int W, dfd_stream stream);
+/* JPEG-compression augmentation (data.RandomJpeg is its PIL form): picture n of the uint8 [N][H][W][3] batch `src` becomes in `out` what
+ * Image.save(buf, "JPEG", quality=q) followed by Image.open(buf) makes of it, byte for byte — 4:2:0 chroma, the Annex K tables
+ * with baseline clamping, libjpeg's integer DCT both ways and its triangle chroma upsampling, without the lossless entropy coding
+ * (csrc/dfd_jpeg.hip; tests/_jpeg_ref.py restates it in numpy).  jobs_dev: DEVICE int32 [N][2] = {quality, flip}: quality 0 copies the
+ * picture through, 1..100 compress; flip != 0 reads the picture mirrored in x BEFORE it is compressed or copied (RandomHorizontalFlip
+ * in front of the round trip, with which it does not commute).  ws: dfd_jpeg_ws(N, H, W) bytes of scratch (the reconstructed Y
+ * plane and the two half-size chroma planes, about 1.5 bytes per pixel), no initial contents required.  src != out; any H, any
+ * W >= 5 (libjpeg upsamples a chroma plane of width 1 or 2 differently): DFD_EINVAL otherwise, and for a NULL pointer.  Two launches. */
+int dfd_jpeg_u8(const unsigned char* src, const int* jobs_dev, void* ws, unsigned char* out, int N, int H, int W, dfd_stream stream);
+size_t dfd_jpeg_ws(int N, int H, int W);
 
 /* Input tail on the device (trainers/efficientnet.py:111-234): a uint8 NHWC
  * batch [N][H][W][3] -> RandomHorizontalFlip -> ToTensor (/255) -> Normalize((x-mean)/std) ->
