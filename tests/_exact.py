@@ -20,6 +20,10 @@ float64 reference then applies the prologue forward to the raw input like the ke
 
 The builders below return the raw inputs (f32 tensors holding values every storage dtype represents), the float64 reference
 and have run check_exact; tests/test_exact_cpu.py evaluates the f32 oracle on the same data, tests/test_exact_gpu.py the kernels.
+
+Most builders take an activation code.  With SiLU / GELU the pre-activations are drawn from a SATURATING set, where the kernels'
+formulas return exactly 0 or exactly z (act64 below), so the same argument holds for the activation-bearing instantiations:
+tests/test_exact_act_cpu.py and tests/test_exact_act_gpu.py.
 """
 
 from __future__ import annotations
@@ -79,6 +83,125 @@ def f32(t: torch.Tensor) -> torch.Tensor:
     if not torch.equal(out.double(), t.double()):
         raise ConditionViolated("a generated value is not an f32 number")
     return out.contiguous()
+
+
+# ------------------------------------------------------------------------------------- saturated SiLU / GELU (activation codes)
+ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 3
+ACTS = (ACT_SILU, ACT_GELU)
+SAT_NEG, SAT_POS = (-128, -96), (32, 64)
+SAT = SAT_NEG + SAT_POS
+SAT_LEAN = SAT_NEG + (32, 32)                       # where K or the row count is large: one positive level (still every other draw)
+SAT_DOWN = 2.0 ** -5                                # brings act(z) in {0, 32, 64} back to {0, 1, 2}: carried by the weights ...
+SAT_GATES = (2.0 ** -5, 2.0 ** -4)                  # ... or by the gates of the BN + gate prologue
+SAT_PROBE = (-65280, -32640, -2048, -256, -128, -96, 32, 64, 128, 256, 2048, 32640, 65280)   # the sets above and the reach of the epilogue tests
+SAT_PROBE_GELU = (-64, -32)                         # GELU only (the 64 Z + 32 lattice of gemm_bias_act): SiLU is not saturated there
+SAT_FLOOR = {1: -96, 3: -32}                        # act code -> the largest negative pre-activation a case may use (positive: >= 32)
+SAT_QUANTUM = 2.0 ** -7                             # the smallest quantum any case here works in (xhat of bn_add_act_bwd)
+
+
+def bn_state_sat(C: int, seed: int) -> torch.Tensor:
+    """[4, C] f64 state in front of a saturated activation: scale in {16, 32, 64}, shift in {-32, 0, 32}, integer mean, rstd in
+    {0.5, 1, 2}.  z - shift is a multiple of 32 for every z of SAT, so the raw input (z - shift) / scale is a multiple of 0.5 with
+    |raw| <= 10: bf16 holds it, and xhat = (raw - mean) * rstd stays a small multiple of 1/4 for the statistics."""
+    return torch.stack([pick((C,), seed, (16.0, 32.0, 64.0)), pick((C,), seed + 1, (-32, 0, 32)), pick((C,), seed + 2, (-1, 0, 1)),
+                        pick((C,), seed + 3, POW2)])
+
+
+def pick_balanced(shape, seed: int, vals) -> torch.Tensor:
+    """pick(), but every row (all dimensions behind the first, an even count) holds each value as often as its negative: the
+    operands behind an activation are >= 0, and a row of weights that adds up to zero keeps the mean of the outputs at zero."""
+    n = 1
+    for d in shape[1:]:
+        n *= d
+    assert n % 2 == 0
+    half = pick((shape[0], n // 2), seed, vals)
+    row = torch.cat([half, -half], 1)
+    g = torch.Generator().manual_seed(seed + 1)
+    perm = torch.argsort(torch.rand((shape[0], n), generator=g), 1)
+    return torch.gather(row, 1, perm).reshape(tuple(shape))
+
+
+def act64(z: torch.Tensor, act: int) -> torch.Tensor:
+    """The activation as the float64 reference applies it: identity for code none; for SiLU / GELU max(z, 0), which is the
+    correctly rounded value of the true function at every saturated z (tests/test_exact_act_cpu.py proves that for the sets
+    used) - and an error of the test's data anywhere else.
+
+    Saturation of the kernels' own formulas (csrc/dfd_common.h: sigmoid_f, gelu_parts and the packed-pair twins), emulated in f32
+    with exp(v) = exp2(v * log2 e) and rcp(v) = 1 / v: SiLU gives (-0, -0) for z <= -89 (exp(-z) overflows, rcp(inf) = 0) and
+    (z, 1) for z >= 17 (1 + exp(-z) rounds to 1); GELU gives (-0, 0) for z <= -16 and (z, 1) for z >= 6 (exp(-z*z / 2) underflows
+    or drops out of 1 - x).  Measured on an MI355X by test_saturated_activations_probe (tests/test_exact_act_gpu.py), f32 and
+    bf16, forward through bn_act_apply and derivative through act_bn_bwd: every point of SAT_PROBE, -65280 .. -96 and 32 .. 65280,
+    comes back as -0 / z with derivative -0 / 1 under SiLU and as -0 / z with derivative 0 / 1 under GELU, and so do -64 and -32
+    under GELU - the emulation's table, sign of zero included.  So the sets stay where the emulation put them.  (The probe holds
+    the points the cases use and some beyond; the exact thresholds -89 / 17 and -16 / 6 are the emulation's and were not searched
+    for on the device.)"""
+    if act == ACT_NONE:
+        return z
+    if not bool(((z <= SAT_FLOOR[act]) | (z >= 32)).all()):
+        raise ConditionViolated(f"a pre-activation lies outside the saturated ranges z <= {SAT_FLOOR[act]}, z >= 32")
+    return torch.where(z > 0, z, torch.zeros_like(z))
+
+
+def act_grad64(z: torch.Tensor, act: int) -> torch.Tensor:
+    if act == ACT_NONE:
+        return torch.ones_like(z)
+    act64(z, act)
+    return (z > 0).to(z.dtype)
+
+
+def emulate_act_f32(z: torch.Tensor, act: int):
+    """(act(z), act'(z)) by the kernels' formulas, operation for operation in f32 on the CPU (an FMA as the float64 sum rounded once
+    to f32 - exact for these operands up to double rounding, which cannot happen at a saturated point)."""
+    f = lambda t: t.to(F32)
+    fma = lambda a, b, c: f(a.double() * b.double() + c.double())
+    z = f(z)
+    one = torch.ones_like(z)
+    log2e = f(torch.tensor(1.44269504088896340736))
+    if act == ACT_SILU:
+        s = one / (one + torch.exp2(f(-z * log2e)))
+        return f(z * s), f(s * f(one + f(z * f(one - s))))
+    assert act == ACT_GELU
+    x = f(z.abs() * f(torch.tensor(0.70710678118654752)))
+    t = one / fma(f(torch.tensor(0.3275911)).expand_as(x), x, one)
+    ez = torch.exp2(f(f(-x * x) * log2e))
+    poly = f(torch.tensor(1.061405429)).expand_as(t)
+    for c in (-1.453152027, 1.421413741, -0.284496736, 0.254829592):
+        poly = fma(t, poly, f(torch.tensor(c)).expand_as(t))
+    half_erfc = f(f(f(torch.tensor(0.5)) * f(t * poly)) * ez)
+    cdf = torch.where(z >= 0, f(one - half_erfc), half_erfc)
+    return f(z * cdf), fma(f(z * f(torch.tensor(0.39894228040143268))), ez, cdf)
+
+
+def true_act64(z: torch.Tensor, act: int):
+    """(act(z), act'(z)) of the mathematical function, float64, written so that the tails keep their relative accuracy."""
+    z = z.double()
+    if act == ACT_SILU:
+        s = torch.sigmoid(z)
+        return z * s, s * (1 + z * (1 - s))
+    cdf = 0.5 * torch.special.erfc(-z / 2.0 ** 0.5)
+    return z * cdf, cdf + z * torch.exp(-0.5 * z * z) / (2 * torch.pi) ** 0.5
+
+
+def flush_denormals(t: torch.Tensor) -> torch.Tensor:
+    """|v| < 2**-126 -> 0: torch's f32 sigmoid / gelu on the CPU return a denormal (silu(-96) ~ -2e-40) where the kernels' formula
+    returns -0; the f32 oracle is compared after this flush."""
+    return torch.where(t.abs() < 2.0 ** -126, torch.zeros_like(t), t)
+
+
+def quantum_of(t: torch.Tensor) -> float:
+    """The largest power of two in 2**-10 .. 2**10 that divides every element."""
+    q = 2.0 ** 10
+    while q > 2.0 ** -10 and not torch.equal(t / q, (t / q).round()):
+        q /= 2
+    return q
+
+
+def nonzero_share(what: str, t: torch.Tensor) -> float:
+    """About half of the operands behind a saturated activation are exact zeros; a dropped term shows only where it was not one."""
+    share = float((t != 0).double().mean())
+    if share < 0.40:
+        raise ConditionViolated(f"{what}: only {share:.1%} of the operands behind the activation are non-zero")
+    return share
 
 
 # ------------------------------------------------------------------------------------------------------------- conditions
@@ -185,24 +308,29 @@ def _abs_stats(y):
 
 
 # ------------------------------------------------------------------------------------------------ 1x1 forward (pwconv)
-def prologue64(a, mode, coef=None, a2=None, gate=None):
-    """A operand [N, HW, K] after the GEMM prologue, float64, activation none."""
+def prologue64(a, mode, coef=None, a2=None, gate=None, act=ACT_NONE):
+    """A operand [N, HW, K] after the GEMM prologue, float64; `act` (modes 1 and 2) at saturated pre-activations only."""
     if mode == 0:
         return a
     if mode == 3:
         return coef[0] * a + coef[1] * a2 + coef[2]
-    v = coef[0] * a + coef[1]
+    v = act64(coef[0] * a + coef[1], act)
     return v * gate[:, None, :] if mode == 2 else v
 
 
-def pro_inputs(target, mode, seed):
-    """Raw inputs whose prologue of `mode` (0 none, 1 BN, 2 BN + gate, 3 affine2) gives `target` [N, HW, K]."""
+def pro_inputs(target, mode, seed, act=ACT_NONE):
+    """Raw inputs whose prologue of `mode` (0 none, 1 BN, 2 BN + gate, 3 affine2) gives `target` [N, HW, K].  With an activation
+    (modes 1 and 2) `target` is the PRE-activation z, drawn from a saturating set: the raw input is un_bn(z), the operand behind
+    the prologue max(z, 0), times a gate from SAT_GATES in mode 2."""
     N, _, K = target.shape
     if mode == 0:
         return NS(a=target, coef=None, a2=None, gate=None)
     if mode == 3:
         coef, a2 = coef3(K, seed), pick(target.shape, seed + 5, S2)
         return NS(a=un_affine2(target, a2, coef), coef=coef, a2=a2, gate=None)
+    if act != ACT_NONE:
+        st = bn_state_sat(K, seed)
+        return NS(a=un_bn(target, st), coef=st, a2=None, gate=pick((N, K), seed + 7, SAT_GATES) if mode == 2 else None)
     st = bn_state(K, seed)
     if mode == 1:
         return NS(a=un_bn(target, st), coef=st, a2=None, gate=None)
@@ -260,6 +388,59 @@ def pw_fwd(ci: int, mode: int):
               out_res=(out + res).view(N, HW, 1, No))
 
 
+# The tiers of PW_FWD_CASES that take a prologue, and a ring shape whose 64-row tiles span four images (HW = 25; M = 1000 is 16 row
+# tiles, the ring kernel's minimum): with HW = 64 (aligned), 103 and 197 above, the gate table of a tile holds 4, 1, 2 and 2 images
+PW_ACT_CASES = [c for c in PW_FWD_CASES if c[0] != "gemm"] + [("ring", (40, 25, 136, 24), S2, S1)]
+PW_ACT_MODES = (1, 2)
+
+
+@functools.lru_cache(maxsize=4)
+def pw_fwd_act(ci: int, mode: int, act: int):
+    """pw_fwd for BN + act and BN + act + gate at saturated pre-activations: A = max(z, 0) [* gate]; the weights carry 2**-5 in mode 1,
+    the gates in mode 2, so A w^T is a sum of small integers.  The weight rows are balanced (pick_balanced)."""
+    tier, (N, HW, K, No), _, wset = PW_ACT_CASES[ci]
+    what = f"pwconv {tier} {(N, HW, K, No)} mode {mode} act {act}"
+    z = pick((N, HW, K), 100 + ci, SAT_LEAN if N * HW >= 65536 else SAT)
+    inp = pro_inputs(z, mode, 200 + ci, act)
+    w = pick_balanced((No, K), 300 + ci, wset) * (SAT_DOWN if mode == 1 else 1.0)
+    A = prologue64(inp.a, mode, inp.coef, None, inp.gate, act)
+    out = A @ w.t()
+    share = nonzero_share(what, A)
+    check_exact(what, operands=[("a", inp.a, DTYPES), ("A", A, DTYPES), ("w", w, DTYPES)],
+                reductions=[("a w^T", A.abs() @ w.abs().t(), 1.0)], results=[("out", out, DTYPES)],
+                stats=[("sum y*y", _abs_stats(out), 1.0)])
+    return NS(what=what, tier=tier, shape=(N, HW, K, No), mode=mode, act=act, a=f32(inp.a).view(N, HW, 1, K), w=f32(w), coef=f32(inp.coef),
+              a2=None, gate=None if inp.gate is None else f32(inp.gate), A=A, out=out.view(N, HW, 1, No), sums=sums64(out), has_stats=True,
+              has_res=False, share=share, z=z)
+
+
+# The eval form: out = act(scale * y + shift) behind the product, SiLU only.  y is an integer, scale in {256, 512} and shift = +-scale / 2, so
+# z = (scale / 2) (2 y +- 1) is never 0 and |z| >= 128: saturated on either side whatever the product gives
+PW_EVAL_CASES = (0, 2, 4, 5)                     # indices into PW_FWD_CASES: panel-resident and tile kernel, |y| <= 127
+
+
+def eval_state(C: int, seed: int) -> torch.Tensor:
+    scale = pick((C,), seed, (256.0, 512.0))
+    return torch.stack([scale, scale / 2 * pick((C,), seed + 1, S1)])
+
+
+def eval_result(what: str, y: torch.Tensor, st: torch.Tensor, dtypes) -> torch.Tensor:
+    out = act64(st[0] * y + st[1], ACT_SILU)
+    for dt in dtypes:
+        if not representable(out, dt):
+            raise ConditionViolated(f"{what}: the activated output is not exactly representable in {dt}")
+    nonzero_share(what, out)
+    return out
+
+
+@functools.lru_cache(maxsize=2)
+def pw_eval(ci: int):
+    c = pw_fwd(ci, 0)
+    No = c.shape[3]
+    st = eval_state(No, 450 + ci)
+    return NS(what=f"pwconv_eval {c.shape}", c=c, st=f32(st), out=eval_result(f"pwconv_eval {c.shape}", c.out.double(), st, DTYPES))
+
+
 # ------------------------------------------------------------------------------------------ 1x1 weight gradient (pwconv_wgrad)
 # (N, HW, Ni, Nj): p [N, HW, 1, Ni], q [N, HW, 1, Nj]; dw [Ni, Nj].  The PW_CASES shapes of tests/test_ops_gpu.py and two whose
 # row count is 64 * 40 + 1 / 64 * 40 - 1: the last reduction step of the last split holds one row / misses one row
@@ -271,15 +452,45 @@ WGRAD_LARGE_CASES = [(2, 100003, 32, 8), (3, 66001, 24, 144), (3, 66003, 144, 24
 WGRAD_LARGE_MODES = [(0, 0), (3, 0), (0, 3)]
 
 
-@functools.lru_cache(maxsize=6)
-def pw_wgrad(case, pmode: int, qmode: int, large: bool = False):
+# with SiLU / GELU: the tiled kernel takes BN + act and BN + act + gate on q; the wave-autonomous kernel takes them on its WIDE operand
+# only, BN + act + gate with SiLU and either mode of its narrow operand, BN + act with SiLU or GELU and affine2 on the narrow one
+WGRAD_TILED_ACT_MODES = [(pm, qm) for pm in (0, 3) for qm in (1, 2)]
+WGRAD_LARGE_ACT_MODES = [(0, 2, ACT_SILU), (3, 2, ACT_SILU), (3, 1, ACT_SILU), (3, 1, ACT_GELU)]      # (narrow mode, wide mode, act)
+
+
+def tnw_serves(case, narrow_mode: int, wide_mode: int, act: int) -> bool:
+    """The conditions under which pwconv_wgrad runs the wave-autonomous kernel in bf16 (dfd_pw_tnw / tnw_launch in csrc/dfd_pwtnw.hip;
+    it has no plan function): M >= 196,608, narrow operand <= 32 channels, wide one <= 128 or 144, narrow mode none / affine2, a gate
+    only with SiLU and H*W >= the 32- or 16-row step, BN + act only behind affine2 and with SiLU or GELU."""
     N, HW, Ni, Nj = case
-    what = f"pwconv_wgrad {case} p{pmode} q{qmode}"
+    narrow, wide = min(Ni, Nj), max(Ni, Nj)
+    ok = N * HW >= 2048 * 32 * 3 and narrow <= 32 and (wide <= 128 or (wide <= 144 and wide % 16 == 0)) and narrow_mode in (0, 3)
+    if wide_mode == 2:
+        return ok and act == ACT_SILU and HW >= (32 if wide <= 96 else 16)
+    if wide_mode == 1:
+        return ok and narrow_mode == 3 and act in ACTS
+    return ok and not (wide_mode == 3 and narrow_mode == 3)
+
+
+@functools.lru_cache(maxsize=6)
+def pw_wgrad(case, pmode: int, qmode: int, large: bool = False, act: int = ACT_NONE):
+    """With `act` the operand whose mode is 1 or 2 has saturated pre-activations (max(z, 0), times a gate from SAT_GATES in mode 2);
+    in mode 1 the OTHER operand carries the 2**-5 instead, so every term of the sum is an integer either way."""
+    N, HW, Ni, Nj = case
+    what = f"pwconv_wgrad {case} p{pmode} q{qmode}" + (f" act {act}" if act else "")
     vals = S1 if large else S3
-    P = pick((N, HW, Ni), 500 + Ni, vals)
-    Q = pick((N, HW, Nj), 600 + Nj, vals)
-    ip, iq = pro_inputs(P, pmode, 700 + Ni), pro_inputs(Q, qmode, 800 + Nj)
-    Pa, Qa = prologue64(ip.a, pmode, ip.coef, ip.a2, ip.gate), prologue64(iq.a, qmode, iq.coef, iq.a2, iq.gate)
+    sat = {m: act != ACT_NONE and m in (1, 2) for m in (pmode, qmode)}
+    assert not (sat[pmode] and sat[qmode])
+
+    def target(shape, seed, mine, other):
+        if sat[mine]:
+            return pick(shape, seed, SAT)
+        return pick(shape, seed, vals) * (SAT_DOWN if sat[other] and other == 1 else 1.0)
+
+    P, Q = target((N, HW, Ni), 500 + Ni, pmode, qmode), target((N, HW, Nj), 600 + Nj, qmode, pmode)
+    ip, iq = pro_inputs(P, pmode, 700 + Ni, act), pro_inputs(Q, qmode, 800 + Nj, act)
+    Pa, Qa = prologue64(ip.a, pmode, ip.coef, ip.a2, ip.gate, act), prologue64(iq.a, qmode, iq.coef, iq.a2, iq.gate, act)
+    share = min([nonzero_share(what, t) for t, m in ((Pa, pmode), (Qa, qmode)) if sat[m]], default=1.0)
     M = N * HW
     dw = Pa.reshape(M, Ni).t() @ Qa.reshape(M, Nj)
     pre = pick((Ni, Nj), 900, S3)
@@ -288,12 +499,14 @@ def pw_wgrad(case, pmode: int, qmode: int, large: bool = False):
                 + [(n, t, DTYPES) for n, t in (("p2", ip.a2), ("q2", iq.a2)) if t is not None],
                 reductions=[("p^T q", Pa.abs().reshape(M, Ni).t() @ Qa.abs().reshape(M, Nj) + pre.abs(), 1.0)],
                 results=[("dw", dw, (F32,)), ("dw + preload", dw + pre, (F32,))])
+    if quantum_of(Pa) * quantum_of(Qa) < 1.0:
+        raise ConditionViolated(f"{what}: the terms of the sum are no integers")
 
     def ship(i, n):
         return NS(a=f32(i.a).view(N, HW, 1, n), coef=None if i.coef is None else f32(i.coef),
                   a2=None if i.a2 is None else f32(i.a2).view(N, HW, 1, n), gate=None if i.gate is None else f32(i.gate))
 
-    return NS(what=what, shape=case, p=ship(ip, Ni), q=ship(iq, Nj), P=Pa, Q=Qa, dw=dw, pre=f32(pre), dw_acc=dw + pre)
+    return NS(what=what, shape=case, p=ship(ip, Ni), q=ship(iq, Nj), P=Pa, Q=Qa, dw=dw, pre=f32(pre), dw_acc=dw + pre, act=act, share=share)
 
 
 # -------------------------------------------------------------------------------------- fused expand backward (pwconv_bwd_fused)
@@ -323,6 +536,8 @@ def pw_fused(case):
 # N, H, W, C, k, s, pt, pl: the ragged and asymmetric entries of DW_CASES in tests/test_ops_gpu.py
 DW_CASES = [(2, 15, 13, 24, 3, 2, 0, 0), (2, 16, 16, 48, 5, 2, 1, 1), (2, 29, 31, 192, 3, 1, 1, 1), (3, 9, 9, 8, 3, 1, 1, 1),
             (2, 7, 7, 1152, 5, 1, 2, 2)]
+# the matrix-core forward plans another tile behind an activating prologue here (two images per tile instead of one; three images: ragged)
+DW_MM_ACT_CASE = (3, 9, 9, 96, 5, 2, 2, 2)
 DW_SQUEEZED_CASE = (6, 30, 30, 144, 3, 1, 1, 1)      # several work items per workgroup once dfd_tune keys 8-11 squeeze the grid
 
 
@@ -346,34 +561,63 @@ def dwconv_bwd64(dy, xa, w, k, s, pt, pl):
 
 
 @functools.lru_cache(maxsize=2)
-def dw(case):
+def dw(case, act: int = ACT_NONE):
     """One data set per shape.  xt / dyt: the operands as the kernels see them behind the BN prologue / the BN-backward map (also
-    the inputs of the variants without them); x / dz: the raw inputs whose prologue / map gives them."""
+    the inputs of the variants without them); x / dz: the raw inputs whose prologue / map gives them.
+    With `act` the prologue is BN + SiLU / GELU at saturated pre-activations z: xt = max(z, 0) in {0, 32, 64}, the weights carry 2**-5
+    and the output gradient 2**5, so y, the data gradient and its act' epilogue (dzin = da where z > 0, else 0) are small integers."""
     N, H, W, C, k, s, pt, pl = case
-    what = f"depthwise {case}"
+    what = f"depthwise {case}" + (f" act {act}" if act else "")
     Ho, Wo = -(-H // s), -(-W // s)
-    xt = pick((N, H, W, C), 2000 + C, S3 if k == 3 else S2)
-    w = pick((C, 1, k, k), 2100 + C, S3)
-    st = bn_state(C, 2200 + C)
-    x = un_bn(xt, st)
-    dyt = pick((N, Ho, Wo, C), 2300 + C, S2)
+    if act:
+        z = pick((N, H, W, C), 2000 + C, SAT)
+        st = bn_state_sat(C, 2200 + C)
+        x, xt = un_bn(z, st), act64(z, act)
+        w = pick((C, 1, k, k), 2100 + C, S3) * SAT_DOWN
+        dyt = pick((N, Ho, Wo, C), 2300 + C, S2) / SAT_DOWN
+        share = nonzero_share(what, xt)
+    else:
+        xt = pick((N, H, W, C), 2000 + C, S3 if k == 3 else S2)
+        w = pick((C, 1, k, k), 2100 + C, S3)
+        st = bn_state(C, 2200 + C)
+        x = un_bn(xt, st)
+        z = xt
+        dyt = pick((N, Ho, Wo, C), 2300 + C, S2)
+        share = 1.0
     coef, yraw = coef3(C, 2400 + C), pick((N, Ho, Wo, C), 2500 + C, S2)
     dz = un_affine2(dyt, yraw, coef)
-    xa, dy = st[0] * x + st[1], coef[0] * dz + coef[1] * yraw + coef[2]
+    xa, dy = act64(st[0] * x + st[1], act), coef[0] * dz + coef[1] * yraw + coef[2]
     y = dwconv64(xa, w, k, s, pt, pl, Ho, Wo)
     da, dwt = dwconv_bwd64(dy, xa, w, k, s, pt, pl)
     da_abs, dwt_abs = dwconv_bwd64(dy.abs(), xa.abs(), w.abs(), k, s, pt, pl)
+    dzin = da * act_grad64(z, act)
     xhat = (x - st[2]) * st[3]
     check_exact(what,
                 operands=[("x", x, DTYPES), ("xa", xa, DTYPES), ("w", w, DTYPES), ("dz", dz, DTYPES), ("yraw", yraw, DTYPES),
                           ("dy", dy, DTYPES)],
                 reductions=[("taps", dwconv64(xa.abs(), w.abs(), k, s, pt, pl, Ho, Wo), 1.0), ("taps^T", da_abs, 1.0),
-                            ("dy * xa", dwt_abs, 1.0)],
-                results=[("y", y, DTYPES), ("dzin", da, DTYPES), ("dw", dwt, (F32,))],
+                            ("dy * xa", dwt_abs, quantum_of(dy) * quantum_of(xa) if act else 1.0)],
+                results=[("y", y, DTYPES), ("da", da, DTYPES), ("dzin", dzin, DTYPES), ("dw", dwt, (F32,))],
                 stats=[("sum y*y", _abs_stats(y), 1.0),
-                       ("sum |dzin * xhat|", (da.abs() * xhat.abs()).reshape(-1, C).sum(0), 1.0 / 16)])
+                       ("sum |dzin * xhat|", (dzin.abs() * xhat.abs()).reshape(-1, C).sum(0), 1.0 / 16)])
+    if quantum_of(xa) * quantum_of(w) < 1.0 or quantum_of(dy) * quantum_of(w) < 1.0 or quantum_of(xhat) < 1.0 / 16:
+        raise ConditionViolated(f"{what}: a term is no multiple of its quantum")
     return NS(what=what, shape=case, Ho=Ho, Wo=Wo, x=f32(x), xt=f32(xt), w=f32(w), st=f32(st), dz=f32(dz), dyt=f32(dyt),
-              yraw=f32(yraw), coef=f32(coef), y=y, y_sums=sums64(y), dzin=da, dzin_sums=sums_xhat64(da, x, st), dw=dwt)
+              yraw=f32(yraw), coef=f32(coef), y=y, y_sums=sums64(y), da=da, dzin=dzin, dzin_sums=sums_xhat64(dzin, x, st), dw=dwt,
+              act=act, share=share)
+
+
+@functools.lru_cache(maxsize=2)
+def dw_eval(case):
+    """dwconv_eval: act(scale * dwconv(x) + shift) stored activated (SiLU), on the integer data of dw(case); and the channel sums of the
+    stored tensor per image, which the kernel leaves as per-(tile, image) partial rows."""
+    c = dw(case)
+    C = case[3]
+    what = f"dwconv_eval {case}"
+    st = eval_state(C, 2600 + C)
+    out = eval_result(what, c.y, st, DTYPES)
+    check_exact(what, reductions=[("sums of the stored tensor", out.sum((1, 2)), quantum_of(out))], results=[("sums", out.sum((1, 2)), (F32,))])
+    return NS(what=what, c=c, st=f32(st), out=out, img_sums=out.sum((1, 2)))
 
 
 # ------------------------------------------------------------------------------------------------------------------- stem
@@ -419,21 +663,30 @@ ROW_CASES = [(4, 5, 3, 672), (2, 8, 8, 1280), (3, 56, 56, 96), (3, 64, 64, 96)]
 
 
 @functools.lru_cache(maxsize=2)
-def rows(case):
+def rows(case, act: int = ACT_NONE):
+    """With `act`: scale * y + shift = z from the saturating set, the pooling kernels add up max(z, 0), and dz = (...) * act'(z) is the
+    plain dz where z > 0 and 0 elsewhere."""
     N, H, W, C = case
-    what = f"row passes {case}"
+    what = f"row passes {case}" + (f" act {act}" if act else "")
     HW = H * W
     pow2_hw = HW & (HW - 1) == 0
-    st = bn_state(C, 4000 + C)
-    at = pick(case, 4100 + C, S2)                      # scale * y + shift, what the pooling kernels add up
-    y = un_bn(at, st)
+    if act:
+        st = bn_state_sat(C, 4000 + C)
+        z = pick(case, 4100 + C, SAT)
+        at, mask = act64(z, act), act_grad64(z, act)
+        share = nonzero_share(what, at)
+    else:
+        st = bn_state(C, 4000 + C)
+        z = pick(case, 4100 + C, S2)
+        at, mask, share = z, torch.ones_like(z), 1.0   # scale * y + shift, what the pooling kernels add up
+    y = un_bn(z, st)
     g = 2.0 * pick(case, 4200 + C, S2)                 # even: g * gate stays an integer
     rs = pick((N,), 4300, POW2)
     gate = pick((N, C), 4400, POW2)
     dpool = HW * pick((N, C), 4500, S3)                # dpool / (H*W) is an integer
     xhat = (y - st[2]) * st[3]
     rsb, gb, qb = rs[:, None, None, None], gate[:, None, None, :], (dpool / HW)[:, None, None, :]
-    dzs = [g, g * gb + qb, qb.expand(N, H, W, C)]
+    dzs = [g * mask, (g * gb + qb) * mask, qb.expand(N, H, W, C) * mask]
     flat = lambda t: t.reshape(-1, C)
     # f32 at an H*W that is no power of two: the stored dz is off by e = one f32 ulp of the quotient (plus the half ulp of the sum it
     # is a term of, mode 1), so the kernel's sums are no longer sums of exact terms.  Bound of ANY f32 summation order over n rows:
@@ -442,21 +695,82 @@ def rows(case):
     rows_n = N * H * W
     sum_tol = [None]
     for m in (1, 2):
-        e = _spacing(qb.to(F32)).expand(N, H, W, C) + (0.5 * _spacing(dzs[m].to(F32)) if m == 1 else 0.0)
+        e = (_spacing(qb.to(F32)).expand(N, H, W, C) + (0.5 * _spacing(dzs[m].to(F32)) if m == 1 else 0.0)) * mask
         u = (rows_n + 2) * 2.0 ** -24 * 1.01
         sum_tol.append(torch.stack([flat(e).sum(0) + u * flat(dzs[m]).abs().sum(0),
                                     flat(e * xhat.abs()).sum(0) + u * flat(dzs[m] * xhat).abs().sum(0)]))
     check_exact(what,
-                operands=[("y", y, DTYPES), ("a", st[0] * y + st[1], DTYPES), ("g", g, DTYPES), ("g * rs", g * rsb, DTYPES)],
+                operands=[("y", y, DTYPES), ("z", st[0] * y + st[1], DTYPES), ("a", at, DTYPES), ("g", g, DTYPES), ("g * rs", g * rsb, DTYPES)],
                 reductions=[("pool", at.abs().sum((1, 2)), 1.0), ("pool bwd", (at * g).abs().sum((1, 2)), 1.0)],
-                results=[(f"dz mode {m}", d, DTYPES) for m, d in enumerate(dzs)],
+                results=[(f"dz mode {m}", d, DTYPES) for m, d in enumerate(dzs)] + [("act(z)", at, DTYPES)],
                 stats=[("sum |g rs|", flat(g * rsb).abs().sum(0), 0.5), ("sum |g rs xhat|", flat(g * rsb * xhat).abs().sum(0), 1.0 / 32),
                        ("sum g*g", flat(g * g).sum(0), 1.0)]
                 + [(f"sum |dz xhat| mode {m}", flat(d * xhat).abs().sum(0), 1.0 / 16) for m, d in enumerate(dzs)])
+    if not torch.equal(st[0] * y + st[1], z) or quantum_of(xhat) < 1.0 / 16:
+        raise ConditionViolated(f"{what}: the BN of the raw input is not the pre-activation, or xhat is finer than 1/16")
     return NS(what=what, shape=case, HW=HW, pow2_hw=pow2_hw, y=f32(y), g=f32(g), st=f32(st), rs=f32(rs), gate=f32(gate), dpool=f32(dpool),
               red=sums_xhat64(g, y, st), red_rs=sums_xhat64(g * rsb, y, st), bias=flat(g).sum(0), bias_rs=flat(g * rsb).sum(0),
               dz=dzs, dz_sums=[sums_xhat64(d, y, st) for d in dzs], pooled=at.sum((1, 2)) / HW, pool_bwd=(at * g).sum((1, 2)), quot=qb, dz_sum_tol=sum_tol,
-              g_stats=sums64(g), at=at)
+              g_stats=sums64(g), at=at, act=act, share=share)
+
+
+ADD_ACT_CASE = (3, 7, 7, 40)
+
+
+@functools.lru_cache(maxsize=2)
+def bn_add(act: int):
+    """bn_add_act / bn_add_act_bwd: out = act(scale * y + shift + other), d = g * act'(..), sums (d, d * xhat).  The pre-activation z is
+    from the saturating set, the addend a small integer, so the raw y = (z - other - shift) / scale is a multiple of 1/64."""
+    N, H, W, C = ADD_ACT_CASE
+    what = f"bn_add_act {ADD_ACT_CASE} act {act}"
+    st = bn_state_sat(C, 4900)
+    z, other, g = pick(ADD_ACT_CASE, 4901, SAT), pick(ADD_ACT_CASE, 4902, S3), pick(ADD_ACT_CASE, 4903, S3)
+    y = (z - other - st[1]) / st[0]
+    pre = st[0] * y + st[1] + other
+    out, d = act64(pre, act), g * act_grad64(pre, act)
+    xhat = (y - st[2]) * st[3]
+    nonzero_share(what, out)
+    check_exact(what, operands=[("y", y, DTYPES), ("other", other, DTYPES), ("g", g, DTYPES), ("bn(y)", st[0] * y + st[1], (F32,))],
+                results=[("out", out, DTYPES), ("d", d, DTYPES)],
+                stats=[("sum |d|", d.abs().reshape(-1, C).sum(0), 1.0), ("sum |d xhat|", (d * xhat).abs().reshape(-1, C).sum(0), SAT_QUANTUM)])
+    if not torch.equal(pre, z) or quantum_of(xhat) < SAT_QUANTUM:
+        raise ConditionViolated(f"{what}: the pre-activation is not the chosen z, or xhat is finer than 2**-7")
+    return NS(what=what, act=act, y=f32(y), other=f32(other), g=f32(g), st=f32(st), out=out, d=d, d_sums=sums_xhat64(d, y, st), pre=pre)
+
+
+def probe_points(act: int):
+    return SAT_PROBE + (SAT_PROBE_GELU if act == ACT_GELU else ())
+
+
+@functools.lru_cache(maxsize=2)
+def act_probe(act: int):
+    """Every probe point in every channel position of a [1, points, 1, 16] tensor: the raw input is z / 32 behind a BN of scale 32."""
+    C = 16
+    pts = probe_points(act)
+    z = torch.tensor(pts, dtype=torch.float64).view(1, -1, 1, 1).expand(1, len(pts), 1, C).contiguous()
+    st = torch.stack([torch.full((C,), 32.0), torch.zeros(C), torch.zeros(C), torch.ones(C)]).double()
+    y = un_bn(z, st)
+    fwd, grad = torch.where(z > 0, z, torch.zeros_like(z)), (z > 0).double()
+    check_exact("activation probe", operands=[("y", y, DTYPES), ("z", z, DTYPES)])
+    return NS(z=z, y=f32(y), st=f32(st), ones=f32(torch.ones_like(z)), fwd=fwd, grad=grad)
+
+
+MX_ROWS_CASE = (257, 256)                              # M, K of mx_quant_rows behind a saturated prologue (tests/test_mx_gpu.py)
+
+
+@functools.lru_cache(maxsize=2)
+def mx_rows(act: int):
+    """mx_quant_rows behind BN + act: the values to quantise are max(z, 0) in {0, 32, 64}, which e4m3 with a power-of-two block scale
+    holds exactly; the first block of row 0 is negative throughout (an all-zero block behind the activation)."""
+    M, Kd = MX_ROWS_CASE
+    z = pick((M, Kd), 4950, SAT)
+    z[0, :32] = pick((32,), 4951, SAT_NEG)
+    st = bn_state_sat(Kd, 4952)
+    a = un_bn(z, st)
+    want = act64(st[0] * a + st[1], act)
+    nonzero_share(f"mx_quant_rows act {act}", want)
+    check_exact(f"mx_quant_rows act {act}", operands=[("a", a, DTYPES), ("act(z)", want, DTYPES + (torch.float8_e4m3fn,))])
+    return NS(a=f32(a), st=f32(st), want=want)
 
 
 SUM_ROWS_P = (1, 33, 1025)
@@ -514,16 +828,26 @@ def col2im64(dcol, in_shape, k, s, p):
 
 
 @functools.lru_cache(maxsize=2)
-def conv(case):
+def conv(case, act: int = ACT_NONE):
+    """With `act`: BN + act in front of the convolution at saturated pre-activations, xa = max(z, 0) in {0, 32}; the weights (balanced
+    rows) carry 2**-5, so y is a sum of up to 9 C values from {-1, 0, 1}; the weight gradient is a multiple of 32."""
     k, s, p, C, Co, H, N = case
-    what = f"dense conv {case}"
+    what = f"dense conv {case}" + (f" act {act}" if act else "")
     Ho = (H + 2 * p - k) // s + 1
     M, Kd = N * Ho * Ho, k * k * C
-    xt = pick((N, H, H, C), 5000 + C, S1)
-    st = bn_state(C, 5100 + C)
-    x = un_bn(xt, st)
-    w = pick((Co, C, k, k), 5200 + Co, S1)
-    xa = st[0] * x + st[1]
+    if act:
+        z = pick((N, H, H, C), 5000 + C, SAT_LEAN)
+        st = bn_state_sat(C, 5100 + C)
+        x, xt = un_bn(z, st), act64(z, act)
+        w = pick_balanced((Co, C, k, k), 5200 + Co, S1) * SAT_DOWN
+        share = nonzero_share(what, xt)
+    else:
+        xt = pick((N, H, H, C), 5000 + C, S1)
+        st = bn_state(C, 5100 + C)
+        x = un_bn(xt, st)
+        w = pick((Co, C, k, k), 5200 + Co, S1)
+        share = 1.0
+    xa = act64(st[0] * x + st[1], act)
     conv64 = lambda a, ww: F.conv2d(a.permute(0, 3, 1, 2), ww, stride=s, padding=p).permute(0, 2, 3, 1)
     y = conv64(xa, w)
     P = pick((N, Ho, Ho, Co), 5300 + Co, S1)
@@ -534,6 +858,9 @@ def conv(case):
     dw = Pa.reshape(M, Co).t() @ col.reshape(M, Kd)
     dcol = pick((N, Ho, Ho, Kd), 5600 + C, S1)
     dx = col2im64(dcol, (N, H, H, C), k, s, p)
+    qa = quantum_of(xa) if act else 1.0                      # |P| = 1 and |col| <= qa: at most M quanta per sum
+    if float(xa.abs().max()) > qa or quantum_of(xa) * quantum_of(w) < 1.0:
+        raise ConditionViolated(f"{what}: the operand behind the prologue is not in {{-q, 0, q}}, or a tap is no integer")
     check_exact(what,
                 operands=[("x", x, DTYPES), ("xa", xa, DTYPES), ("w", w, DTYPES), ("p", praw, DTYPES), ("p2", p2, DTYPES), ("P", Pa, DTYPES),
                           ("dcol", dcol, DTYPES)],
@@ -541,7 +868,7 @@ def conv(case):
                             ("col2im", col2im64(dcol.abs(), (N, H, H, C), k, s, p), 1.0)],
                 results=[("y", y, DTYPES), ("dw", dw, (F32,)), ("dx", dx, DTYPES)], stats=[("sum y*y", _abs_stats(y), 1.0)])
     return NS(what=what, shape=case, Ho=Ho, x=f32(x), xt=f32(xt), st=f32(st), w=f32(w), y=y, y_sums=sums64(y), p=f32(praw), pt=f32(P),
-              p2=f32(p2), coef=f32(coef), dw=dw, dcol=f32(dcol), dx=dx)
+              p2=f32(p2), coef=f32(coef), dw=dw, dcol=f32(dcol), dx=dx, xa=xa, act=act, share=share)
 
 
 # ----------------------------------------------------------------------------------------- matrix products of the ViT path
@@ -598,21 +925,34 @@ def linear():
 GEMM_BIAS_ACT_CASE = (256 * 80 + 17, 192, 520)          # M, K, N: served by dfd_gemm_bias_act (tests/test_vit_ops_gpu.py)
 
 
-@functools.lru_cache(maxsize=1)
-def gemm_bias_act():
-    """out = (scale * y + shift) * row_scale + residual with y = a w^T.  K is even and the operands are odd, so y is even; scale in
-    {1, 2} and an even shift keep scale * y + shift even, so the row scales {0.5, 1} leave an integer for the bf16 store."""
+@functools.lru_cache(maxsize=2)
+def gemm_bias_act(act: int = ACT_NONE):
+    """out = act(scale * y + shift) * row_scale + residual with y = a w^T.  K is even and the operands are odd, so y is even; scale in
+    {1, 2} and an even shift keep scale * y + shift even, so the row scales {0.5, 1} leave an integer for the bf16 store.
+    With the GELU epilogue: scale 32 and shift 32 * (an odd number) put z = 32 (y + odd) into 64 Z + 32, which is never 0 and
+    saturated either side; the row scales 2**-5 and 2**-4 bring max(z, 0) back to a small integer."""
     M, Kd, N = GEMM_BIAS_ACT_CASE
     a, w = pick((M, Kd), 6500, S1), pick((N, Kd), 6501, S1)
     y = matmul_case("gemm_bias_act product", a, w.t(), (BF16,), (BF16,))
-    st = torch.stack([pick((N,), 6502, (1.0, 2.0)), pick((N,), 6503, (-2, 0, 2))])
-    rs, res = pick((M,), 6504, (0.5, 1.0)), pick((M, N), 6505, S3)
+    if act:
+        st = torch.stack([torch.full((N,), 32.0, dtype=torch.float64), 32.0 * pick((N,), 6503, (-3, -1, 1, 3))])
+        rs = pick((M,), 6504, SAT_GATES)
+    else:
+        st = torch.stack([pick((N,), 6502, (1.0, 2.0)), pick((N,), 6503, (-2, 0, 2))])
+        rs = pick((M,), 6504, (0.5, 1.0))
+    res = pick((M, N), 6505, S3)
     z = st[0] * y + st[1]
-    out = z * rs[:, None] + res
-    check_exact("gemm_bias_act epilogue", operands=[("z", z, (BF16,)), ("z * rs", z * rs[:, None], (BF16,)), ("res", res, (BF16,))],
+    if act and not torch.equal((z - 32) / 64, ((z - 32) / 64).round()):
+        raise ConditionViolated("gemm_bias_act: a pre-activation is not in 64 Z + 32")
+    za = act64(z, act)
+    if act:
+        nonzero_share("gemm_bias_act", za)
+    out = za * rs[:, None] + res
+    check_exact("gemm_bias_act epilogue", operands=[("z", z, (BF16,) if not act else (F32,)), ("act(z) * rs", za * rs[:, None], (BF16,)),
+                                                    ("res", res, (BF16,))],
                 results=[("out", out, (BF16,))])
     return NS(a=f32(a).view(M, 1, 1, Kd), w=f32(w), st=f32(st), rs=f32(rs), res=f32(res).view(M, 1, 1, N), y=y.view(M, 1, 1, N),
-              out=out.view(M, 1, 1, N))
+              out=out.view(M, 1, 1, N), act=act, z=z)
 
 
 @functools.lru_cache(maxsize=1)

@@ -13,10 +13,14 @@ reference bit for bit.  The conditions under which that holds are asserted on th
   * every reduction has sum |term| <= 2**24 quanta, so every f32 summation order is exact;
   * every bf16-stored result is an integer with |v| <= 256, every f32 result has |v| <= 2**24;
   * statistics: the bound holds for the total over all rows, so device-side and host-side partial sums are both exact.
-A case that violates one is an error of the test, never a skip; no element is masked or left out of a comparison.  Only the
-activation code "none" gives exact arithmetic, so it is used wherever an entry point takes one; an entry point that declines it
-for some prologue is covered with the prologues it does accept.  tests/test_exact_cpu.py checks the same cases (conditions, and the
-f32 oracle on the same data) on any machine.
+A case that violates one is an error of the test, never a skip; no element is masked or left out of a comparison.  This file uses
+the activation code "none" wherever an entry point takes one; an entry point that declines it for some prologue is covered with
+the prologues it does accept.  The SiLU / GELU instantiations are exact too where the activation SATURATES: with pre-activations
+from {-128, -96, 32, 64} the kernels' own formulas return exactly 0 and exactly z (derivative 0 and 1), so SiLU and GELU act as a
+ReLU computed through the real SiLU / GELU code and the argument above carries over.  Those cases - the variants that cannot be
+reached with "none" at all among them - are in tests/test_exact_act_gpu.py (sets, thresholds and the probe that measures them:
+tests/_exact.py, act64).  tests/test_exact_cpu.py and tests/test_exact_act_cpu.py check the same cases (conditions, and the f32 oracle
+on the same data) on any machine.
 
 Two quantities are not bit-exact by nature, because a multiplication by the rounded reciprocal and a division differ by up to one
 f32 ulp: the pooled mean and the dpool / (H*W) term of act_bn_bwd.  Where H*W is a power of two they are exact as well; elsewhere
@@ -84,22 +88,22 @@ def part_sums(parts, n, C):
     return parts[: n * 2 * C].view(n, 2, C).double().sum(0).cpu()
 
 
-def make_pro(K, i, mode, HW, rd):
+def make_pro(K, i, mode, HW, rd, act=ACT_NONE):
     """Prologue struct of `mode` (0 none, 1 BN, 2 BN + gate, 3 affine2) over the inputs of a builder; the tensors stay alive with it."""
     if mode == 0:
         return None
     if mode == 3:
         return K.pro_affine2(dev(i.a2, rd), dev(i.coef))
     if mode == 1:
-        return K.pro_bn_act(dev(i.coef), ACT_NONE)
-    return K.pro_bn_act_gate(dev(i.coef), ACT_NONE, dev(i.gate), HW)
+        return K.pro_bn_act(dev(i.coef), act)
+    return K.pro_bn_act_gate(dev(i.coef), act, dev(i.gate), HW)
 
 
 # ======================================================================================================== 1x1 forward
 def _pw_fwd(K, c, rd):
     N, HW, Kd, No = c.shape
     a = dev(c.a, rd)
-    pro = make_pro(K, c, c.mode, HW, rd)
+    pro = make_pro(K, c, c.mode, HW, rd, getattr(c, "act", ACT_NONE))
     w_nk, _ = K.prep_weights(dev(c.w), rd, True, False)
     out, parts, n = K.pwconv(a, pro, w_nk, None, stats=c.has_stats)
     same(out, c.out, f"{c.what} {rd}: out")
@@ -152,7 +156,7 @@ def _wgrad_into(K, p, pro_p, q, pro_q, dw, accumulate):
 def _wgrad(K, c, pmode, qmode, rd, accumulate):
     N, HW, Ni, Nj = c.shape
     p, q = dev(c.p.a, rd), dev(c.q.a, rd)
-    pro_p, pro_q = make_pro(K, c.p, pmode, HW, rd), make_pro(K, c.q, qmode, HW, rd)
+    pro_p, pro_q = make_pro(K, c.p, pmode, HW, rd, c.act), make_pro(K, c.q, qmode, HW, rd, c.act)
     same(K.pwconv_wgrad(p, pro_p, q, pro_q), c.dw, f"{c.what} {rd}: dw")
     if accumulate:
         slot = dev(c.pre).clone()
@@ -199,13 +203,18 @@ def test_fused_expand_backward_is_exact(case):
 
 # ================================================================================================================ depthwise
 def _dw_all(K, c, rd, tag):
-    """Forward, data gradient and weight gradient of one shape, with and without the BN prologue / epilogue and the BN-backward map."""
+    """Forward, data gradient and weight gradient of one shape, with and without the BN prologue / epilogue and the BN-backward map.
+    c.act is the activation of the prologue / epilogue (E.dw(case, act)); the variants without a BN state take none."""
     N, H, W, C, k, s, pt, pl = c.shape
+    act = c.act
     x, xt, w, st = dev(c.x, rd), dev(c.xt, rd), dev(c.w), dev(c.st)
     dz, dyt, yraw, coef = dev(c.dz, rd), dev(c.dyt, rd), dev(c.yraw, rd), dev(c.coef)
-    y, parts, n = K.dwconv_fwd(x, st, ACT_NONE, w, k, s, pt, pl, c.Ho, c.Wo, stats=True)
+    y, parts, n = K.dwconv_fwd(x, st, act, w, k, s, pt, pl, c.Ho, c.Wo, stats=True)
     same(y, c.y, f"{tag}: forward with the BN prologue")
     same(part_sums(parts, n, C), c.y_sums, f"{tag}: forward statistics")
+    if act != ACT_NONE:
+        y1, _, _ = K.dwconv_fwd(x, st, act, w, k, s, pt, pl, c.Ho, c.Wo, stats=False)
+        same(y1, c.y, f"{tag}: forward with the BN prologue, without statistics")
     y2, parts, n = K.dwconv_fwd(xt, None, ACT_NONE, w, k, s, pt, pl, c.Ho, c.Wo, stats=True)
     same(y2, c.y, f"{tag}: forward")
     same(part_sums(parts, n, C), c.y_sums, f"{tag}: forward statistics, no prologue")
@@ -214,14 +223,14 @@ def _dw_all(K, c, rd, tag):
     for (d, yr, cf), (xin, sti) in [((dz, yraw, coef), (x, st)), ((dyt, None, None), (x, st)), ((dz, yraw, coef), (None, None)),
                                     ((dyt, None, None), (None, None))]:
         v = f"{'map' if cf is not None else 'plain'}, {'epilogue' if xin is not None else 'no epilogue'}"
-        dzin, parts, n = K.dwconv_bwd_data(d, yr, cf, w, xin, sti, ACT_NONE, (N, H, W, C), k, s, pt, pl)
-        same(dzin, c.dzin, f"{tag}: data gradient ({v})")
+        dzin, parts, n = K.dwconv_bwd_data(d, yr, cf, w, xin, sti, act if sti is not None else ACT_NONE, (N, H, W, C), k, s, pt, pl)
+        same(dzin, c.dzin if xin is not None else c.da, f"{tag}: data gradient ({v})")
         if xin is not None:
             same(part_sums(parts, n, C), c.dzin_sums, f"{tag}: data-gradient sums (dzin, dzin * xhat) ({v})")
     for (d, yr, cf), (xin, sti) in [((dz, yraw, coef), (x, st)), ((dyt, None, None), (xt, None)), ((dz, yraw, coef), (xt, None)),
                                     ((dyt, None, None), (x, st))]:
         v = f"{'map' if cf is not None else 'plain'}, {'prologue' if sti is not None else 'no prologue'}"
-        same(K.dwconv_bwd_weight(d, yr, cf, xin, sti, ACT_NONE, k, s, pt, pl), c.dw, f"{tag}: weight gradient ({v})")
+        same(K.dwconv_bwd_weight(d, yr, cf, xin, sti, act if sti is not None else ACT_NONE, k, s, pt, pl), c.dw, f"{tag}: weight gradient ({v})")
 
 
 @pytest.mark.parametrize("rd", DT)

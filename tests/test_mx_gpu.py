@@ -119,6 +119,28 @@ def test_activation_quantisation_behind_a_gelu_prologue():
     assert float((got != ref).float().mean()) < 2e-3            # and only where the two GELUs round differently
 
 
+@pytest.mark.parametrize("dtype", [BF, torch.float32])
+@pytest.mark.parametrize("act", ["silu", "gelu"])
+def test_activation_quantisation_behind_a_saturated_prologue_is_exact(act, dtype):
+    """The SiLU / GELU prologue at saturated pre-activations (tests/_exact.py, act64; the saturation itself is measured by
+    tests/test_exact_act_gpu.py): the values to quantise are exactly max(z, 0) in {0, 32, 64}, so unlike the Gaussian test above
+    the scale bytes and the element bytes have to be the oracle's - up to the sign bit of a zero, because the kernels' formulas
+    return -0 below the threshold (0x80 where the oracle's max(z, 0) has 0x00)."""
+    from tests import _exact as E
+
+    K = _K()
+    code = {"silu": E.ACT_SILU, "gelu": E.ACT_GELU}[act]
+    c = E.mx_rows(code)
+    M, Kd = E.MX_ROWS_CASE
+    q, s = K.mx_quant_rows(c.a.to(dtype).cuda().view(M, 1, 1, Kd), K.pro_bn_act(c.st.cuda(), code))
+    torch.cuda.synchronize()
+    qr, sr = R.mx_quant(c.want.float())
+    q = q.cpu()
+    assert torch.equal(s.cpu(), sr), "scale bytes"
+    assert torch.equal(torch.where((q & 0x7F) == 0, torch.zeros_like(q), q), qr), int((q != qr).sum())
+    assert torch.equal(R.mx_dequant(q, s.cpu()).double(), c.want)
+
+
 @pytest.mark.parametrize("M,K_,N", [(64, 128, 128), (100, 256, 36), (53 * 7, 1024, 256), (4096, 512, 1536)])
 def test_scaled_mfma_gemm_exact_on_integer_data(M, K_, N):
     """Small integers and power-of-two block scales are exact in e4m3/e8m0 and their products sum exactly in f32: any
