@@ -250,12 +250,6 @@ def load() -> ctypes.CDLL:
             raise RuntimeError(f"libdfd_hip.so does not export {name}") from exc
         fn.restype = restype
         fn.argtypes = argtypes
-    # DFD_TUNE="key=value,key=value": planner knobs of include/dfd_hip.h (dfd_tune) from the command line — A/B runs of
-    # bench.py / the layer scripts without a rebuild.  Applied once, before anything launches.
-    for item in filter(None, _os.environ.get("DFD_TUNE", "").split(",")):
-        key, _, value = item.partition("=")
-        if lib.dfd_tune(int(key), int(value)) != DFD_OK:
-            raise RuntimeError(f"DFD_TUNE: unknown key in {item!r}")
     _lib = lib
     return lib
 

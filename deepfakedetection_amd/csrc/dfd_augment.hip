@@ -283,8 +283,7 @@ extern "C" int dfd_augment_u8(const unsigned char* src, const dfd_augment_job* j
     if (!src || !jobs_dev || !dst || N < 1 || H < 1 || W < 1 || src == dst) return DFD_EINVAL;
     const long bytes = (long)H * W * 3;
     if (bytes > AUG_MAX_BYTES || H >= 32768 || W >= 32768) return DFD_EUNSUPPORTED;        // the picture must fit one CU's LDS
-    struct AugTag;
-    dfd_allow_lds_once<AugTag>(k_augment_u8<false>, AUG_MAX_BYTES);
+    dfd_allow_lds_once<k_augment_u8<false>>(AUG_MAX_BYTES);
     hipLaunchKernelGGL(k_augment_u8<false>, dim3(N), dim3(AUG_THREADS), (size_t)((bytes + 15) / 16 * 16), (hipStream_t)stream, src, jobs_dev, dst, H, W);
     return DFD_CHECK_LAUNCH();
 }
@@ -307,8 +306,7 @@ extern "C" int dfd_augment_policy_u8(const unsigned char* src, const dfd_augment
             if (o.op >= DFD_AUG_SHEAR_X && o.op <= DFD_AUG_ROTATE && (o.ip < 0 || o.ip > 4 || (o.ip >= 3 && H != W))) return DFD_EINVAL;
         }
     }
-    struct AugPolicyTag;
-    dfd_allow_lds_once<AugPolicyTag>(k_augment_u8<true>, AUG_MAX_BYTES);
+    dfd_allow_lds_once<k_augment_u8<true>>(AUG_MAX_BYTES);
     hipLaunchKernelGGL(k_augment_u8<true>, dim3(N), dim3(AUG_THREADS), (size_t)((bytes + 15) / 16 * 16), (hipStream_t)stream, src, jobs_dev, dst, H, W);
     return DFD_CHECK_LAUNCH();
 }

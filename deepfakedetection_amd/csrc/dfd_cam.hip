@@ -28,9 +28,6 @@
 #define CAM_RENDER_THREADS 1024
 #define CAM_MAX_C 16384              // step-1 weights live in LDS: 64 KiB
 
-struct CamMapF32Tag {};
-struct CamMapBf16Tag {};
-
 template <typename T> __device__ __forceinline__ float cam_ld(const T* p, long i);
 template <> __device__ __forceinline__ float cam_ld<float>(const float* p, long i) { return p[i]; }
 template <> __device__ __forceinline__ float cam_ld<bf16>(const bf16* p, long i) { return bf2f(p[i].x); }
@@ -173,11 +170,11 @@ extern "C" int dfd_gradcam_map(const void* act, const void* grad, int dtype, int
     const size_t lds = (size_t)C * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
     if (dtype == DFD_F32) {
-        dfd_allow_lds_once<CamMapF32Tag>(k_gradcam_map<float>, (int)(CAM_MAX_C * sizeof(float)));
+        dfd_allow_lds_once<k_gradcam_map<float>>((int)(CAM_MAX_C * sizeof(float)));
         hipLaunchKernelGGL(k_gradcam_map<float>, dim3(N), dim3(CAM_MAP_THREADS), lds, s, (const float*)act, (const float*)grad,
                            HW, C, cam_out);
     } else {
-        dfd_allow_lds_once<CamMapBf16Tag>(k_gradcam_map<bf16>, (int)(CAM_MAX_C * sizeof(float)));
+        dfd_allow_lds_once<k_gradcam_map<bf16>>((int)(CAM_MAX_C * sizeof(float)));
         hipLaunchKernelGGL(k_gradcam_map<bf16>, dim3(N), dim3(CAM_MAP_THREADS), lds, s, (const bf16*)act, (const bf16*)grad,
                            HW, C, cam_out);
     }

@@ -16,12 +16,13 @@
 
 // Host-side kernel-attribute caches ("kernel-attribute caches behind std::call_once"): the forward runs on the main
 // thread and the backward on autograd's thread, and the first launch of an instantiation may happen inside a stream capture.
-// `Tag` names the call site, so every (site, kernel instantiation) pair owns one flag.
-template <typename Tag, typename KernelT>
-static inline void dfd_allow_lds_once(KernelT kern, int bytes) {
+// dfd_allow_lds_once is keyed by the kernel itself (its address is the template argument), so every kernel instantiation owns one flag.
+template <auto Kern>
+static inline void dfd_allow_lds_once(int bytes) {
     static std::once_flag once;
-    std::call_once(once, [&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); });
+    std::call_once(once, [&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); });
 }
+// dfd_kernel_regs_once is keyed by (`Tag` = the call site, the kernel's function-pointer TYPE): instantiations with one signature share a flag.
 template <typename Tag, typename KernelT>
 static inline int dfd_kernel_regs_once(KernelT kern, int fallback) {
     static std::once_flag once;
@@ -172,14 +173,12 @@ __device__ __forceinline__ void gelu_parts2(dfd_f2 z, dfd_f2& cdf, dfd_f2& ez) {
 }
 template <int ACT> __device__ __forceinline__ dfd_f2 act_fwd2(dfd_f2 z) {
     if constexpr (ACT == DFD_ACT_GELU) { dfd_f2 cdf, ez; gelu_parts2(z, cdf, ez); return z * cdf; }
-#ifndef DFD_SILU_SCALAR
     else if constexpr (ACT == DFD_ACT_SILU) {
         // z * rcp(1 + exp(-z)) with the multiply / add / multiply on pairs (v_pk_*_f32); operation for operation act_fwd<SILU>
         const dfd_f2 t = z * splat2(-1.44269504088896340736f);               // __expf(-z) = exp2(-z * log2 e)
         const dfd_f2 d = (dfd_f2){__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)} + splat2(1.0f);
         return z * (dfd_f2){__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
     }
-#endif
     else return (dfd_f2){act_fwd<ACT>(z.x), act_fwd<ACT>(z.y)};
 }
 template <int ACT> __device__ __forceinline__ dfd_f2 act_grad2(dfd_f2 z) {
@@ -188,7 +187,6 @@ template <int ACT> __device__ __forceinline__ dfd_f2 act_grad2(dfd_f2 z) {
         gelu_parts2(z, cdf, ez);
         return __builtin_elementwise_fma(z * splat2(0.39894228040143268f), ez, cdf);
     }
-#ifndef DFD_SILU_SCALAR
     else if constexpr (ACT == DFD_ACT_SILU) {
         // s * (1 + z * (1 - s)), s = rcp(1 + exp(-z)): act_grad<SILU> operation for operation, on pairs
         const dfd_f2 t = z * splat2(-1.44269504088896340736f);
@@ -196,7 +194,6 @@ template <int ACT> __device__ __forceinline__ dfd_f2 act_grad2(dfd_f2 z) {
         const dfd_f2 sg = (dfd_f2){__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
         return sg * (splat2(1.0f) + z * (splat2(1.0f) - sg));
     }
-#endif
     else return (dfd_f2){act_grad<ACT>(z.x), act_grad<ACT>(z.y)};
 }
 // act(scale * v + shift) / act'(..) over an array of N values, in pairs
@@ -284,10 +281,10 @@ int dfd_stem_wgrad_mfma(const float* x, const void* dz, const void* yraw, const 
         default: return DFD_EUNSUPPORTED;                                            \
     }
 
-// knobs (dfd_tune): A/B switches and sizes read by the host-side planners; set once at start-up, before any launch
-enum { DFD_TUNE_DW_MFMA = 0, DFD_TUNE_DW_LDS_KB = 1, DFD_TUNE_DW_GRID = 2, DFD_TUNE_DEBUG = 3, DFD_TUNE_PW_NTD = 4, DFD_TUNE_NTD_NS = 5, DFD_TUNE_NTD_MAXN = 6, DFD_TUNE_NTD_MINT = 7,
-       DFD_TUNE_DWQ_GRID_FWD = 8, DFD_TUNE_DWQ_GRID_BWD = 9, DFD_TUNE_DWQ_GRID_WGRAD = 10, DFD_TUNE_DWQ_GRID_MIN = 11, DFD_TUNE_TN_WGS = 12, DFD_TUNE_DWQ_WIDE = 13,
-       DFD_TUNE_COUNT = 16 };
+// knobs (dfd_tune): the tier switches and grid sizes by which the tests and per-layer scripts reach a kernel tier; read by the
+// host-side planners, set before any launch.  The key numbers are the ABI's (include/dfd_hip.h); every other key is DFD_EINVAL.
+enum { DFD_TUNE_DW_MFMA = 0, DFD_TUNE_PW_NTD = 4, DFD_TUNE_DWQ_GRID_FWD = 8, DFD_TUNE_DWQ_GRID_BWD = 9, DFD_TUNE_DWQ_GRID_WGRAD = 10, DFD_TUNE_DWQ_GRID_MIN = 11,
+       DFD_TUNE_COUNT = 12 };
 int dfd_tune_get(int key);
 
 // sums P partial rows of L floats; the buffer needs room for P + ceil(P/32) rows (two-stage reduction)

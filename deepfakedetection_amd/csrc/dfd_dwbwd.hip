@@ -12,9 +12,6 @@
 // staged-column map is a compile-time table once the parity of pad_left is a template
 // parameter (PLP).
 #include "dfd_dwq.h"
-#ifndef DFD_ABLATE
-#define DFD_ABLATE 0   // timing experiments (scripts/build_variant.sh): 1 = staging only, 2 = taps only
-#endif
 
 // WPC = workgroups per CU the instance is compiled for: 4, or 3 for the wide occupancy class of the 5x5 stride-1 layers (dwq_occupancy), where only
 // three are resident anyway: 168 instead of 128 registers per lane.  The 4-per-CU 5x5 instances with the epilogue spill 20-48 bytes per lane; the
@@ -84,15 +81,10 @@ k_dw_bwd_data_q(const T* __restrict__ dz, const T* __restrict__ yraw, const floa
         const int sy0 = (S == 1) ? ny : (ny >= 0 ? ny / 2 : -((-ny + 1) / 2));
         const int sx0 = (S == 1) ? nx : (nx >= 0 ? nx / 2 : -((-nx + 1) / 2));
         __syncthreads();
-#if DFD_ABLATE != 2
         stage_dy<T, COEF, (WPC == 3 ? 2 : 1) * StageDepth<K, S>::DY>(tile, dz, yraw, cf, cvbV, vl, (long)n * g.Ho * g.Wo * g.C, g.Ho, g.Wo, g.C, c0, cvalid, sy0, sx0,
                           g.IH, g.IW, g.iw_magic, g.cvb_log2);
-#endif
         __syncthreads();
         if (!cvalid) continue;
-#if DFD_ABLATE == 1
-        continue;
-#endif
 #pragma unroll 1
         for (int q = lane; q < g.NQ; q += PL) {
             const int qy = (int)(((unsigned)q * g.qw_magic) >> 20), qx = q - qy * g.QW;

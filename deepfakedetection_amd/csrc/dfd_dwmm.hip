@@ -26,11 +26,11 @@
 typedef float dwm_f4 __attribute__((ext_vector_type(4)));
 typedef __bf16 dwm_bf8 __attribute__((ext_vector_type(8)));
 
-static int g_tune[DFD_TUNE_COUNT] = {/*DW_MFMA*/ 1, /*DW_LDS_KB*/ 156, /*DW_GRID*/ 256, /*DEBUG*/ 0, /*PW_NTD*/ 1, /*NTD_NS*/ 0, /*NTD_MAXN*/ 0, /*NTD_MINT*/ 16,
-                                      /*DWQ_GRID_FWD*/ 1024, /*DWQ_GRID_BWD*/ 1024, /*DWQ_GRID_WGRAD*/ 1024, /*DWQ_GRID_MIN*/ 32, /*TN_WGS*/ 512, /*DWQ_WIDE*/ -1};
-int dfd_tune_get(int key) { return (key >= 0 && key < DFD_TUNE_COUNT) ? g_tune[key] : 0; }
+static int g_tune[DFD_TUNE_COUNT] = {/*DW_MFMA*/ 1, 0, 0, 0, /*PW_NTD*/ 1, 0, 0, 0, /*DWQ_GRID_FWD*/ 1024, /*DWQ_GRID_BWD*/ 1024, /*DWQ_GRID_WGRAD*/ 1024, /*DWQ_GRID_MIN*/ 32};
+static bool tune_key_ok(int key) { return key == DFD_TUNE_DW_MFMA || key == DFD_TUNE_PW_NTD || (key >= DFD_TUNE_DWQ_GRID_FWD && key <= DFD_TUNE_DWQ_GRID_MIN); }
+int dfd_tune_get(int key) { return tune_key_ok(key) ? g_tune[key] : 0; }
 extern "C" int dfd_tune(int key, int value) {
-    if (key < 0 || key >= DFD_TUNE_COUNT) return DFD_EINVAL;
+    if (!tune_key_ok(key)) return DFD_EINVAL;
     g_tune[key] = value;
     return DFD_OK;
 }
@@ -39,11 +39,13 @@ extern "C" int dfd_tune(int key, int value) {
 #define DWP_MAXV 6          // staged 16-byte vectors per thread and item
 #define DWP_MAXS 4          // stored 16-byte vectors per thread and item
 #define DWP_MAXR 8         // runs per wave and item
+#define DWP_LDS_KB 156      // LDS budget of one workgroup in KiB (one workgroup per CU)
+#define DWP_GRID 256        // workgroups a launch aims for, all channel chunks together: one per CU
 
 template <int K, int S, int ACT, bool PRO, bool STATS, bool WHOLE>
 __global__ void __launch_bounds__(DWP_THREADS, 2)
 k_dw_fwd_mp(const unsigned short* __restrict__ x, const float* __restrict__ bnstate, const float* __restrict__ w,
-            unsigned short* __restrict__ y, DwMGeom g, float* __restrict__ partials, int dbg) {
+            unsigned short* __restrict__ y, DwMGeom g, float* __restrict__ partials) {
     constexpr int KK = K * K, NPAIR = (KK + 1) / 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* image0 = smem;
@@ -181,7 +183,6 @@ k_dw_fwd_mp(const unsigned short* __restrict__ x, const float* __restrict__ bnst
                                            : x + (((long)n0 * g.H + iy0) * g.W + ix0) * g.C + c0;
         const long dummy = x - base;                           // out of the picture: a valid address (masked to zero in A)
         inb_mask = 0;
-        if (dbg & 8) return;
         // straight-line code: integer masks and selects, no per-element branches (the first version of this loop compiled to 35
         // branches and 140 scalar-register spills for six loads)
 #pragma unroll
@@ -201,7 +202,7 @@ k_dw_fwd_mp(const unsigned short* __restrict__ x, const float* __restrict__ bnst
         for (int u = 0; u < DWP_MAXV; ++u) {
             if (u >= nslots) break;
             uint4 q = raw[u];
-            if (PRO && !(dbg & 1)) {
+            if constexpr (PRO) {
                 f2 a[4];
                 unpack2(q, a);
 #pragma unroll
@@ -226,7 +227,6 @@ k_dw_fwd_mp(const unsigned short* __restrict__ x, const float* __restrict__ bnst
         }
     };
     auto T = [&](Org o, int par) {                             // taps of an item
-        if (dbg & 2) return;
         const int n0 = o.ib * g.NI, oy0 = o.ty * g.TH, ox0 = o.tx * g.TW;
         const unsigned char* img = image0 + par * g.in_bytes;
         unsigned char* ot = out0 + par * g.out_bytes + owave;
@@ -255,7 +255,6 @@ k_dw_fwd_mp(const unsigned short* __restrict__ x, const float* __restrict__ bnst
         }
     };
     auto St = [&](Org o, int par) {                            // output tile of an item -> global
-        if (dbg & 4) return;
         const int n0 = o.ib * g.NI, oy0 = o.ty * g.TH, ox0 = o.tx * g.TW;
         const unsigned char* ot = out0 + par * g.out_bytes;
         unsigned short* base = y + (((long)n0 * g.Ho + oy0) * g.Wo + ox0) * g.C + c0;
@@ -352,7 +351,7 @@ bool dfd_dwm_geom(const dfd_dwconv_shape* s, bool centre_is_input, bool pro, int
     if (centre_is_input) return false;                       // (the data gradient has its own planner)
     const int K = s->k, S = s->stride;
     g->N = s->N; g->H = s->H; g->W = s->W; g->C = s->C; g->Ho = s->Ho; g->Wo = s->Wo; g->pt = s->pad_top; g->pl = s->pad_left;
-    const long budget = (long)dfd_tune_get(DFD_TUNE_DW_LDS_KB) * 1024 - extra_lds;
+    const long budget = (long)DWP_LDS_KB * 1024 - extra_lds;
     const int CH = s->Ho, CW = s->Wo;
     const int gmax = s->C >= 64 ? 4 : s->C / 16;                       // groups of the widest chunk
     const int nv = gmax == 1 ? 2 : (gmax == 2 ? 4 : 8);                // 16-byte vectors per pixel
@@ -436,7 +435,7 @@ int dfd_dw_fwd_mm(const void* x, const float* in_bnstate, int in_act, const floa
     g.remap = (nchunks > 1 && g.tiles_y * g.tiles_x >= 2 && (s->C * 2) % 128 != 0) ? 1 : 0;
     const bool stats = partials != nullptr;
     const int cap = stats ? (pcap < DFD_MAX_PARTIALS ? pcap : DFD_MAX_PARTIALS) : DFD_MAX_PARTIALS;
-    int gy = dfd_tune_get(DFD_TUNE_DW_GRID) / nchunks;
+    int gy = DWP_GRID / nchunks;
     if (gy < 1) gy = 1;
     if (gy > cap) gy = cap;
     if (gy > g.nwork) gy = g.nwork;
@@ -446,17 +445,16 @@ int dfd_dw_fwd_mm(const void* x, const float* in_bnstate, int in_act, const floa
     dim3 grid(nchunks, gy);
 #define LAUNCH_MM(PRO, STATS)                                                                                                     \
     do {                                                                                                                          \
-        struct DwmTag;                                                                                                            \
         if (g.whole) {                                                                                                            \
-            auto kern = k_dw_fwd_mp<K, S, ACT, PRO, STATS, true>;                                                                \
-            dfd_allow_lds_once<DwmTag>(kern, 160 * 1024);                                                                         \
+            constexpr auto kern = k_dw_fwd_mp<K, S, ACT, PRO, STATS, true>;                                                      \
+            dfd_allow_lds_once<kern>(160 * 1024);                                                                                 \
             hipLaunchKernelGGL(kern, grid, dim3(DWP_THREADS), lds, st, (const unsigned short*)x, in_bnstate, w, (unsigned short*)y, \
-                               g, partials, dfd_tune_get(DFD_TUNE_DEBUG));                                                        \
+                               g, partials);                                                                                      \
         } else {                                                                                                                  \
-            auto kern = k_dw_fwd_mp<K, S, ACT, PRO, STATS, false>;                                                               \
-            dfd_allow_lds_once<DwmTag>(kern, 160 * 1024);                                                                         \
+            constexpr auto kern = k_dw_fwd_mp<K, S, ACT, PRO, STATS, false>;                                                     \
+            dfd_allow_lds_once<kern>(160 * 1024);                                                                                 \
             hipLaunchKernelGGL(kern, grid, dim3(DWP_THREADS), lds, st, (const unsigned short*)x, in_bnstate, w, (unsigned short*)y, \
-                               g, partials, dfd_tune_get(DFD_TUNE_DEBUG));                                                        \
+                               g, partials);                                                                                      \
         }                                                                                                                         \
     } while (0)
     DISPATCH_KS(s->k, s->stride, {

@@ -103,7 +103,7 @@ bool dfd_dwq_geom(const dfd_dwconv_shape* s, int vec, int max_cvb, bool centre_i
 // it wins on the 5x5 stride-1 layers (data gradient 7x7 C1152 82 -> 49 us, 28x28 C240 212 -> 174, 14x14 C480 / C672 86 -> 72 / 122 -> 111;
 // forward 28x28 153 -> 140, 7x7 51 -> 43; weight gradient 14x14 80 -> 71 / 104 -> 101) and on the 3x3 stride-2 data gradient (389 -> 379,
 // 63 -> 55), and loses on the other 3x3 and stride-2 launches (56x56 C144 forward 174 -> 189, weight gradient 232 -> 250; 14 -> 7 5x5
-// forward 52 -> 63), so the rule below names those classes.  dfd_tune key 13: -1 this rule, 0 never wide, 1 always wide (A/B runs).
+// forward 52 -> 63), so the rule names those classes.
 struct DwqOcc { long lds_budget; int grid; };
 DwqOcc dwq_occupancy(int op, const dfd_dwconv_shape* s);
 

@@ -17,9 +17,6 @@
 #include "dfd_common.h"
 #include "dfd_pw.h"
 
-#ifndef GD_ROWS128
-#define GD_ROWS128 1            // 128-row tiles where 256-row tiles would leave CUs idle (A/B switch)
-#endif
 #define GD_BN 256
 #define GD_BK 64
 #define GD_B_BYTES (GD_BN * 128)
@@ -183,8 +180,7 @@ template <int WM, int EACT>
 static int gemm_nt_dma_launch(const void* a, const void* w, void* out, int M, int K, int N, int m_tiles, int n_tiles, const GdEpi& ep,
                               hipStream_t st) {
     using G = GdGeom<WM>;
-    struct GdTag;
-    dfd_allow_lds_once<GdTag>(k_gemm_nt_dma<WM, EACT>, G::LDS);
+    dfd_allow_lds_once<k_gemm_nt_dma<WM, EACT>>(G::LDS);
     hipLaunchKernelGGL((k_gemm_nt_dma<WM, EACT>), dim3((unsigned)(m_tiles * n_tiles)), dim3(G::THREADS), G::LDS, st, (const unsigned short*)a,
                        (const unsigned short*)w, (unsigned short*)out, M, K, N, m_tiles, n_tiles, ep);
     return DFD_CHECK_LAUNCH();
@@ -194,7 +190,7 @@ static bool gemm_nt_dma_plan(int M, int K, int N, int* wm, int* m_tiles, int* n_
     *n_tiles = (N + GD_BN - 1) / GD_BN;
     const int mt256 = (M + 255) / 256, mt128 = (M + 127) / 128;
     if ((long)mt256 * *n_tiles >= 160) { *wm = 4; *m_tiles = mt256; return true; }
-    if (GD_ROWS128 && (long)mt128 * *n_tiles >= 160) { *wm = 2; *m_tiles = mt128; return true; }
+    if ((long)mt128 * *n_tiles >= 160) { *wm = 2; *m_tiles = mt128; return true; }   // 128-row tiles where 256-row tiles would leave CUs idle
     return false;                                        // fewer tiles than CUs: the smaller tiles of k_pw_nt fill the chip better
 }
 int dfd_gemm_nt_dma(const void* a, const void* w, void* out, int M, int K, int N, hipStream_t st) {

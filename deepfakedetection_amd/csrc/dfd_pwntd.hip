@@ -27,6 +27,9 @@
 
 #define ND_BM 64
 #define ND_RED_BYTES (DFD_THREADS * 16 * 4)
+#define ND_MAXN 192         // widest column tile (NT = 12); 96 / 128 measured slower or equal on every shape but one
+#define ND_MINT 16          // fewest 64-row tiles for which this kernel is used: 16 measured best at batch 32 / 64 (4.40 -> 4.25 ms,
+                            // 5.74 -> 5.64 ms per EfficientNet-B0 step), neutral at 256
 
 typedef __attribute__((address_space(3))) unsigned char nd_lds_u8;
 
@@ -56,7 +59,7 @@ template <int NT, int PRO, int ACT, bool RES, bool STATS>
 __global__ void __launch_bounds__(DFD_THREADS, 2)
 k_pw_ntd(const unsigned short* __restrict__ a, ProArgs pa, const unsigned short* __restrict__ w, unsigned short* __restrict__ out,
          const unsigned short* __restrict__ res, int M, int K, int Nout, int m_tiles, int n_tiles, int ns, int coff, int goff,
-         float* __restrict__ partials, int dbg) {
+         float* __restrict__ partials) {
     using G = NdGeom<NT, PRO>;
     constexpr int BN = G::BN, WPC = G::WPC, J = G::J, OROW = G::OROW;
     constexpr int NROW = PRO == DFD_PRO_AFFINE2 ? 3 : 2;
@@ -123,19 +126,15 @@ k_pw_ntd(const unsigned short* __restrict__ a, ProArgs pa, const unsigned short*
         const unsigned sb = lds0 + buf * G::STAGE + wave * 1024;
         const char* ab = reinterpret_cast<const char*>(a) + k * 2;
         const char* wb = reinterpret_cast<const char*>(w) + k * 2;
-        if (!(dbg & 8)) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) nd_dma16(ab + offA[j], sb + j * 4096);
-        }
         if constexpr (PRO == DFD_PRO_AFFINE2) {
             const char* a2b = reinterpret_cast<const char*>(a2) + k * 2;
 #pragma unroll
             for (int j = 0; j < 2; ++j) nd_dma16(a2b + offA[j], sb + 8192 + j * 4096);
         }
-        if (!(dbg & 4)) {
 #pragma unroll
         for (int j = 0; j < WPC; ++j) nd_dma16(wb + offW[j], sb + G::WOFF + j * 4096);
-        }
     };
 
     f32x4_t acc[NT];
@@ -198,23 +197,18 @@ k_pw_ntd(const unsigned short* __restrict__ a, ProArgs pa, const unsigned short*
 #pragma unroll
                     for (int x = 0; x < 8; ++x) gt[x] = 0.f;
                 }
-                if (!(dbg & 1)) fa = apply_pro_v<bf16, PRO, ACT, 8>(fa, fa2, c0, c1, c2, gt);
+                fa = apply_pro_v<bf16, PRO, ACT, 8>(fa, fa2, c0, c1, c2, gt);
             }
             if (kk >= K) fa = make_uint4(0, 0, 0, 0);
-            if (!(dbg & 2)) {
 #pragma unroll
             for (int i = 0; i < NT; ++i)
                 acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, fw[i]), __builtin_bit_cast(bf16x8_t, fa), acc[i], 0, 0, 0);
-            } else {
-                acc[0][0] += __uint_as_float(fa.x ^ fw[NT - 1].y);        // (timing only: keeps the reads alive)
-            }
         }
         if (++buf == ns) buf = 0;
     }
 
     // ---- epilogue (overlays the ring): accumulators -> this wave's patch [16][BN] -> 16-byte row-major stores
     __syncthreads();
-    if (dbg & 16) { if (acc[0][0] == 123.456f) out[0] = 1; return; }
     unsigned char* eb = smem + wave * 16 * OROW;
 #pragma unroll
     for (int i = 0; i < NT; ++i)
@@ -297,25 +291,22 @@ static int ntd_launch(const void* a, const ProArgs& pa, const void* w, void* out
     const int gtab = PRO == DFD_PRO_BN_ACT_GATE ? (imgs * K * 4 + 1023) / 1024 * 1024 + 256 : 0;
     const int tables = ctab + gtab;
     // stages: three with two workgroups per CU when that fits (80 KB each), else two, else one workgroup per CU with up to four
-    int ns = dfd_tune_get(DFD_TUNE_NTD_NS);
-    if (ns < 2 || ns > 4) {
-        const int half = 80 * 1024 - 512;
-        if (3 * G::STAGE + tables <= half) ns = 3;
-        else if (2 * G::STAGE + tables <= half) ns = 2;
-        else { ns = (160 * 1024 - 1024 - tables) / G::STAGE; if (ns > 4) ns = 4; }
-    }
+    int ns;
+    const int half = 80 * 1024 - 512;
+    if (3 * G::STAGE + tables <= half) ns = 3;
+    else if (2 * G::STAGE + tables <= half) ns = 2;
+    else { ns = (160 * 1024 - 1024 - tables) / G::STAGE; if (ns > 4) ns = 4; }
     if (ns > nk + 1) ns = nk + 1;
     if (ns < 2) ns = 2;
     int ring = ns * G::STAGE;
     if (ring < G::EPI) ring = G::EPI;
     const int lds = ring + tables;
     if (lds > 160 * 1024) return DFD_EUNSUPPORTED;
-    auto kern = k_pw_ntd<NT, PRO, ACT, RES, STATS>;
-    struct NdTag;
-    dfd_allow_lds_once<NdTag>(kern, 160 * 1024);
+    constexpr auto kern = k_pw_ntd<NT, PRO, ACT, RES, STATS>;
+    dfd_allow_lds_once<kern>(160 * 1024);
     hipLaunchKernelGGL(kern, dim3((unsigned)(m_tiles * n_tiles)), dim3(DFD_THREADS), lds, st, (const unsigned short*)a, pa,
                        (const unsigned short*)w, (unsigned short*)out, (const unsigned short*)residual, M, K, Nout, m_tiles, n_tiles, ns,
-                       ring, ring + ctab, partials, dfd_tune_get(DFD_TUNE_DEBUG) >> 8);
+                       ring, ring + ctab, partials);
     return DFD_CHECK_LAUNCH();
 }
 
@@ -342,19 +333,22 @@ static int ntd_nt(const void* a, const dfd_prologue* pro, const void* w, void* o
 
 // column-tile width (in 16-column fragments) for an output of Nout channels: the narrowest instance that covers it in the fewest tiles
 static int ntd_pick(int Nout) {
-    const int wmax = dfd_tune_get(DFD_TUNE_NTD_MAXN) > 0 ? dfd_tune_get(DFD_TUNE_NTD_MAXN) : 192;   // (A/B: narrower column tiles)
-    const int tiles = (Nout + wmax - 1) / wmax;
+    const int tiles = (Nout + ND_MAXN - 1) / ND_MAXN;
     const int per = ((Nout + tiles - 1) / tiles + 15) / 16;
     return per <= 4 ? 4 : per <= 6 ? 6 : per <= 8 ? 8 : 12;
 }
 
+// does the ring kernel serve a layer of M rows and K input channels?  `cap`: partial rows the caller has room for (one per row tile)
+static bool ntd_serves(int M, int K, int cap) {
+    const int m_tiles = (M + ND_BM - 1) / ND_BM;
+    // rows: enough tiles to give most CUs one, few enough for one partial row per tile; K: at least one full step
+    return (dfd_tune_get(DFD_TUNE_PW_NTD) & 1) && m_tiles >= ND_MINT && m_tiles <= cap && K >= 64 && (long)M * K < (1l << 30);
+}
+
 int dfd_pw_ntd(int dtype, const void* a, const dfd_prologue* pro, const void* w, void* out, const void* residual, int M, int K,
                int Nout, float* partials, int pcap, int* nparts, hipStream_t st) {
-    if (!(dfd_tune_get(DFD_TUNE_PW_NTD) & 1) || dtype != DFD_BF16) return DFD_EUNSUPPORTED;
-    const int m_tiles = (M + ND_BM - 1) / ND_BM;
     const int cap = partials ? (pcap < DFD_MAX_PARTIALS ? pcap : DFD_MAX_PARTIALS) : DFD_MAX_PARTIALS;
-    // rows: enough tiles to give most CUs one, few enough for one partial row per tile; K: at least one full step
-    if (m_tiles < dfd_tune_get(DFD_TUNE_NTD_MINT) || m_tiles > cap || K < 64 || (long)M * K >= (1l << 30)) return DFD_EUNSUPPORTED;
+    if (dtype != DFD_BF16 || !ntd_serves(M, K, cap)) return DFD_EUNSUPPORTED;
     switch (ntd_pick(Nout)) {
         case 4: return ntd_nt<4>(a, pro, w, out, residual, M, K, Nout, partials, nparts, st);
         case 6: return ntd_nt<6>(a, pro, w, out, residual, M, K, Nout, partials, nparts, st);
@@ -364,7 +358,5 @@ int dfd_pw_ntd(int dtype, const void* a, const dfd_prologue* pro, const void* w,
 }
 // which column-tile width serves this shape (0: not this kernel) — tests assert the path they name
 extern "C" int dfd_pw_ntd_plan(int M, int K, int Nout) {
-    const int m_tiles = (M + ND_BM - 1) / ND_BM;
-    if (!(dfd_tune_get(DFD_TUNE_PW_NTD) & 1) || m_tiles < dfd_tune_get(DFD_TUNE_NTD_MINT) || m_tiles > DFD_MAX_PARTIALS || K < 64 || (long)M * K >= (1l << 30)) return 0;
-    return 16 * ntd_pick(Nout);
+    return ntd_serves(M, K, DFD_MAX_PARTIALS) ? 16 * ntd_pick(Nout) : 0;
 }

@@ -409,9 +409,8 @@ static int tnw_dg_launch(const void* x, int Cin, const void* dz, const dfd_prolo
     woff = (woff + 15) / 16 * 16;
     const int lds = woff + NA * 16 * wstride;
     if (lds > 80 * 1024) return DFD_EUNSUPPORTED;               // two workgroups per CU
-    struct TnwDgTag;
-    dfd_allow_lds_once<TnwDgTag>(k_pw_tnw<ROWS, NA, NBT, DFD_PRO_NONE, DFD_PRO_AFFINE2, DFD_ACT_NONE, 2>, 80 * 1024);
-    dfd_allow_lds_once<TnwDgTag>(k_pw_tnw<ROWS, NA, NBT, DFD_PRO_NONE, DFD_PRO_AFFINE2, DFD_ACT_NONE, 1>, 80 * 1024);
+    dfd_allow_lds_once<k_pw_tnw<ROWS, NA, NBT, DFD_PRO_NONE, DFD_PRO_AFFINE2, DFD_ACT_NONE, 2>>(80 * 1024);
+    dfd_allow_lds_once<k_pw_tnw<ROWS, NA, NBT, DFD_PRO_NONE, DFD_PRO_AFFINE2, DFD_ACT_NONE, 1>>(80 * 1024);
     if (residual)
         hipLaunchKernelGGL((k_pw_tnw<ROWS, NA, NBT, DFD_PRO_NONE, DFD_PRO_AFFINE2, DFD_ACT_NONE, 2>), dim3(nblocks), dim3(DFD_THREADS), lds, st,
                            (const bf16*)x, pa, Cin, (const bf16*)dz, pb, Cm, M, rpb, 1, ws, (const bf16*)w_kn, (const bf16*)residual, (bf16*)dx,

@@ -87,39 +87,24 @@ typedef void* dfd_stream;          /* a hipStream_t */
  * 139 = dfd_augment_policy_u8 (RandAugment / TrivialAugmentWide behind rotation and ColorJitter, in dfd_augment_u8's launch shape);
  * 140 = dfd_grad_sumsq, dfd_grad_clip_finish, dfd_adamw_step_clip (gradient clipping by global norm or by value in the AdamW step);
  * 141 = the one-kernel depthwise backward export of 120 (3x3 stride 1, data and weight gradient together) removed;
- * 142 = dfd_jpeg_u8, dfd_jpeg_ws (JPEG-compression augmentation: the pixels of a baseline JPEG round trip, byte-exact with Pillow). */
+ * 142 = dfd_jpeg_u8, dfd_jpeg_ws (JPEG-compression augmentation: the pixels of a baseline JPEG round trip, byte-exact with Pillow);
+ * 143 = dfd_tune keeps keys 0, 4 and 8-11; keys 1-3, 5-7, 12 and 13 (A/B-only sizes and the timing-only ablation mask) are DFD_EINVAL. */
 int dfd_version(void);
 
-/* Planner knobs (A/B switches and sizes the host-side kernel selection reads).  Process-wide plain ints: set them once at
- * start-up, before the first launch — they are not synchronised with concurrent callers.  Unknown key: DFD_EINVAL.
+/* Planner knobs: the tier switches and grid sizes by which tests and per-layer scripts reach a kernel tier.  Process-wide plain ints:
+ * set them before the first launch — they are not synchronised with concurrent callers.  Any other key: DFD_EINVAL.  (Keys 1-3, 5-7,
+ * 12 and 13 of ABI 130-142 were A/B knobs; each was swept once and its winner is now a named constant at its point of use.)
  *   0 DFD_TUNE_DW_MFMA    bit 0: the depthwise forward runs on the matrix cores (bf16, C % 16 == 0) for the shapes where that form
  *                         measured faster (5x5 stride 1 on maps of at most 64 pixels); bit 3: for every shape it can serve
  *                         (tests, A/B runs); 0 = the vector-unit kernels everywhere                          (default 1)
- *   1 DFD_TUNE_DW_LDS_KB  LDS budget of one matrix-core depthwise workgroup in KiB                           (default 156)
- *   2 DFD_TUNE_DW_GRID    workgroups a matrix-core depthwise launch aims for                                 (default 256)
- *   3 DFD_TUNE_DEBUG      timing-only ablations of the matrix-core depthwise kernels (results are WRONG when non-zero): bit 0
- *                         no activation arithmetic, 1 no tap loop, 2 no stores, 3 no loads; bits 8-12: the same for the LDS-DMA ring
- *                         kernel of dfd_pwconv_fwd (8 no prologue arithmetic, 9 no MFMAs, 10 no weight DMA, 11 no activation DMA,
- *                         12 no epilogue; scripts/pw_mid_ablate.py)                                         (default 0)
  *   4 DFD_TUNE_PW_NTD     bit 0: dfd_pwconv_fwd runs bf16 layers of 1 k .. 64 k rows on the LDS-DMA ring kernel (dfd_pw_ntd_plan
  *                         tells which); 0 = the register-staged tile kernel everywhere (A/B runs)             (default 1)
- *   5 DFD_TUNE_NTD_NS     stages of that kernel's LDS ring, 2..4; 0 = chosen from the LDS budget              (default 0)
- *   6 DFD_TUNE_NTD_MAXN   widest column tile of that kernel (A/B: 96 / 128); 0 = 192                          (default 0)
- *   7 DFD_TUNE_NTD_MINT   fewest 64-row tiles for which it is used: 16 measured best at batch 32 / 64 (4.40 -> 4.25 ms,
- *                         5.74 -> 5.64 ms per EfficientNet-B0 step), neutral at 256                          (default 16)
  *   8 / 9 / 10            workgroups a vector-unit depthwise launch aims for (all channel chunks together): forward / data gradient /
  *                         weight gradient.  1024 = what is co-resident at four per CU: every workgroup starts at once and walks
  *                         its work items, nobody queues behind a first round (measured against 768 / 1536 / 2048 / 3072 per
  *                         EfficientNet-B0 layer, scripts/dw_ab.py; 2048 was the value of rounds 2-4: B0 12.94 -> 12.75,
  *                         EfficientFormerV2-S1 17.00 -> 16.65 ms per step)                                    (default 1024)
- *   11                    fewest work slots per channel chunk of those launches                             (default 32)
- *   12 DFD_TUNE_TN_WGS    workgroups a tiled weight-gradient launch (k_pw_tn: output tiles x row splits) aims for.  512 = what is
- *                         co-resident at two per CU; measured 256 / 384 / 512 / 768 / 1024 on one box: EfficientNet-B0 12.88 / 12.80 /
- *                         12.62 / 13.03 / 12.96 ms, EfficientFormerV2-S1 16.71 / 16.57 / 16.44 / 16.94 / 17.11, FasterViT-0 22.04 /
- *                         21.46 / 19.59 / 20.27 / 20.20                                                       (default 512)
- *   13 DFD_TUNE_DWQ_WIDE  occupancy class of the vector-unit depthwise launches: -1 = by shape (5x5 stride-1 layers and the 3x3
- *                         stride-2 data gradient run THREE workgroups per CU with 48 KB of tile + tables and 3/4 of the grid
- *                         target, everything else four per CU with 39 KB), 0 = never wide, 1 = always wide (A/B)   (default -1) */
+ *   11                    fewest work slots per channel chunk of those launches                             (default 32) */
 int dfd_tune(int key, int value);
 
 /* Batched final summation of weight gradients.  The weight-gradient entry points whose result goes straight to the

@@ -1,7 +1,7 @@
 #!/bin/bash
-# SQ counters of ONE kernel of one block under a DFD_TUNE setting: bash scripts/pmc_sq.sh <op> <block> <tag> [DFD_TUNE]
+# SQ counters of ONE kernel of one block: bash scripts/pmc_sq.sh <op> <block> <tag>
 set -e
-OP=$1; BLK=$2; TAG=${3:-pmc}; export DFD_TUNE=${4:-}
+OP=$1; BLK=$2; TAG=${3:-pmc}
 OUT=$PWD/gpurun_out/pmc_$TAG
 mkdir -p "$OUT"
 REPO=$(cd "$(dirname "$0")/.." && pwd)

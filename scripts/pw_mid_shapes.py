@@ -1,7 +1,7 @@
 """A/B of the 1x1 NT kernels on the MID-SIZE layers of EfficientNet-B0 at batch 256 (14 x 14 and 7 x 7 maps): the register-staged
-tile kernel k_pw_nt (dfd_tune key 4 = 0) against the LDS-DMA ring kernel k_pw_ntd (key 4 = 1, ring depth by key 5).
+tile kernel k_pw_nt (dfd_tune key 4 = 0) against the LDS-DMA ring kernel k_pw_ntd (key 4 = 1).
 
-    python scripts/pw_mid_shapes.py [ns ...]        (default ring depths: 0 = automatic)
+    python scripts/pw_mid_shapes.py
 
 Per layer and variant (expand forward = plain operand + statistics, project forward = BN + SiLU + gate prologue + statistics,
 project data gradient = plain, expand data gradient = BN-backward map of two tensors + residual): microseconds, and the rate
@@ -43,14 +43,13 @@ def timeit(fn, reps=20):
 
 
 def main() -> None:
-    depths = [int(v) for v in sys.argv[1:]] or [0]
     # (rows, HW, Cin, Cmid, Cout) of blocks 5..15 + head (distinct shapes)
     shapes = [(50176, 196, 80, 480, 80), (50176, 196, 80, 480, 112), (50176, 196, 112, 672, 112), (12544, 49, 112, 672, 192),
               (12544, 49, 192, 1152, 192), (12544, 49, 192, 1152, 320), (12544, 49, 320, 1280, 0)]
     g = torch.Generator(device="cuda").manual_seed(1)
     rnd = lambda *s: torch.randn(*s, device="cuda", generator=g)
-    print(f"{'variant':<12} {'shape':<26} {'k_pw_nt us':>10} " + " ".join(f"{'ntd ns=' + str(d):>12}" for d in depths) + f" {'GB/s best':>10}  same bits")
-    tot = {"nt": 0.0, **{d: 0.0 for d in depths}}
+    print(f"{'variant':<12} {'shape':<26} {'k_pw_nt us':>10} {'k_pw_ntd us':>12} {'GB/s best':>10}  same bits")
+    tot = {"nt": 0.0, "ntd": 0.0}
     for (M, HW, Cin, Cm, Co) in shapes:
         N = M // HW
         variants = []
@@ -76,24 +75,17 @@ def main() -> None:
             ref = fn()
             t_nt = timeit(fn)
             tot["nt"] += t_nt
-            cells, best, same = [], t_nt, True
-            for d in depths:
-                L.dfd_tune(4, 1)
-                L.dfd_tune(5, d)
-                if not L.dfd_pw_ntd_plan(a.shape[0], a.shape[1], w.shape[0]):
-                    cells.append(f"{'-':>12}")
-                    tot[d] += t_nt
-                    continue
+            L.dfd_tune(4, 1)
+            if L.dfd_pw_ntd_plan(a.shape[0], a.shape[1], w.shape[0]):
                 got = fn()
-                same = same and torch.equal(got[0], ref[0])
-                td = timeit(fn)
-                tot[d] += td
-                best = min(best, td)
-                cells.append(f"{td:12.1f}")
-            print(f"{name:<12} {f'{M}x{a.shape[1]}->{w.shape[0]}':<26} {t_nt:10.1f} " + " ".join(cells) + f" {nbytes / best / 1e3:10.0f}  {same}")
-    L.dfd_tune(4, 1)
-    L.dfd_tune(5, 0)
-    print("totals (us): k_pw_nt", round(tot["nt"], 1), {d: round(tot[d], 1) for d in depths})
+                same = torch.equal(got[0], ref[0])
+                t_ntd = timeit(fn)
+                cell = f"{t_ntd:12.1f}"
+            else:                                             # not the ring kernel's shape: both arms ran k_pw_nt
+                same, t_ntd, cell = True, t_nt, f"{'-':>12}"
+            tot["ntd"] += t_ntd
+            print(f"{name:<12} {f'{M}x{a.shape[1]}->{w.shape[0]}':<26} {t_nt:10.1f} {cell} {nbytes / min(t_nt, t_ntd) / 1e3:10.0f}  {same}")
+    print("totals (us): k_pw_nt", round(tot["nt"], 1), " k_pw_ntd", round(tot["ntd"], 1))
 
 
 if __name__ == "__main__":

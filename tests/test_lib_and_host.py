@@ -46,20 +46,27 @@ def test_bad_arguments_are_rejected_without_a_gpu(lib):
 
 def test_kernel_planners_answer_without_a_gpu(lib):
     """Host-side kernel selection (no launch): which column-tile width the LDS-DMA ring kernel picks for EfficientNet-B0's mid-size
-    1x1 layers at batch 256, what it leaves to the other kernels, and that the planner knobs switch it."""
+    1x1 layers at batch 256, what it leaves to the other kernels, that the tier switch (dfd_tune key 4) switches it, and that
+    dfd_tune knows the six keys that reach a tier and no other."""
     plan = lib.dfd_pw_ntd_plan
-    assert plan(12544, 1152, 192) == 192 and plan(50176, 480, 80) == 96 and plan(50176, 672, 112) == 128
-    assert plan(12544, 192, 1152) == 192 and plan(12544, 1152, 320) == 192 and plan(6272, 240, 40) == 64
-    assert plan(960, 480, 80) == 0            # fewer than 16 row tiles
-    assert plan(200704, 240, 40) == 0         # more row tiles than partial rows
-    assert plan(50176, 40, 240) == 0          # K below one 64-wide step
+
+    def defaults_hold():
+        assert plan(12544, 1152, 192) == 192 and plan(50176, 480, 80) == 96 and plan(50176, 672, 112) == 128
+        assert plan(12544, 192, 1152) == 192 and plan(12544, 1152, 320) == 192 and plan(6272, 240, 40) == 64
+        assert plan(960, 480, 80) == 0            # fewer than 16 row tiles
+        assert plan(200704, 240, 40) == 0         # more row tiles than partial rows
+        assert plan(50176, 40, 240) == 0          # K below one 64-wide step
+
+    defaults_hold()
     try:
         assert lib.dfd_tune(4, 0) == 0 and plan(12544, 1152, 192) == 0
-        assert lib.dfd_tune(4, 1) == 0 and lib.dfd_tune(6, 96) == 0 and plan(12544, 1152, 192) == 96
     finally:
         lib.dfd_tune(4, 1)
-        lib.dfd_tune(6, 0)
-    assert lib.dfd_tune(99, 0) != 0
+    for key, value in ((1, 48), (2, 512), (3, 1), (5, 2), (6, 96), (7, 64), (12, 256), (13, 0), (99, 0)):      # the retired A/B knobs, and no knob
+        assert lib.dfd_tune(key, value) != 0, key
+    for key, default in ((0, 1), (4, 1), (8, 1024), (9, 1024), (10, 1024), (11, 32)):
+        assert lib.dfd_tune(key, default) == 0, key
+    defaults_hold()
     assert lib.dfd_sum_passengers_discard() == 0 and lib.dfd_sum_batch_end_deferred() != 0      # no open batch: DFD_EINVAL
 
 
