@@ -24,6 +24,12 @@ and have run check_exact; tests/test_exact_cpu.py evaluates the f32 oracle on th
 Most builders take an activation code.  With SiLU / GELU the pre-activations are drawn from a SATURATING set, where the kernels'
 formulas return exactly 0 or exactly z (act64 below), so the same argument holds for the activation-bearing instantiations:
 tests/test_exact_act_cpu.py and tests/test_exact_act_gpu.py.
+
+FasterViT's batched coordinate MLPs (csrc/dfd_coord.hip) are held to tolerance 0 the same way: coord_mlp (integer coordinates with
+zeros, so that pre-activations of exactly 0 occur) and coord_cpb (the chain MLP -> table -> 16 sigmoid(table[idx]) -> dtable -> MLP
+backward at a table that paired hidden units make exactly 0); tests/test_coord_gpu.py runs the kernels on them, tests/test_exact_cpu.py
+plain f32 torch and the oracle's PosEmb1D.  coord_shipped holds the shipped geometries on real numbers (a tolerance test) with the
+condition under which its ReLU masks are determined (relu_margin).
 """
 
 from __future__ import annotations
@@ -989,6 +995,219 @@ def vit_small():
                          ("scatter", scat, (F32,)), ("relpos dtable", dtable, (F32,)), ("subsample bwd", dx1, DTYPES)])
     return NS(x=f32(x), pooled=pooled, gp=f32(gp), dpool=dpool, gt=f32(gt), rowtable=gt.sum(0).view(49, 64), idx=idx, dfull=f32(dfull),
               scat=scat, n=n, ridx=ridx, dbias=f32(dbias), nl=nl, ng=ng, T=T, H=H, dtable=dtable, gs=f32(gs), dx0=f32(dx0), dx1=dx1)
+
+
+# ------------------------------------------------------------------- batched coordinate MLPs of FasterViT (csrc/dfd_coord.hip)
+# (T, D, Hd) of table = relu(coords w0^T + b0) w2^T, the smallest shapes at which each branch of the kernels turns: one row / one
+# column / one hidden quad; the shipped tables (16 and 49 rows x dim, 49 and 169 rows x heads); T = 64 | 65 (16 or 44 rows per row
+# group in the backward), T = 88 | 89 (dtable staged 32 or 16 columns per pass) with D no multiple of either; T = 176 (the largest
+# table) with Hd = 36 (one hidden chunk, 28 idle lanes); Hd = 1024 (the widest); D = 65 (one column behind the forward's 64-column
+# chunk) at T = 25 (one row behind its 8-row chunk)
+COORD_SHAPES = [(1, 1, 4), (16, 320, 512), (49, 256, 512), (49, 1024, 512), (49, 16, 512), (169, 8, 512), (64, 33, 1024), (65, 17, 512),
+                (88, 40, 512), (89, 40, 512), (176, 70, 36), (25, 65, 512)]
+COORD_GRID16 = len(COORD_SHAPES)                       # one more case: the 4 x 4 carrier grid's own coordinates (multiples of 1/2), dim 24
+COORD_CASES = tuple(range(len(COORD_SHAPES) + 1))
+COORD_SET = (-3, -2, -1, 0, 1, 2, 3)
+COORD_B0 = (-3, -1, 0, 1, 3)
+
+
+def grid_coords(s: int) -> torch.Tensor:
+    """[s*s, 2] f64: (y, x) / (s // 2) - 1, the coordinates PosEmbMLPSwinv1D feeds its MLP."""
+    ar = torch.arange(0, s, dtype=torch.float64)
+    grid = torch.stack(torch.meshgrid([ar, ar], indexing="ij"))
+    return ((grid - s // 2) / (s // 2)).flatten(1).t().contiguous()
+
+
+def mlp64(coords, w0, b0, w2, dtable):
+    """(pre-activation, table, dw0, db0, dw2) of table = relu(coords w0^T + b0) w2^T under the output gradient dtable, float64 by
+    autograd: torch.relu passes no gradient at a pre-activation of exactly 0."""
+    w0, b0, w2 = (t.clone().requires_grad_(True) for t in (w0, b0, w2))
+    pre = coords @ w0.t() + b0
+    table = torch.relu(pre) @ w2.t()
+    table.backward(dtable)
+    return pre.detach(), table.detach(), w0.grad, b0.grad, w2.grad
+
+
+def _mlp_conditions(what, coords, w0, b0, w2, dtable, ref, q_dt=1.0):
+    """check_exact for one MLP job: every sum stated as sum |term| per output (dw0 / db0 through dh)."""
+    pre, table, dw0, db0, dw2 = ref
+    qc = quantum_of(coords)
+    h_abs = coords.abs() @ w0.abs().t() + b0.abs()                     # >= |pre| >= h: bounds the pre-activation's own sum too
+    dh_abs = dtable.abs() @ w2.abs()
+    mask = (pre > 0).double()
+    check_exact(what,
+                operands=[("coords", coords, (F32,)), ("w0", w0, (F32,)), ("b0", b0, (F32,)), ("w2", w2, (F32,)), ("dtable", dtable, (F32,))],
+                reductions=[("coords w0^T + b0", h_abs, qc), ("h w2^T", h_abs @ w2.abs().t(), qc), ("dtable^T h", dtable.abs().t() @ h_abs, qc * q_dt),
+                            ("dtable w2", dh_abs, q_dt), ("dh^T coords", (dh_abs * mask).t() @ coords.abs(), qc * q_dt),
+                            ("sum dh", (dh_abs * mask).sum(0), q_dt)],
+                results=[("table", table, (F32,)), ("dw0", dw0, (F32,)), ("db0", db0, (F32,)), ("dw2", dw2, (F32,))])
+    if quantum_of(pre) < qc or quantum_of(dtable) < q_dt:
+        raise ConditionViolated(f"{what}: a term is no multiple of its quantum")
+
+
+@functools.lru_cache(maxsize=None)                       # the largest case holds 1024 x 512 doubles: the batch tests reuse all of them
+def coord_mlp(ci: int):
+    """One MLP job on integer data: coords in [-3, 3] (zeros included), w0 and w2 from S2, b0 from (-3, -1, 0, 1, 3), dtable from S3.
+    Pre-activations of exactly 0 occur (h = 0 and no gradient through them); the builder asserts that they do wherever the case has a
+    thousand pre-activations, and that some of them would carry a gradient if the mask let it through."""
+    if ci == COORD_GRID16:
+        T, D, Hd = 16, 24, 512
+        coords = grid_coords(4)
+    else:
+        T, D, Hd = COORD_SHAPES[ci]
+        coords = pick((T, 2), 8000 + ci, COORD_SET)
+    what = f"coord MLP {(T, D, Hd)}" + (" on the 4 x 4 grid" if ci == COORD_GRID16 else "")
+    w0, b0, w2 = pick((Hd, 2), 8100 + ci, S2), pick((Hd,), 8200 + ci, COORD_B0), pick((D, Hd), 8300 + ci, S2)
+    dtable = pick((T, D), 8400 + ci, S3)
+    ref = mlp64(coords, w0, b0, w2, dtable)
+    _mlp_conditions(what, coords, w0, b0, w2, dtable, ref)
+    pre = ref[0]
+    at_zero = pre == 0
+    if T * Hd >= 1000:
+        share = float(at_zero.double().mean())
+        if not 0.02 <= share <= 0.25:
+            raise ConditionViolated(f"{what}: {share:.1%} of the pre-activations are exactly 0")
+        if not bool(((dtable @ w2) * at_zero.double() != 0).any()):
+            raise ConditionViolated(f"{what}: no unit with a pre-activation of 0 would carry a gradient")
+    return NS(what=what, shape=(T, D, Hd), coords=f32(coords), w0=f32(w0), b0=f32(b0), w2=f32(w2), dtable=f32(dtable), pre=pre,
+              table=ref[1], dw0=ref[2], db0=ref[3], dw2=ref[4], zeros=int(at_zero.sum()))
+
+
+# (n_local, n_global, T, H, index): window attention with 4 carrier tokens, level 3's window attention, the carrier grid's attention -
+# all with the relative position index of their window - and one job whose random index leaves table rows without a reference
+CPB_GEOMS = [(49, 4, 169, 8, "window"), (49, 0, 169, 16, "window"), (16, 0, 49, 8, "window"), (49, 4, 169, 8, "sparse")]
+SIGMOID_SAT = (-128, 64)                                # sigmoid_f gives exactly 0 / exactly 1 there (act64: z <= -89 / z >= 17)
+
+
+def window_index(ws: int) -> torch.Tensor:
+    """int32 [ws^4]: the relative position index of a ws x ws window (PosEmbMLPSwinv2D)."""
+    ar = torch.arange(ws)
+    pos = torch.flatten(torch.stack(torch.meshgrid([ar, ar], indexing="ij")), 1)
+    rc = (pos[:, :, None] - pos[:, None, :]).permute(1, 2, 0).contiguous() + (ws - 1)
+    return (rc[:, :, 0] * (2 * ws - 1) + rc[:, :, 1]).reshape(-1).to(torch.int32)
+
+
+@functools.lru_cache(maxsize=None)
+def coord_cpb(gi: int):
+    """The whole "cpb" chain, exact end to end: MLP -> table -> bias = 16 sigmoid(table[idx]) -> dbias -> dtable -> MLP backward.
+    The hidden units come in pairs with the same w0 / b0 row and opposite w2 columns, so the table of a non-trivial MLP is exactly 0
+    in any summation order: bias = 8 in the local block and 0 in the carrier rows / columns, dtable = 16 * 0.5 * 0.5 * scatter(dbias),
+    and the MLP backward goes on from there on integers.  `sat_*`: a second table from SIGMOID_SAT for the forward gather alone
+    (bias = 0 or 16 by the row the index names; the derivative is 0 there, so the backward is checked at table = 0)."""
+    nl, ng, T, H, kind = CPB_GEOMS[gi]
+    Hd, S = 512, nl + ng
+    what = f"cpb chain {CPB_GEOMS[gi]}"
+    gen = torch.Generator().manual_seed(8500 + gi)
+    if kind == "window":
+        idx = window_index(int(nl ** 0.5))
+    else:
+        rows = torch.randperm(T, generator=gen)[: T // 2]                           # half of the rows are never named
+        idx = rows[torch.randint(0, rows.numel(), (nl * nl,), generator=gen)].to(torch.int32)
+    if int(idx.min()) < 0 or int(idx.max()) >= T:
+        raise ConditionViolated(f"{what}: the index leaves the table")
+    used = torch.zeros(T, dtype=torch.bool).index_fill_(0, idx.long(), True)
+    if kind == "sparse" and int((~used).sum()) < T // 4:
+        raise ConditionViolated(f"{what}: too few table rows without a reference")
+    coords = pick((T, 2), 8600 + gi, COORD_SET)
+    half_w0, half_b0, half_w2 = pick((Hd // 2, 2), 8700 + gi, S2), pick((Hd // 2,), 8800 + gi, COORD_B0), pick((H, Hd // 2), 8900 + gi, S2)
+    w0, b0 = half_w0.repeat_interleave(2, 0), half_b0.repeat_interleave(2, 0)
+    w2 = torch.stack([half_w2, -half_w2], 2).reshape(H, Hd)
+    dbias = pick((H, S, S), 9000 + gi, S3)
+    local = dbias[:, ng:, ng:].reshape(H, nl * nl)
+    dtable = 4.0 * torch.zeros(H, T, dtype=torch.float64).index_add_(1, idx.long(), local).t().contiguous()
+    dtable_abs = 4.0 * torch.zeros(H, T, dtype=torch.float64).index_add_(1, idx.long(), local.abs()).t()
+    ref = mlp64(coords, w0, b0, w2, dtable)
+    if float(ref[1].abs().max()) != 0.0 or float(torch.relu(ref[0]).max()) == 0.0:
+        raise ConditionViolated(f"{what}: the table is not exactly 0 behind a non-trivial hidden layer")
+    if bool((dtable[~used] != 0).any()) or not bool((dtable[used] != 0).any()):
+        raise ConditionViolated(f"{what}: dtable is not zero exactly in the rows the index never names")
+    check_exact(what, operands=[("dbias", dbias, (F32,))], reductions=[("scatter", dtable_abs, 1.0)], results=[("dtable", dtable, (F32,))])
+    _mlp_conditions(what, coords, w0, b0, w2, dtable, ref, 4.0)
+    bias = torch.zeros(H, S, S, dtype=torch.float64)
+    bias[:, ng:, ng:] = 8.0
+    sat_table = pick((T, H), 9100 + gi, SIGMOID_SAT)
+    sat_bias = torch.zeros(H, S, S, dtype=torch.float64)
+    sat_bias[:, ng:, ng:] = 16.0 * (sat_table[idx.long()] > 0).double().view(nl, nl, H).permute(2, 0, 1)
+    return NS(what=what, geom=(nl, ng, T, H), shape=(T, H, Hd), idx=idx, used=used, coords=f32(coords), w0=f32(w0), b0=f32(b0), w2=f32(w2),
+              dbias=f32(dbias), bias=bias, dtable=dtable, pre=ref[0], table=ref[1], dw0=ref[2], db0=ref[3], dw2=ref[4],
+              sat_table=f32(sat_table), sat_bias=sat_bias)
+
+
+# The shipped geometries on real numbers: (dim, tokens) of the position tables, (window, heads, tokens) of the attention biases
+SHIPPED_POS = [(256, 49), (256, 16), (1024, 49)]
+SHIPPED_CPB = [(7, 8, 53), (7, 16, 49), (4, 8, 16)]
+SHIPPED_SEED = 0
+
+
+def relu_margin(what: str, coords: torch.Tensor, w0: torch.Tensor, b0: torch.Tensor) -> float:
+    """A hidden unit whose pre-activation changes sign between f32 and float64 moves dw0 / db0 by a whole term, not by rounding.  So
+    every pre-activation v (float64, of the f32 operands) has to satisfy |v| > 4 * 2**-24 * (|cx w0x| + |cy w0y| + |b0|): four times
+    the worst rounding of any f32 evaluation order, fused or not.  Returns the smallest |v| / bound; raises below 1."""
+    c, w, b = coords.double(), w0.double(), b0.double()
+    v = c @ w.t() + b
+    bound = 4.0 * 2.0 ** -24 * (c.abs() @ w.abs().t() + b.abs())
+    ratio = float((v.abs() / bound.clamp_min(1e-300)).min())
+    if not bool((v.abs() > bound).all()):
+        raise ConditionViolated(f"{what}: a pre-activation lies within f32 rounding of 0 (|v| / bound = {ratio:.3g}): its ReLU mask is "
+                                f"not determined")
+    return ratio
+
+
+def randomise_cpb(module: torch.nn.Module, gen: torch.Generator) -> None:
+    """As tests/test_fastervit_gpu.py randomise(): first layer N(0, 0.5), second N(0, 0.05), bias N(0, 0.1), drawn in f32."""
+    with torch.no_grad():
+        for name, p in module.named_parameters():
+            if name.endswith("bias"):
+                p.copy_(torch.randn(p.shape, generator=gen) * 0.1)
+            else:
+                p.copy_(torch.randn(p.shape, generator=gen) * (0.5 if p.shape[-1] == 2 else 0.05))
+
+
+@functools.lru_cache(maxsize=2)
+def coord_shipped(seed: int = SHIPPED_SEED):
+    """The six coordinate MLPs of a hierarchical-attention block at the shipped sizes, weights as the model tests draw them.  Per job:
+    the project's own coordinate / index buffers and the f32 parameters (what the kernels get), the oracle module carrying the same
+    parameters in float64, its output and the gradients under a Gaussian output gradient.  relu_margin has passed for every job."""
+    from deepfakedetection_amd.fastervit import PosEmbMLPSwinv1D, PosEmbMLPSwinv2D
+    from oracle.fastervit_ref import PosEmb1D, PosEmb2D
+
+    gen = torch.Generator().manual_seed(seed)
+    jobs = []
+    for kind, spec in [("pos", s) for s in SHIPPED_POS] + [("cpb", s) for s in SHIPPED_CPB]:
+        if kind == "pos":
+            dim, tokens = spec
+            ours, ref32 = PosEmbMLPSwinv1D(dim, tokens), PosEmb1D(dim, tokens)
+            coords, idx, nl, ng = ours._coords, None, 0, 0
+        else:
+            ws, heads, tokens = spec
+            ours, ref32 = PosEmbMLPSwinv2D(ws, heads, tokens), PosEmb2D(ws, heads, tokens)
+            coords, idx, nl, ng = ours._coords2d, ours._idx32, ws * ws, tokens - ws * ws
+            if not torch.equal(idx.long(), ref32.relative_position_index.reshape(-1)):
+                raise ConditionViolated(f"shipped {kind} {spec}: the project's index is not the oracle's")
+        randomise_cpb(ref32, gen)
+        w0, b0, w2 = (p.detach().clone() for p in (ref32.cpb_mlp[0].weight, ref32.cpb_mlp[0].bias, ref32.cpb_mlp[2].weight))
+        what = f"shipped {kind} {spec} seed {seed}"
+        margin = relu_margin(what, coords, w0, b0)
+        out32 = (ref32.table(tokens)[0] if kind == "pos" else ref32.bias(tokens)[0]).detach()       # the oracle as the model tests run it
+        ref64 = ref32.double()                                                      # the same f32 numbers, held as float64
+        if kind == "pos":
+            # PosEmb1D.table builds its grid in f32 inside the call, which a float64 module cannot take: the float64 reference is
+            # the oracle's cpb_mlp on the same grid, after the grid has been checked against the oracle's formula
+            if float((coords.double() - grid_coords(int(tokens ** 0.5))).abs().max()) > 2.0 ** -24:
+                raise ConditionViolated(f"{what}: the project's coordinates are not the oracle's")
+            out = ref64.cpb_mlp(coords.double())
+        else:
+            if not torch.equal(coords.double(), ref64.relative_coords_table.reshape(-1, 2)):
+                raise ConditionViolated(f"{what}: the project's coordinates are not the oracle's")
+            out = ref64.bias(tokens)[0]
+        drift = float((out32.double() - out.detach()).abs().max() / out.detach().abs().max())
+        if not drift <= 2e-6:
+            raise ConditionViolated(f"{what}: the f32 oracle is {drift:.3g} of max |ref| away from its float64 form")
+        g = torch.randn(out.shape, generator=gen)
+        grads = torch.autograd.grad(out, [ref64.cpb_mlp[0].weight, ref64.cpb_mlp[0].bias, ref64.cpb_mlp[2].weight], g.double())
+        jobs.append(NS(kind=kind, spec=spec, coords=coords.clone(), idx=idx, n_local=nl, n_global=ng, w0=w0, b0=b0, w2=w2, g=g,
+                       out=out.detach(), dw0=grads[0], db0=grads[1], dw2=grads[2], margin=margin, drift=drift))
+    return jobs
 
 
 # ------------------------------------------------------------------------------------------- rounding of the bf16 stores
