@@ -78,33 +78,27 @@ class ModelEma:
             else:
                 raise RuntimeError(f"EMA: {name}: no kernel for {s.dtype} tensors of {s.numel()} elements")
             self._pairs.append((s.detach(), d.detach(), kind))
-        self._flat = [t for s, d, _ in self._pairs for t in (s, d)]      # what the table points at
         self.device = self._pairs[0][0].device if self._pairs else None
         self._w = torch.zeros(1, dtype=torch.float32, device=self.device) if self._pairs else None
-        self._cached: tuple | None = None           # (addresses, pinned host table, device table)
+        self._cached: K.AddressTable | None = None
         self._table()                               # built outside any capture: a capture cannot allocate it
 
-    def _table(self) -> torch.Tensor:
-        key = tuple(t.data_ptr() for t in self._flat)
+    def _table(self) -> K.AddressTable:
+        flat = [t for s, d, _ in self._pairs for t in (s, d)]      # what the table points at
         cached = self._cached
-        if cached is not None and cached[0] == key:
-            return cached[2]
+        if cached is not None and cached.valid_for(flat):
+            return cached
         rows = []
         for s, d, kind in self._pairs:
             n, esz = (s.numel(), 4) if kind == EMA_LERP else (s.numel() * s.element_size() // 8, 8)
             for off in range(0, n, _CHUNK):
                 rows.append([s.data_ptr() + esz * off, d.data_ptr() + esz * off, min(_CHUNK, n - off), kind])
-        host = torch.tensor(rows, dtype=torch.int64).pin_memory()
-        assert host.shape[1] == EMA_TABLE_COLS
-        if cached is not None and cached[2].shape == host.shape:
-            dev = cached[2]
-        elif torch.cuda.is_current_stream_capturing():
+        assert len(rows[0]) == EMA_TABLE_COLS
+        if (cached is None or len(rows) != cached.dev.shape[0]) and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("ModelEma: the table grew under stream capture; rebuild the captured step")
-        else:
-            dev = torch.empty_like(host, device=self.device)
-        dev.copy_(host, non_blocking=True)          # pinned + async: legal under stream capture
-        self._cached = (key, host, dev)
-        return dev
+        table = self._cached = K.AddressTable(flat)
+        table.upload(rows, self.device, cached)
+        return table
 
     def decay_at(self, k: int) -> float:
         return decay_at(k, self.decay, self.warmup)
@@ -124,10 +118,7 @@ class ModelEma:
             return
         if self.updates == 0:
             raise RuntimeError("ModelEma.update() needs prepare() first")
-        table = self._table()
-        K.journal_note(self._flat)                  # the table carries these addresses (no-op outside a capture)
-        K.journal_note((table, self._w))
-        K.ema_update(table, self._w)
+        K.ema_update(self._table(), self._w)
 
     def step(self) -> None:
         """prepare() + update(): one EMA update after an eager optimizer step."""

@@ -87,30 +87,23 @@ class CoordTablesFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, jobs, *params):
-        from ._lib import CmlpJob, RelposJob
-
         dev = params[0].device
-        n = len(jobs)
         tables, outs = [], []
-        cj = (CmlpJob * n)()
-        rp = []
+        cj, rp = [], []
         for i, job in enumerate(jobs):
             w0, b0, w2 = params[3 * i:3 * i + 3]
             T, D = job.coords.shape[0], w2.shape[0]
             tab = torch.empty((T, D), dtype=torch.float32, device=dev)
             tables.append(tab)
-            cj[i] = CmlpJob(K._p(job.coords), K._p(w0), K._p(b0), K._p(w2), K._p(tab), None, None, None, None, T, D, w0.shape[0], 0)
+            cj.append((job.coords, w0, b0, w2, tab))
             if job.kind == "cpb":
                 S = job.n_local + job.n_global
                 full = torch.empty((D, S, S), dtype=torch.float32, device=dev)
-                rp.append(RelposJob(K._p(tab), K._p(job.idx), K._p(full), None, None, D, T, job.n_local, job.n_global))
+                rp.append((tab, job.idx, full, job.n_local, job.n_global))
                 outs.append(full)
             else:
                 outs.append(tab)
-        K.check(K._L().dfd_coord_mlp_fwd_multi(cj, n, K._stream()), "dfd_coord_mlp_fwd_multi")
-        if rp:
-            arr = (RelposJob * len(rp))(*rp)
-            K.check(K._L().dfd_relpos_bias_fwd_multi(arr, len(rp), K._stream()), "dfd_relpos_bias_fwd_multi")
+        K.coord_tables_fwd(cj, rp)
         # never keep an OUTPUT on ctx: output -> grad_fn (this node) -> ctx -> output is a cycle Python's collector cannot see
         # through; it would pin this node and the AccumulateGrad nodes behind it across iterations (and a stale AccumulateGrad
         # node on the legacy stream breaks a later hipGraph capture).  Only the raw tables of the "cpb" jobs are needed.
@@ -121,13 +114,11 @@ class CoordTablesFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *gouts):
-        from ._lib import CmlpJob, RelposJob
-
         jobs, params, shapes, raw = ctx.jobs, ctx.params, ctx.shapes, ctx.raw
         need = ctx.needs_input_grad[1:]
         dev = params[0].device
         grads: list = [None] * len(params)
-        cj, rp, keep = [], [], []
+        cj, rp = [], []
         for i, job in enumerate(jobs):
             g = gouts[i]
             nw0, nb0, nw2 = need[3 * i:3 * i + 3]
@@ -138,8 +129,7 @@ class CoordTablesFunction(torch.autograd.Function):
             g = _c(g.float())
             if job.kind == "cpb":
                 dtab = torch.empty((T, D), dtype=torch.float32, device=dev)
-                rp.append(RelposJob(K._p(raw[i]), K._p(job.idx), None, K._p(g), K._p(dtab), D, T, job.n_local, job.n_global))
-                keep.append(g)
+                rp.append((raw[i], job.idx, g, dtab, job.n_local, job.n_global))
                 g = dtab
             dw0 = (_slot(w0, True, tuple(w0.shape)) if nw0 else None)
             db0 = (_slot(b0, True, tuple(b0.shape)) if nb0 else None)
@@ -151,15 +141,8 @@ class CoordTablesFunction(torch.autograd.Function):
             if nw2 and dw2 is None:
                 dw2 = torch.empty_like(w2)
             grads[3 * i], grads[3 * i + 1], grads[3 * i + 2] = dw0, db0, dw2
-            keep.append(g)
-            cj.append(CmlpJob(K._p(job.coords), K._p(w0), K._p(b0), K._p(w2), None, K._p(g), K._p(dw0), K._p(db0), K._p(dw2),
-                              T, D, w0.shape[0], 0))
-        if rp:
-            arr = (RelposJob * len(rp))(*rp)
-            K.check(K._L().dfd_relpos_bias_bwd_multi(arr, len(rp), K._stream()), "dfd_relpos_bias_bwd_multi")
-        if cj:
-            arr = (CmlpJob * len(cj))(*cj)
-            K.check(K._L().dfd_coord_mlp_bwd_multi(arr, len(cj), K._stream()), "dfd_coord_mlp_bwd_multi")
+            cj.append((job.coords, w0, b0, w2, g, dw0, db0, dw2))
+        K.coord_tables_bwd(rp, cj)
         return (None, *grads)
 
 
@@ -239,11 +222,7 @@ def window_attention_bwd(qkv, dO, saved, bias, H: int, need_bias: bool):
     dq, dk, dv = dqkv.view(n * T, 3 * C)[:, 0:C], dqkv.view(n * T, 3 * C)[:, C:2 * C], dqkv.view(n * T, 3 * C)[:, 2 * C:]
     K.bgemm(Pm, (H * L, L, 1, T), dO, (T * C, hd, C, 1), dv, (T * 3 * C, hd, 3 * C, 1), n, H, T, hd, T)
     dS_buf = torch.empty((_partial_rows(n), H, T, T), dtype=torch.float32, device=dev)
-    from ._lib import check
-
-    check(K._L().dfd_attn_softmax_bwd(dT2.data_ptr(), Pm.data_ptr(), None, None, None, dS_buf.data_ptr(), n, H, T, T, K._stream()),
-          "dfd_attn_softmax_bwd")
-    dS = dS_buf[:n]
+    _, dS = K.attn_softmax_bwd(dT2, Pm, None, out=dS_buf[:n])
     scale = hd ** -0.5
     K.bgemm(dS, (H * L, L, T, 1), k, (T * 3 * C, hd, 3 * C, 1), dq, (T * 3 * C, hd, 3 * C, 1), n, H, T, hd, T, alpha=scale)
     K.bgemm(dS, (H * L, L, 1, T), q, (T * 3 * C, hd, 3 * C, 1), dk, (T * 3 * C, hd, 3 * C, 1), n, H, T, hd, T, alpha=scale)

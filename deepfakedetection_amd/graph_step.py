@@ -38,8 +38,9 @@ capture — scripts/probes/external_event_probe.py — so "one graph + events" i
 the exchange and then runs (replays) AdamW with grad_scale = 1/world — bench.py --gpus N and the trainers drive this
 same object.
 
-By-address hazards.  A graph records raw addresses.  Every tensor whose address reached the library during a capture
-is journalled (kernels.capture_journal); the ones owned by something outside the captured body (parameters, buffers,
+By-address hazards.  A graph records raw addresses.  Every tensor whose address reached the library during a capture,
+as a direct argument (kernels._p) or inside a table of addresses (kernels.AddressTable), is journalled
+(kernels.capture_journal); the ones owned by something outside the captured body (parameters, buffers,
 derived-weight / BN-coefficient caches, index maps, optimizer state and tables, the Philox state) are checked before
 EVERY replay: if one was freed or moved (a cache rebuilt after .to(), a regrown table) the replay raises `StaleGraphError`
 instead of reading or writing memory it no longer owns.

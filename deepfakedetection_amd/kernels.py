@@ -4,6 +4,11 @@ Every function here takes NHWC tensors ([N, H, W, C] contiguous, f32 or bf16) th
 live on a HIP device, allocates outputs with torch (device memory is torch's job),
 and enqueues exactly the kernels of libdfd_hip.so on torch's current stream.  There
 is no fallback: a CPU tensor or a missing library raises.
+
+Only this module loads or calls the library, and a device address reaches it in two
+ways: as a direct argument through the gate `_p`, or inside a table of addresses (job
+array, chunk table) whose `AddressTable` the launching front end notes.  Both record
+the tensor in the open capture journal: a captured graph's replay guard is complete.
 """
 
 from __future__ import annotations
@@ -36,22 +41,30 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
-def _dt(t: torch.Tensor) -> int:
-    if t.dtype == torch.float32:
+def _dt(t: torch.Tensor | torch.dtype) -> int:
+    """The ABI's dtype code of a tensor or of a torch.dtype."""
+    dtype = t.dtype if isinstance(t, torch.Tensor) else t
+    if dtype == torch.float32:
         return F32
-    if t.dtype == torch.bfloat16:
+    if dtype == torch.bfloat16:
         return BF16
-    raise TypeError(f"unsupported activation dtype {t.dtype}")
+    raise TypeError(f"unsupported activation dtype {dtype}")
 
 
 # ---- capture journal (graph_step.GraphedTrainStep / GraphedForward).  A hipGraph records raw addresses.  While a capture
 # is open every tensor whose address goes to the library is noted here (weak reference to the tensor — or to its base
-# when it is a view — plus the address).  After the capture the owner keeps the entries that (a) are still alive, i.e.
-# are owned by something outside the captured body (parameters, buffers, caches, the optimizer's state and tables, the
-# Philox state), and (b) do not sit in the graph's private memory pool; before every replay it asserts that each of
-# them still lives at the recorded address (`stale_entries`).  A cache that replaced or dropped a recorded tensor
+# when it is a view — plus the address).  Nothing but `_p` (direct arguments) and `AddressTable.note` (addresses inside a
+# job array or a chunk table) hands an address to the library, and both note it.  After the capture the owner keeps the
+# entries that (a) are still alive, i.e. are owned by something outside the captured body (parameters, buffers, caches,
+# the optimizer's state and tables, the Philox state), and (b) do not sit in the graph's private memory pool; before
+# every replay it asserts that each of them still lives at the recorded address (`stale_entries`).  A cache that replaced or dropped a recorded tensor
 # (dtype switch, regrown buffer, rebuilt table) then raises instead of letting the replay read or write freed memory.
 _journal: dict | None = None
+
+
+def _root(t: torch.Tensor) -> torch.Tensor:
+    """The tensor that owns `t`'s memory: its base when `t` is a view."""
+    return t._base if t._base is not None else t
 
 
 def journal_note(t) -> None:
@@ -65,9 +78,12 @@ def journal_note(t) -> None:
         return
     if not t.is_cuda:
         return
-    base = t._base if t._base is not None else t
+    base = _root(t)
     key = id(base)
-    if key not in j:
+    seen = j.get(key)
+    if seen is None or seen[0]() is not base:
+        if seen is not None:
+            j[(key, len(j))] = seen             # the id() of a tensor that died was reused: its record moves aside
         try:
             j[key] = (weakref.ref(base), base.data_ptr(), base.numel() * base.element_size(), tuple(base.shape), base.dtype)
         except TypeError:
@@ -123,16 +139,60 @@ def stale_entries(guard: list[tuple]) -> list[str]:
     return bad
 
 
-def _p(t: torch.Tensor | None):
+def _p(t: torch.Tensor | None, strided: bool = False):
+    """The gate: the device address of `t` as a library argument, noted in the open capture journal.  strided: the
+    entry point takes the strides next to the address (dfd_bgemm), so `t` may be any view."""
     if t is None:
         return None
     if not t.is_cuda:
         raise RuntimeError("dfd kernels need tensors on a HIP device (no CPU fallback)")
-    if not t.is_contiguous():
+    if not strided and not t.is_contiguous():
         raise ValueError(f"dfd kernels need contiguous tensors, got shape {tuple(t.shape)} strides {t.stride()}")
     if _journal is not None:
         journal_note(t)
     return t.data_ptr()
+
+
+class AddressTable:
+    """What the owner of a table of raw addresses (a ctypes job array, an int64 chunk table `dev` in device memory) keeps
+    beside its rows: the tensors the rows point at (weakly, by the tensor that owns the memory, like the journal) with the
+    addresses they had when it was built, and the table's own device storage.  The launching front end calls note()."""
+
+    def __init__(self, tensors, own=()) -> None:
+        tensors = [t for t in tensors if t is not None]
+        self.refs = [weakref.ref(_root(t)) for t in tensors]
+        self.ptrs = [t.data_ptr() for t in tensors]
+        self.own = [t for t in own if t is not None]
+        self.host = self.dev = None
+
+    def valid_for(self, tensors) -> bool:
+        """Do `tensors` live where the rows say?  The table then refers to them (equal addresses, maybe new tensor objects)."""
+        tensors = [t for t in tensors if t is not None]
+        if len(tensors) != len(self.ptrs) or any(t.data_ptr() != p for t, p in zip(tensors, self.ptrs)):
+            return False
+        self.refs = [weakref.ref(_root(t)) for t in tensors]
+        return True
+
+    def upload(self, rows: list, device, old: "AddressTable | None" = None) -> None:
+        """int64 `rows` -> `dev` through pinned memory, into `old`'s device storage when the shape is unchanged."""
+        self.host = torch.tensor(rows, dtype=torch.int64).pin_memory()
+        reuse = old is not None and old.dev is not None and old.dev.shape == self.host.shape
+        self.dev = old.dev if reuse else torch.empty_like(self.host, device=device)
+        self.dev.copy_(self.host, non_blocking=True)        # pinned + async: legal under stream capture
+
+    def note(self) -> None:
+        if _journal is not None:
+            journal_note(r() for r in self.refs)
+            journal_note(self.own)
+            journal_note(self.dev)
+
+
+def _table(table) -> tuple:
+    """(address, rows) of an int64 chunk table for a launch: an AddressTable (noted) or a bare device tensor."""
+    if isinstance(table, AddressTable):
+        table.note()
+        table = table.dev
+    return _p(table), table.shape[0]
 
 
 def _chk_nhwc(t: torch.Tensor) -> None:
@@ -737,8 +797,7 @@ def prep_weights(w: torch.Tensor, dtype: torch.dtype, want_nk: bool = True, want
     Nn, K = w.shape[0], w.shape[1]
     w_nk = torch.empty((Nn, K), dtype=dtype, device=w.device) if want_nk else None
     w_kn = torch.empty((K, Nn), dtype=dtype, device=w.device) if want_kn else None
-    code = BF16 if dtype == torch.bfloat16 else F32
-    check(_L().dfd_pw_prep_weights(code, _p(w), _p(w_nk), _p(w_kn), Nn, K, _stream()), "dfd_pw_prep_weights")
+    check(_L().dfd_pw_prep_weights(_dt(dtype), _p(w), _p(w_nk), _p(w_kn), Nn, K, _stream()), "dfd_pw_prep_weights")
     return w_nk, w_kn
 
 
@@ -749,31 +808,25 @@ class DerivedWeights:
     destination buffers are allocated once and handed out by index."""
 
     def __init__(self, items: list[tuple[torch.Tensor, bool, bool, bool]], dtype: torch.dtype) -> None:
-        from ._lib import PrepJob
-
         self.dtype = dtype
-        self.sources = [src for src, _, _, _ in items]
-        self.ptrs = [src.data_ptr() for src in self.sources]
         self.out: list[tuple[torch.Tensor | None, torch.Tensor | None]] = []
-        jobs = (PrepJob * len(items))()
+        jobs = (_lib.PrepJob * len(items))()
         for i, (src, want_nk, want_kn, is_se) in enumerate(items):
             n, kdim = src.shape[0], src.shape[1]
             dt = torch.float32 if is_se else dtype
             nk = torch.empty((n, kdim), dtype=dt, device=src.device) if want_nk else None
             kn = torch.empty((kdim, n), dtype=dt, device=src.device) if want_kn else None
             self.out.append((nk, kn))
-            jobs[i] = PrepJob(src.data_ptr(), nk.data_ptr() if nk is not None else None,
-                              kn.data_ptr() if kn is not None else None, n, kdim, BF16 if dt == torch.bfloat16 else F32, 0)
+            jobs[i] = _lib.PrepJob(src.data_ptr(), nk.data_ptr() if nk is not None else None,
+                                   kn.data_ptr() if kn is not None else None, n, kdim, _dt(dt), 0)
         self._jobs = jobs
+        self.table = AddressTable([src for src, _, _, _ in items], own=[t for pair in self.out for t in pair])
 
     def valid_for(self, sources: list[torch.Tensor], dtype: torch.dtype) -> bool:
-        return dtype == self.dtype and len(sources) == len(self.ptrs) and all(
-            s.data_ptr() == p for s, p in zip(sources, self.ptrs))
+        return dtype == self.dtype and self.table.valid_for(sources)
 
     def refresh(self) -> None:
-        if _journal is not None:                # the job table carries raw addresses: sources and destinations
-            journal_note(self.sources)
-            journal_note([t for pair in self.out for t in pair])
+        self.table.note()
         check(_L().dfd_prep_weights_multi(self._jobs, len(self._jobs), _stream()), "dfd_prep_weights_multi")
 
 
@@ -802,14 +855,10 @@ class MxWeights:
     (dfd_mx_quant_weights_multi) together with the dequantised [K][N] copies the bf16 backward multiplies by."""
 
     def __init__(self, sources: list[torch.Tensor], dtype: torch.dtype) -> None:
-        from ._lib import MxJob
-
         self.dtype = dtype
-        self.sources = list(sources)
-        self.ptrs = [s.data_ptr() for s in self.sources]
         self.out: list[tuple[MxWeight, torch.Tensor]] = []
-        jobs = (MxJob * len(self.sources))()
-        for i, src in enumerate(self.sources):
+        jobs = (_lib.MxJob * len(sources))()
+        for i, src in enumerate(sources):
             n, kdim = src.shape
             if kdim % 128:
                 raise ValueError(f"MX fp8 weights need K % 128 == 0, got {tuple(src.shape)}")
@@ -817,16 +866,15 @@ class MxWeights:
             sc = torch.empty((n, kdim // 32), dtype=torch.uint8, device=src.device)
             kn = torch.empty((kdim, n), dtype=dtype, device=src.device)
             self.out.append((MxWeight(q, sc), kn))
-            jobs[i] = MxJob(src.data_ptr(), q.data_ptr(), sc.data_ptr(), kn.data_ptr(), n, kdim, _code(dtype), 0)
+            jobs[i] = _lib.MxJob(src.data_ptr(), q.data_ptr(), sc.data_ptr(), kn.data_ptr(), n, kdim, _dt(dtype), 0)
         self._jobs = jobs
+        self.table = AddressTable(sources, own=[t for w, kn in self.out for t in (w.q, w.scale, kn)])
 
     def valid_for(self, sources: list[torch.Tensor], dtype: torch.dtype) -> bool:
-        return dtype == self.dtype and len(sources) == len(self.ptrs) and all(s.data_ptr() == p for s, p in zip(sources, self.ptrs))
+        return dtype == self.dtype and self.table.valid_for(sources)
 
     def refresh(self) -> None:
-        if _journal is not None:
-            journal_note(self.sources)
-            journal_note([t for w, kn in self.out for t in (w.q, w.scale, kn)])
+        self.table.note()
         check(_L().dfd_mx_quant_weights_multi(self._jobs, len(self._jobs), _stream()), "dfd_mx_quant_weights_multi")
 
 
@@ -853,9 +901,23 @@ def mx_gemm(aq: torch.Tensor, ascale: torch.Tensor, w: MxWeight, out_dtype: torc
     if Kd != w.K:
         raise ValueError(f"mx_gemm: K mismatch {Kd} vs {w.K}")
     out = torch.empty(out_shape if out_shape is not None else (M, w.N), dtype=out_dtype, device=aq.device)
-    check(_L().dfd_mx_gemm(_p(aq), _p(ascale), _p(w.q), _p(w.scale), _code(out_dtype), _p(out), M, Kd, w.N, _stream()),
+    check(_L().dfd_mx_gemm(_p(aq), _p(ascale), _p(w.q), _p(w.scale), _dt(out_dtype), _p(out), M, Kd, w.N, _stream()),
           "dfd_mx_gemm", f"M={M} K={Kd} N={w.N}")
     return out
+
+
+def _bn_eval_jobs(bns: list):
+    """(coefficient blocks [4][C] cut from one buffer, BnEvalJob array, AddressTable) for BatchNorm2d modules or BNParams."""
+    tens = [(bn.weight, bn.bias, getattr(bn, "conv_bias", None), getattr(bn, "ls", None), bn.running_mean, bn.running_var) for bn in bns]
+    with torch.inference_mode(False):
+        flat = torch.empty(sum(4 * ts[4].numel() for ts in tens), dtype=torch.float32, device=tens[0][4].device)
+    states, jobs, at = [], (_lib.BnEvalJob * len(bns))(), 0
+    for i, (bn, ts) in enumerate(zip(bns, tens)):
+        C = ts[4].numel()
+        states.append(flat[at:at + 4 * C].view(4, C))
+        at += 4 * C
+        jobs[i] = _lib.BnEvalJob(*(None if t is None else t.data_ptr() for t in ts), states[i].data_ptr(), float(bn.eps), C)
+    return states, jobs, AddressTable([t for ts in tens for t in ts], own=[flat])
 
 
 class BNEvalBatch:
@@ -867,12 +929,9 @@ class BNEvalBatch:
 
     def __init__(self) -> None:
         self.keys: list[tuple] | None = None
-        self.states: list[torch.Tensor] = []
-        self._jobs = None
-        self._flat = None
+        self.states, self._jobs, self.table = [], None, None
         self._rec: list[tuple[tuple, BNParams]] = []
-        self.pos = 0
-        self.ok = True
+        self.pos, self.ok = 0, True
 
     @staticmethod
     def _key(p: "BNParams") -> tuple:
@@ -882,7 +941,7 @@ class BNEvalBatch:
     def begin(self) -> None:
         self.pos, self.ok, self._rec = 0, True, []
         if self.keys is not None:
-            journal_note(self._flat)
+            self.table.note()
             check(_L().dfd_bn_eval_coeffs_multi(self._jobs, len(self._jobs), _stream()), "dfd_bn_eval_coeffs_multi")
 
     def request(self, p: "BNParams") -> torch.Tensor:
@@ -900,26 +959,11 @@ class BNEvalBatch:
     def end(self) -> None:
         if self.keys is None:
             if self._rec:
-                self._build()
+                self.states, self._jobs, self.table = _bn_eval_jobs([p for _, p in self._rec])
+                self.keys = [k for k, _ in self._rec]
         elif not self.ok or self.pos != len(self.keys):
-            self.keys, self.states, self._jobs, self._flat = None, [], None, None      # the pass changed: record again
+            self.keys, self.states, self._jobs, self.table = None, [], None, None      # the pass changed: record again
         self._rec = []
-
-    def _build(self) -> None:
-        from ._lib import BnEvalJob
-
-        recs = self._rec
-        dev = recs[0][1].running_mean.device
-        with torch.inference_mode(False):
-            self._flat = torch.empty(sum(4 * k[-1] for k, _ in recs), dtype=torch.float32, device=dev)
-        jobs, at, self.states = (BnEvalJob * len(recs))(), 0, []
-        for i, (key, _) in enumerate(recs):
-            C = key[-1]
-            st = self._flat[at:at + 4 * C].view(4, C)
-            at += 4 * C
-            self.states.append(st)
-            jobs[i] = BnEvalJob(key[0], key[1], key[2], key[3], key[4], key[5], st.data_ptr(), key[6], C)
-        self._jobs, self.keys = jobs, [k for k, _ in recs]
 
 
 class EvalBNStates:
@@ -928,33 +972,14 @@ class EvalBNStates:
     network for the duration of its own forward pass: a layer run on its own never sees a stale block."""
 
     def __init__(self, bns: list) -> None:
-        from ._lib import BnEvalJob
-
-        self.ptrs = [(bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr()) for bn in bns]
-        dev = bns[0].running_mean.device
-        total = sum(4 * bn.running_mean.numel() for bn in bns)
-        self.flat = torch.empty(total, dtype=torch.float32, device=dev)
-        self.states, jobs, at = [], (BnEvalJob * len(bns))(), 0
-        for i, bn in enumerate(bns):
-            C = bn.running_mean.numel()
-            st = self.flat[at:at + 4 * C].view(4, C)
-            at += 4 * C
-            self.states.append(st)
-            jobs[i] = BnEvalJob(bn.weight.data_ptr(), bn.bias.data_ptr(), None, None, bn.running_mean.data_ptr(),
-                                bn.running_var.data_ptr(), st.data_ptr(), float(bn.eps), C)
-        self._jobs = jobs
-        self._tensors = [t for bn in bns for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+        self.states, self._jobs, self.table = _bn_eval_jobs(bns)
         self.fresh = False
 
     def valid_for(self, bns: list) -> bool:
-        return len(bns) == len(self.ptrs) and all(
-            (bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr()) == p
-            for bn, p in zip(bns, self.ptrs))
+        return self.table.valid_for([t for bn in bns for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)])
 
     def refresh(self) -> None:
-        if _journal is not None:
-            journal_note(self.flat)
-            journal_note(self._tensors)
+        self.table.note()
         check(_L().dfd_bn_eval_coeffs_multi(self._jobs, len(self._jobs), _stream()), "dfd_bn_eval_coeffs_multi")
 
 
@@ -1201,15 +1226,17 @@ def cam_render(cam: torch.Tensor, size: tuple[int, int], image: torch.Tensor | N
     return heat, overlay
 
 
-def adamw_step(table: torch.Tensor, hp: torch.Tensor) -> None:
-    check(_L().dfd_adamw_step(_p(table), table.shape[0], _p(hp), _stream()), "dfd_adamw_step")
+def adamw_step(table, hp: torch.Tensor) -> None:
+    """One dfd_adamw_step launch over an AdamW chunk table (an AddressTable, or the bare device int64 tensor)."""
+    check(_L().dfd_adamw_step(*_table(table), _p(hp), _stream()), "dfd_adamw_step")
 
 
-def grad_sumsq(table: torch.Tensor, partials: torch.Tensor) -> None:
+def grad_sumsq(table, partials: torch.Tensor) -> None:
     """One dfd_grad_sumsq launch over an AdamW chunk table: partials[row] (f64, device) = sum of the squares of the row's gradients."""
-    if partials.dtype != torch.float64 or partials.numel() < table.shape[0]:
+    ptr, rows = _table(table)
+    if partials.dtype != torch.float64 or partials.numel() < rows:
         raise ValueError("grad_sumsq needs one f64 partial per table row")
-    check(_L().dfd_grad_sumsq(_p(table), table.shape[0], _p(partials), _stream()), "dfd_grad_sumsq")
+    check(_L().dfd_grad_sumsq(ptr, rows, _p(partials), _stream()), "dfd_grad_sumsq")
 
 
 def grad_clip_finish(partials: torch.Tensor, hp: torch.Tensor, cfg: torch.Tensor, state: torch.Tensor) -> None:
@@ -1220,14 +1247,15 @@ def grad_clip_finish(partials: torch.Tensor, hp: torch.Tensor, cfg: torch.Tensor
     check(_L().dfd_grad_clip_finish(_p(partials), partials.numel(), _p(hp), _p(cfg), _p(state), _stream()), "dfd_grad_clip_finish")
 
 
-def adamw_step_clip(table: torch.Tensor, hp: torch.Tensor, cfg: torch.Tensor, state: torch.Tensor) -> None:
+def adamw_step_clip(table, hp: torch.Tensor, cfg: torch.Tensor, state: torch.Tensor) -> None:
     """dfd_adamw_step with the gradient clipped as `cfg` and `state` (written by grad_clip_finish on this stream) say."""
-    check(_L().dfd_adamw_step_clip(_p(table), table.shape[0], _p(hp), _p(cfg), _p(state), _stream()), "dfd_adamw_step_clip")
+    check(_L().dfd_adamw_step_clip(*_table(table), _p(hp), _p(cfg), _p(state), _stream()), "dfd_adamw_step_clip")
 
 
-def ema_update(table: torch.Tensor, w: torch.Tensor) -> None:
-    """One dfd_ema_update launch over a device int64 table [nchunks][EMA_TABLE_COLS]; `w` is the f32 weight in device memory."""
-    check(_L().dfd_ema_update(_p(table), table.shape[0], _p(w), _stream()), "dfd_ema_update")
+def ema_update(table, w: torch.Tensor) -> None:
+    """One dfd_ema_update launch over a device int64 table [nchunks][EMA_TABLE_COLS] (an AddressTable, or the bare tensor);
+    `w` is the f32 weight in device memory."""
+    check(_L().dfd_ema_update(*_table(table), _p(w), _stream()), "dfd_ema_update")
 
 
 # ------------------------------------------------------------------ Mixup / CutMix (ABI 138)
@@ -1337,7 +1365,8 @@ def sum_rows(partials: torch.Tensor, P: int, L: int, out: torch.Tensor, accumula
     tmp = torch.empty((G + (G + 31) // 32 + 1) * L, dtype=torch.float32, device=partials.device)
     for gi in reversed(range(G)):
         rows = min(1024, P - gi * 1024)
-        check(_L().dfd_sum_rows(partials.data_ptr() + gi * 1024 * L * 4, rows, L, tmp.data_ptr() + gi * L * 4, 0, _stream()), "dfd_sum_rows")
+        at = gi * 1024 * L
+        check(_L().dfd_sum_rows(_p(partials[at:at + rows * L]), rows, L, _p(tmp[gi * L:(gi + 1) * L]), 0, _stream()), "dfd_sum_rows")
     return sum_rows(tmp, G, L, out, accumulate)
 
 
@@ -1371,22 +1400,12 @@ def subsample_add_bwd(g: torch.Tensor, dx: torch.Tensor, stride: int) -> torch.T
     return dx
 
 
-def _code(dtype: torch.dtype) -> int:
-    if dtype == torch.float32:
-        return F32
-    if dtype == torch.bfloat16:
-        return BF16
-    raise TypeError(f"unsupported dtype {dtype}")
-
-
 def bgemm(A: torch.Tensor, sa: tuple, B: torch.Tensor, sb: tuple, C: torch.Tensor, sc: tuple, nb: int, nh: int, M: int, N: int,
           Kd: int, alpha: float = 1.0, bias: torch.Tensor | None = None, round_a: bool = False, round_b: bool = False) -> None:
     """C[b,h,m,n] = alpha * sum_k A[b,h,m,k] B[b,h,k,n] (+ bias[h,m,n]); s* = (sb, sh, sr, sc) element strides."""
-    from ._lib import Mat
-
-    ma, mb, mc = Mat(*sa), Mat(*sb), Mat(*sc)
-    check(_L().dfd_bgemm(_code(A.dtype), A.data_ptr(), ctypes.byref(ma), _code(B.dtype), B.data_ptr(), ctypes.byref(mb),
-                         _code(C.dtype), C.data_ptr(), ctypes.byref(mc), _p(bias), alpha, nb, nh, M, N, Kd, int(round_a),
+    ma, mb, mc = _lib.Mat(*sa), _lib.Mat(*sb), _lib.Mat(*sc)
+    check(_L().dfd_bgemm(_dt(A), _p(A, strided=True), ctypes.byref(ma), _dt(B), _p(B, strided=True), ctypes.byref(mb),
+                         _dt(C), _p(C, strided=True), ctypes.byref(mc), _p(bias), alpha, nb, nh, M, N, Kd, int(round_a),
                          int(round_b), _stream()), "dfd_bgemm", f"nb={nb} nh={nh} M={M} N={N} K={Kd}")
 
 
@@ -1462,26 +1481,22 @@ def attn_softmax_fwd(S: torch.Tensor, th: tuple | None):
     """S [B,H,Nq,Nk] f32 -> (P, T2); th = (w1 [H,H], b1 [H], w2 [H,H], b2 [H]) or None (then T2 is P)."""
     B, H, Nq, Nk = S.shape
     P = torch.empty_like(S)
-    if th is None:
-        check(_L().dfd_attn_softmax_fwd(_p(S), None, None, None, None, _p(P), None, B, H, Nq, Nk, _stream()), "dfd_attn_softmax_fwd")
-        return P, P
-    T2 = torch.empty_like(S)
-    w1, b1, w2, b2 = th
+    T2 = torch.empty_like(S) if th is not None else None
+    w1, b1, w2, b2 = th if th is not None else (None,) * 4
     check(_L().dfd_attn_softmax_fwd(_p(S), _p(w1), _p(b1), _p(w2), _p(b2), _p(P), _p(T2), B, H, Nq, Nk, _stream()),
           "dfd_attn_softmax_fwd")
-    return P, T2
+    return P, (T2 if th is not None else P)
 
 
-def attn_softmax_bwd(dT2: torch.Tensor, P: torch.Tensor, th: tuple | None):
-    """-> (dT1 | None, dS)"""
+def attn_softmax_bwd(dT2: torch.Tensor, P: torch.Tensor, th: tuple | None, out: torch.Tensor | None = None):
+    """-> (dT1 | None, dS).  out: a contiguous destination for dS of P's shape (e.g. the leading rows of a padded buffer)."""
     B, H, Nq, Nk = P.shape
-    dS = torch.empty_like(P)
-    if th is None:
-        check(_L().dfd_attn_softmax_bwd(_p(dT2), _p(P), None, None, None, _p(dS), B, H, Nq, Nk, _stream()), "dfd_attn_softmax_bwd")
-        return None, dS
-    dT1 = torch.empty_like(P)
-    check(_L().dfd_attn_softmax_bwd(_p(dT2), _p(P), _p(th[0]), _p(th[2]), _p(dT1), _p(dS), B, H, Nq, Nk, _stream()),
-          "dfd_attn_softmax_bwd")
+    if out is not None and (out.shape != P.shape or out.dtype != P.dtype):
+        raise ValueError(f"attn_softmax_bwd: bad destination {tuple(out.shape)} {out.dtype} for {tuple(P.shape)} {P.dtype}")
+    dS = torch.empty_like(P) if out is None else out
+    dT1 = torch.empty_like(P) if th is not None else None
+    w1, _, w2, _ = th if th is not None else (None,) * 4
+    check(_L().dfd_attn_softmax_bwd(_p(dT2), _p(P), _p(w1), _p(w2), _p(dT1), _p(dS), B, H, Nq, Nk, _stream()), "dfd_attn_softmax_bwd")
     return dT1, dS
 
 
@@ -1662,6 +1677,33 @@ def relpos_bias_bwd(dfull: torch.Tensor, table: torch.Tensor, idx: torch.Tensor,
     return dtable
 
 
+def _launch_jobs(name: str, Job, rows: list) -> None:
+    """One launch of the batched entry point `name` over a ctypes array of `Job`, one per row of constructor arguments;
+    a tensor in a row goes through the gate.  No rows: no launch."""
+    if rows:
+        arr = (Job * len(rows))(*(Job(*(_p(v) if isinstance(v, torch.Tensor) else v for v in row)) for row in rows))
+        check(getattr(_L(), name)(arr, len(rows), _stream()), name)
+
+
+def coord_tables_fwd(cmlp: list, relpos: list) -> None:
+    """Every coordinate MLP of a level in one launch, then every relative-position bias built from their tables in one.
+    cmlp: (coords [T, 2], w0 [Hd, 2], b0 [Hd], w2 [D, Hd], table [T, D]) f32, table = relu(coords w0^T + b0) w2^T;
+    relpos: (table [T, H], idx int32, full [H, S, S], n_local, n_global) as relpos_bias_fwd."""
+    _launch_jobs("dfd_coord_mlp_fwd_multi", _lib.CmlpJob,
+                 [(c, w0, b0, w2, tab, None, None, None, None, c.shape[0], w2.shape[0], w0.shape[0], 0) for c, w0, b0, w2, tab in cmlp])
+    _launch_jobs("dfd_relpos_bias_fwd_multi", _lib.RelposJob,
+                 [(tab, idx, full, None, None, tab.shape[1], tab.shape[0], nl, ng) for tab, idx, full, nl, ng in relpos])
+
+
+def coord_tables_bwd(relpos: list, cmlp: list) -> None:
+    """The backward of coord_tables_fwd, bias first.  relpos: (table, idx, dfull, dtable [T, H], n_local, n_global);
+    cmlp: (coords, w0, b0, w2, dtable [T, D], dw0 | None, db0 | None, dw2 | None)."""
+    _launch_jobs("dfd_relpos_bias_bwd_multi", _lib.RelposJob,
+                 [(tab, idx, None, g, dtab, tab.shape[1], tab.shape[0], nl, ng) for tab, idx, g, dtab, nl, ng in relpos])
+    _launch_jobs("dfd_coord_mlp_bwd_multi", _lib.CmlpJob,
+                 [(c, w0, b0, w2, None, g, dw0, db0, dw2, c.shape[0], w2.shape[0], w0.shape[0], 0) for c, w0, b0, w2, g, dw0, db0, dw2 in cmlp])
+
+
 def axpby(x: torch.Tensor, y: torch.Tensor | None, a: float = 1.0, b: float = 1.0, a_dev: torch.Tensor | None = None,
           out: torch.Tensor | None = None) -> torch.Tensor:
     """(a * a_dev[0]) * x + b * y on f32 tensors (into `out`, e.g. a gradient-arena slot, when given)."""
@@ -1685,8 +1727,7 @@ class DeviceRng:
         with torch.inference_mode(False):
             self.state = torch.zeros(2, dtype=torch.int64, device=device)
         self.reseed(seed)
-        self._counter_key: tuple = ()
-        self._counter_table: torch.Tensor | None = None
+        self._counters = AddressTable([])
 
     @staticmethod
     def mix_seed(seed: int, rank: int) -> int:
@@ -1715,13 +1756,12 @@ class DeviceRng:
 
     def tick(self, counters: list[torch.Tensor]) -> None:
         """One launch: every int64 counter += 1 (BatchNorm.num_batches_tracked) and the Philox offset += 1."""
-        key = tuple(c.data_ptr() for c in counters)
-        if key != self._counter_key:
-            self._counter_key = key
+        if not self._counters.valid_for(counters):
+            table = self._counters = AddressTable(counters)
             with torch.inference_mode(False):
-                self._counter_table = torch.tensor(list(key), dtype=torch.int64).to(self.state.device) if key else None
-        journal_note(counters)
-        check(_L().dfd_step_tick(_p(self._counter_table), len(key), _p(self.state), _stream()), "dfd_step_tick")
+                table.dev = torch.tensor(table.ptrs, dtype=torch.int64).to(self.state.device) if counters else None
+        self._counters.note()
+        check(_L().dfd_step_tick(_p(self._counters.dev), len(counters), _p(self.state), _stream()), "dfd_step_tick")
 
 
 # ------------------------------------------------------------------ measurement hook

@@ -78,7 +78,7 @@ class HipAdamW(torch.optim.Optimizer):
         if limit is not None:
             self._check_clip_groups()
             self._alloc_clip()
-        self._tables: dict[int, tuple[tuple[int, ...], torch.Tensor, torch.Tensor]] = {}
+        self._tables: dict[int, K.AddressTable] = {}
         self._hp: dict[int, torch.Tensor] = {}
         self._shared_step: dict[int, torch.Tensor] = {}
         # gradients of the trainable parameters live at fixed addresses (see arena.py): the
@@ -156,21 +156,19 @@ class HipAdamW(torch.optim.Optimizer):
         if self.arena is not None:
             self.arena.reset()
 
-    def _table(self, gi: int, entries: list[tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]]) -> torch.Tensor:
-        key = tuple(t.data_ptr() for e in entries for t in e)
+    def _table(self, gi: int, entries: list[tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]]) -> K.AddressTable:
+        flat = [t for e in entries for t in e]
         cached = self._tables.get(gi)
-        if cached is not None and cached[0] == key:
-            return cached[2]
+        if cached is not None and cached.valid_for(flat):
+            return cached
         rows = []
         for p, g, m, v in entries:
             base = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr())
             for off in range(0, p.numel(), _CHUNK):
                 rows.append([b + 4 * off for b in base] + [min(_CHUNK, p.numel() - off)])
-        host = torch.tensor(rows, dtype=torch.int64).pin_memory()
-        dev = cached[2] if cached is not None and cached[2].shape == host.shape else torch.empty_like(host, device=entries[0][0].device)
-        dev.copy_(host, non_blocking=True)          # pinned + async: legal under stream capture
-        self._tables[gi] = (key, host, dev)
-        return dev
+        table = self._tables[gi] = K.AddressTable(flat)
+        table.upload(rows, entries[0][0].device, cached)
+        return table
 
     def _ensure_state(self, p: torch.Tensor) -> dict:
         st = self.state[p]
@@ -244,7 +242,6 @@ class HipAdamW(torch.optim.Optimizer):
                 continue
             if gi not in self._hp:
                 raise RuntimeError("HipAdamW.step() under stream capture needs prepare_step() before the capture")
-            K.journal_note([t for e in entries for t in e])     # the table carries these addresses
             if self._clip_limit is None:
                 K.adamw_step(self._table(gi, entries), self._hp[gi])
             else:
@@ -254,11 +251,10 @@ class HipAdamW(torch.optim.Optimizer):
             if self._clip_buffers is None:
                 raise RuntimeError("HipAdamW clipping buffers are missing: the parameters were not on a HIP device at set_clip()")
             partials, cfg, state = self._clip_buffers
-            K.journal_note([partials, cfg, state])
             off = 0
             for table, _ in work:
-                K.grad_sumsq(table, partials[off:off + table.shape[0]])
-                off += table.shape[0]
+                K.grad_sumsq(table, partials[off:off + table.dev.shape[0]])
+                off += table.dev.shape[0]
             K.grad_clip_finish(partials[:off], work[0][1], cfg, state)
             for table, hp in work:
                 K.adamw_step_clip(table, hp, cfg, state)

@@ -214,17 +214,7 @@ def attn_core_bwd(gO, q, k, v, S, P, T2, table, idx, th, geo: AttnGeom, need_tab
         K.bgemm(T2, (H * L, L, 1, Nk), gO, (Nq * H * dv, dv, H * dv, 1), dV, (Nk * H * dv, dv, H * dv, 1), B, H, Nk, dv, Nq)
     # dS gets room for the two-stage row sum that turns it into the bias gradient
     dS_buf = torch.empty((_partial_rows(B), H, Nq, Nk), dtype=torch.float32, device=dev)
-    dS = dS_buf[:B]
-    dT1 = torch.empty_like(dT2) if th is not None else None
-    from ._lib import check  # local: the front end takes whole tensors, here dS is a prefix view
-
-    lib = K._L()
-    if th is None:
-        check(lib.dfd_attn_softmax_bwd(dT2.data_ptr(), P.data_ptr(), None, None, None, dS.data_ptr(), B, H, Nq, Nk, K._stream()),
-              "dfd_attn_softmax_bwd")
-    else:
-        check(lib.dfd_attn_softmax_bwd(dT2.data_ptr(), P.data_ptr(), th[0].data_ptr(), th[2].data_ptr(), dT1.data_ptr(),
-                                       dS.data_ptr(), B, H, Nq, Nk, K._stream()), "dfd_attn_softmax_bwd")
+    dT1, dS = K.attn_softmax_bwd(dT2, P, th, out=dS_buf[:B])
     if mfma:
         dQ = K.attn_apply(dS, k, q.shape, H, alpha=geo.scale)
         dK = K.attn_apply(dS, q, k.shape, H, alpha=geo.scale, transpose=True)

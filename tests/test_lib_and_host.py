@@ -37,6 +37,30 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
     assert lib.dfd_version() >= 100            # a call that needs no GPU
 
 
+def test_only_the_front_end_loads_and_calls_the_library():
+    """kernels.py is where device addresses are checked and journalled (its gate `_p` and `AddressTable`): no other module of the
+    package fetches the library (`_L()`, `_lib.load()`) or calls one of its entry points."""
+    import ast
+
+    package = ROOT / "deepfakedetection_amd"
+    found = []
+    for path in sorted(package.rglob("*.py")):
+        if path == package / "kernels.py":
+            continue
+        for node in ast.walk(ast.parse(path.read_text())):
+            if not isinstance(node, ast.Call):
+                continue
+            fn = node.func
+            name = fn.attr if isinstance(fn, ast.Attribute) else getattr(fn, "id", "")
+            loads = isinstance(fn, ast.Attribute) and name == "load" and isinstance(fn.value, ast.Name) and fn.value.id == "_lib"
+            if (isinstance(fn, ast.Attribute) and name.startswith("dfd_")) or name == "_L" or loads:
+                found.append(f"{path.relative_to(ROOT)}:{node.lineno} {name}")
+    assert not found, found
+    calls = [n for n in ast.walk(ast.parse((package / "kernels.py").read_text()))
+             if isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and n.func.attr.startswith("dfd_")]
+    assert len(calls) > 100                         # the walk does see the entry-point calls where they are allowed
+
+
 def test_bad_arguments_are_rejected_without_a_gpu(lib):
     assert lib.dfd_bn_finalize(None, 0, 0, 0.0, None, None, None, None, 0.1, 1e-5, None, None) == -1     # DFD_EINVAL
     assert lib.dfd_adamw_step(None, 0, None, None) == -1
