@@ -21,8 +21,7 @@ import math
 import torch
 from torch import nn
 
-from .efficientnet import compute_dtype
-from .functions import BNRef, bn_eval_batch
+from .network import HipNetwork, _bnref, compute_dtype
 from .vit_functions import (AttentionCtx, AttentionFunction, AttnGeom, ConvMlpCtx, ConvMlpFunction, ConvStemCtx, ConvStemFunction,
                             DenseConvBNFunction, DenseConvCtx, DownsampleCtx, DownsampleFunction, TailCtx, TailFunction)
 from ._lib import ACT_GELU
@@ -38,10 +37,6 @@ _RATIOS = {
 _NUM_VIT = {"s0": 2, "s1": 2, "s2": 4, "l": 6}
 _DROP_PATH = {"s0": 0.0, "s1": 0.0, "s2": 0.02, "l": 0.1}
 _EPS = 1e-5
-
-
-def _bnref(bn: nn.BatchNorm2d) -> BNRef:
-    return BNRef(bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps)
 
 
 class ConvNorm(nn.Module):
@@ -261,7 +256,7 @@ class HipStem4(nn.Module):
         self.conv2 = ConvNorm(cout // 2, cout, 3, 2)
 
 
-class HipEfficientFormerV2(nn.Module):
+class HipEfficientFormerV2(HipNetwork):
     """EfficientFormerV2-{S0,S1,S2,L} whose forward/backward run on the MI355X kernels."""
 
     def __init__(self, variant: str = "s1", num_classes: int = 1000, img_size: int = 224, drop_rate: float = 0.0,
@@ -295,34 +290,17 @@ class HipEfficientFormerV2(nn.Module):
                 nn.init.trunc_normal_(m.weight, std=0.02)
                 nn.init.zeros_(m.bias)
 
-    def to(self, *args, **kwargs):
-        """`.to(memory_format=torch.channels_last)` (trainers/efficientformer_v2.py:328) is accepted and ignored for the
-        PARAMETERS (kernels read torch's default weight layouts; activations are NHWC inside the engine)."""
-        kwargs.pop("memory_format", None)
-        args = tuple(a for a in args if not isinstance(a, torch.memory_format))
-        return super().to(*args, **kwargs) if (args or kwargs) else self
-
-    def rng(self, device: torch.device):
-        from . import kernels as K
-
-        cur = self.__dict__.get("_rng_obj")
-        if cur is None or cur.state.device != device:
-            cur = self.__dict__["_rng_obj"] = K.DeviceRng(device)
-        return cur
-
     def dp_cut_modules(self) -> list[nn.Module]:
         """Where a replayed data-parallel backward may be cut into segments (graph_step.plan_cuts): the four stages."""
         return list(self.stages)
 
     def forward_features_nhwc(self, x: torch.Tensor, counters: list | None = None) -> torch.Tensor:
-        if not x.is_cuda:
-            raise RuntimeError("HipEfficientFormerV2 runs on a HIP device only (no CPU fallback); move the input with .to('cuda')")
+        xh = self.nhwc_input(x)
         if x.shape[2] != self.img_size or x.shape[3] != self.img_size:
             raise ValueError(f"EfficientFormerV2 was built for {self.img_size}x{self.img_size} inputs (attention bias tables "
                              f"depend on the resolution), got {tuple(x.shape[2:])}")
         dt = compute_dtype()
         tr = self.training
-        xh = x.detach().float().contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
         c1, c2 = self.stem.conv1, self.stem.conv2
         h = ConvStemFunction.apply(xh, *c1.tensors(), ConvStemCtx(2, 1, _bnref(c1.bn), dt, tr, ACT_GELU, counters))
         h = DenseConvBNFunction.apply(h, *c2.tensors(), DenseConvCtx(3, 2, _bnref(c2.bn), tr, ACT_GELU, counters))
@@ -334,21 +312,15 @@ class HipEfficientFormerV2(nn.Module):
 
     def _derived_weights(self, dt: torch.dtype) -> dict:
         """{weight.data_ptr(): (w_nk, w_kn)} for every 1x1 convolution of the network, refreshed by ONE batched launch per
-        forward pass (kernels.DerivedWeights); one cache entry per activation dtype, never freed by a train / eval switch
-        (a captured hipGraph holds raw pointers into it)."""
+        forward pass (HipNetwork._derived)."""
         from . import kernels as K
 
         weights = [m.conv.weight for m in self.modules() if isinstance(m, ConvNorm) and m.conv.kernel_size == (1, 1)]
-        caches = self.__dict__.setdefault("_derived_caches", {})
-        cache = caches.get(dt)
-        if cache is None or not cache.valid_for(weights, dt):
-            with torch.inference_mode(False):
-                cache = caches[dt] = K.DerivedWeights([(w, True, True, False) for w in weights], dt)
-        cache.refresh()
-        return {w.data_ptr(): pair for w, pair in zip(weights, cache.out)}
+        pairs = self._derived(dt, weights, lambda: K.DerivedWeights([(w, True, True, False) for w in weights], dt))
+        return {w.data_ptr(): pair for w, pair in zip(weights, pairs)}
 
     def forward(self, x: torch.Tensor, dropout_u: torch.Tensor | None = None) -> torch.Tensor:
-        with bn_eval_batch(self.__dict__, (self.training, compute_dtype())):     # eval-mode BN blocks: one batched launch per pass
+        with self.pass_scope():
             return self._forward(x, dropout_u)
 
     def _forward(self, x: torch.Tensor, dropout_u: torch.Tensor | None = None) -> torch.Tensor:
@@ -360,8 +332,7 @@ class HipEfficientFormerV2(nn.Module):
         cfg = TailCtx(_bnref(self.norm), self.drop_rate, self.training, counters)
         out = TailFunction.apply(h, self.norm.weight, self.norm.bias, self.head.weight, self.head.bias, self.head_dist.weight,
                                  self.head_dist.bias, u, cfg)
-        if self.training:
-            self.rng(h.device).tick(counters)
+        self.end_pass(counters, h.device)
         return out
 
 

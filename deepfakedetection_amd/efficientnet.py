@@ -21,15 +21,14 @@ without autocast: trainers/efficientnet.py:249-254, orchestrator.py:587-590).
 from __future__ import annotations
 
 import math
-import warnings
 
 import torch
 from torch import nn
 
-from . import functions as F_
 from .arch import BlockPlan, NetPlan, efficientnet_plan
-from .functions import (BNRef, HeadConvFunction, HeadCtx, HeadFunction, HeadTailEvalFunction, MBConvCtx, MBConvFunction,
+from .functions import (HeadConvFunction, HeadCtx, HeadFunction, HeadTailEvalFunction, MBConvCtx, MBConvFunction,
                         StemCtx, StemFunction)
+from .network import HipNetwork, _bnref, compute_dtype
 
 _default_rng: dict = {}
 
@@ -51,28 +50,6 @@ _TIMM_IR_NAMES = dict(expand="conv_pw", expand_bn="bn1", dw="conv_dw", dw_bn="bn
                       se_reduce="se.conv_reduce", se_expand="se.conv_expand", project="conv_pwl", project_bn="bn3")
 _TIMM_DS_NAMES = dict(dw="conv_dw", dw_bn="bn1", se_reduce="se.conv_reduce", se_expand="se.conv_expand",
                       project="conv_pw", project_bn="bn2")
-
-
-def _bnref(bn: nn.BatchNorm2d) -> BNRef:
-    pre = None
-    held = bn.__dict__.get("_dfd_eval")               # (kernels.EvalBNStates, this layer's block), set by the owning network
-    if held is not None and held[0].fresh and not bn.training:
-        pre = held[1]
-    return BNRef(bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps, pre)
-
-
-def compute_dtype(device_type: str = "cuda") -> torch.dtype:
-    """bf16 inside an autocast region, f32 outside."""
-    try:
-        enabled = torch.is_autocast_enabled(device_type)
-    except TypeError:  # older signature
-        enabled = torch.is_autocast_enabled()
-    if not enabled:
-        return torch.float32
-    amp = torch.get_autocast_dtype(device_type) if hasattr(torch, "get_autocast_dtype") else torch.get_autocast_gpu_dtype()
-    if amp != torch.bfloat16:
-        warnings.warn("dfd HIP engine computes autocast regions in bf16 (fp16 autocast requested)", stacklevel=3)
-    return torch.bfloat16
 
 
 class _SEParams(nn.Module):
@@ -144,7 +121,7 @@ class HipMBConv(nn.Module):
                                     see.weight, see.bias, proj.weight, proj_bn.weight, proj_bn.bias, row_scale, cfg)
 
 
-class HipEfficientNet(nn.Module):
+class HipEfficientNet(HipNetwork):
     """EfficientNet-{b0..b4} whose forward/backward run on the MI355X kernels."""
 
     def __init__(self, variant: str = "b0", flavour: str = "timm", num_classes: int = 1000,
@@ -198,14 +175,6 @@ class HipEfficientNet(nn.Module):
                 nn.init.uniform_(m.weight, -bound, bound)
                 nn.init.zeros_(m.bias)
 
-    def to(self, *args, **kwargs):
-        """`.to(memory_format=torch.channels_last)` (trainers/efficientnet.py:409) is accepted and
-        ignored for the PARAMETERS: the kernels read weights in torch's default [O][I][kh][kw]
-        layout, while activations are NHWC inside the engine whatever the input's strides."""
-        kwargs.pop("memory_format", None)
-        args = tuple(a for a in args if not isinstance(a, torch.memory_format))
-        return super().to(*args, **kwargs) if (args or kwargs) else self
-
     # -- named parts, resolved at call time (the reference swaps `_fc` after construction)
     def _parts(self):
         if self.flavour == "lukemelas":
@@ -216,34 +185,23 @@ class HipEfficientNet(nn.Module):
     def block_list(self) -> list[HipMBConv]:
         return self._parts()[2]
 
-    def rng(self, device: torch.device):
-        """This network's Philox state on `device` (created on first use, seeded from torch.initial_seed())."""
-        from . import kernels as K
-
-        cur = self.__dict__.get("_rng_obj")
-        if cur is None or cur.state.device != device:
-            cur = self.__dict__["_rng_obj"] = K.DeviceRng(device)
-        return cur
-
     def dp_cut_modules(self) -> list[nn.Module]:
         """Modules after which a replayed data-parallel backward may be cut into segments (graph_step.plan_cuts): the MBConv blocks —
         one tensor in, one tensor out, in forward order."""
         return list(self.block_list())
 
-    def forward_features_nhwc(self, x: torch.Tensor, drop_masks=None, counters: list | None = None) -> torch.Tensor:
+    def forward_features_nhwc(self, x: torch.Tensor, drop_masks=None, counters: list | None = None):
+        """-> (the last block's output, the head convolution's derived (w_nk, w_kn) pair of this pass)."""
         stem, stem_bn, blocks, _, _, _ = self._parts()
-        if not x.is_cuda:
-            raise RuntimeError("HipEfficientNet runs on a HIP device only (no CPU fallback); move the input with .to('cuda')")
+        xh = self.nhwc_input(x)
         dt = compute_dtype()
-        xh = x.detach().float().contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
         h = StemFunction.apply(xh, stem.weight, stem_bn.weight, stem_bn.bias,
                                StemCtx(self.plan.stem, _bnref(stem_bn), dt, self.training, counters))
         derived = self._derived_weights(dt)
         rng = self.rng(x.device) if self.training else None
         for i, blk in enumerate(blocks):
             h = blk(h, derived[i], rng, counters) if drop_masks is None else blk.run(h, drop_masks[i], derived[i], counters)
-        self._head_derived = derived[len(blocks)]
-        return h
+        return h, derived[len(blocks)]
 
     def _derived_weights(self, dt: torch.dtype) -> list:
         """One batched launch per forward refreshes every derived weight of the network (1x1 conv weights in
@@ -262,68 +220,39 @@ class HipEfficientNet(nn.Module):
             items.append((blk.part("se_expand").weight, False, True, True))
             layout.append(p.expand)
         items.append((head.weight, True, True, False))
-        # one cache entry PER DTYPE: the trainer alternates bf16 training and f32 evaluation, and a captured
-        # hipGraph holds raw pointers into its entry, so an entry is never freed by a train/eval switch; the
-        # buffers are ordinary (non-inference) tensors even when first built under torch.inference_mode()
-        caches = self.__dict__.setdefault("_derived_caches", {})
-        cache = caches.get(dt)
-        if cache is None or not cache.valid_for([it[0] for it in items], dt):
-            with torch.inference_mode(False):
-                cache = caches[dt] = K.DerivedWeights(items, dt)
-        cache.refresh()
+        pairs = self._derived(dt, [it[0] for it in items], lambda: K.DerivedWeights(items, dt))
         out, at = [], 0
         for has_exp in layout:
             exp = None
             if has_exp:
-                exp = cache.out[at]
+                exp = pairs[at]
                 at += 1
-            proj = cache.out[at]
-            w2t = cache.out[at + 1][1]
+            proj = pairs[at]
+            w2t = pairs[at + 1][1]
             at += 2
             out.append((exp, proj, w2t))
-        out.append(cache.out[at])
+        out.append(pairs[at])
         return out
-
-    def _eval_bn_states(self):
-        """Eval / inference forward: every BatchNorm's coefficient block from one batched launch (kernels.EvalBNStates)."""
-        from . import kernels as K
-
-        bns = [m for m in self.modules() if isinstance(m, nn.BatchNorm2d)]
-        cache = self.__dict__.get("_eval_bn_cache")
-        if cache is None or not cache.valid_for(bns):
-            with torch.inference_mode(False):
-                cache = self.__dict__["_eval_bn_cache"] = K.EvalBNStates(bns)
-            for bn, st in zip(bns, cache.states):
-                bn.__dict__["_dfd_eval"] = (cache, st)
-        cache.refresh()
-        return cache
 
     def forward(self, x: torch.Tensor, drop_masks=None, dropout_u: torch.Tensor | None = None) -> torch.Tensor:
         """drop_masks / dropout_u let a test inject the stochastic-depth masks (already
         1/keep scaled, one [N] tensor or None per block) and the dropout uniforms."""
-        if not self.training and x.is_cuda:
-            states = self._eval_bn_states()
-            states.fresh = True
-            try:
-                return self._forward(x, drop_masks, dropout_u)
-            finally:
-                states.fresh = False
-        return self._forward(x, drop_masks, dropout_u)
+        with self.pass_scope():
+            return self._forward(x, drop_masks, dropout_u)
 
     def _forward(self, x: torch.Tensor, drop_masks=None, dropout_u: torch.Tensor | None = None) -> torch.Tensor:
         _, _, _, head, head_bn, fc = self._parts()
         counters: list = []                 # owned by this call: num_batches_tracked of every BatchNorm that ran
-        h = self.forward_features_nhwc(x, drop_masks, counters)
+        h, head_derived = self.forward_features_nhwc(x, drop_masks, counters)
         u = dropout_u
         if u is None and self.training and self.drop_rate > 0 and drop_masks is None:
             u = self.rng(h.device).uniform(h.shape[0] * head.out_channels, stream_id=1 << 20).view(h.shape[0], head.out_channels)
         if head._forward_hooks or head._forward_pre_hooks:
             out = self._hooked_head(h, head, head_bn, fc)
         else:
-            cfg = HeadCtx(_bnref(head_bn), self.drop_rate, self.training, self._head_derived, counters)
+            cfg = HeadCtx(_bnref(head_bn), self.drop_rate, self.training, head_derived, counters)
             out = HeadFunction.apply(h, head.weight, head_bn.weight, head_bn.bias, fc.weight, fc.bias, u, cfg)
-        if self.training:
-            self.rng(h.device).tick(counters)       # one launch: every counter += 1, Philox offset += 1
+        self.end_pass(counters, h.device)
         return out
 
 
@@ -368,4 +297,4 @@ def build_efficientnet(name: str, num_classes: int) -> HipEfficientNet:
     return HipEfficientNet(variant, flavour, num_classes)
 
 
-__all__ = ["HipEfficientNet", "HipMBConv", "build_efficientnet", "compute_dtype"]
+__all__ = ["HipEfficientNet", "HipMBConv", "build_efficientnet"]

@@ -18,10 +18,9 @@ import torch
 from torch import nn
 
 from ._lib import ACT_RELU
-from .efficientnet import compute_dtype
 from .fastervit_functions import (AttnSpec, ConvBlockCtx, ConvBlockFunction, FVDownsampleFunction, HATCtx, HATFunction,
                                   TokenInitFunction, derived_weights)
-from .functions import BNRef, bn_eval_batch
+from .network import HipNetwork, _bnref, compute_dtype
 from .vit_functions import ConvStemCtx, ConvStemFunction, DenseConvBNFunction, DenseConvCtx, TailCtx, TailFunction
 
 _CONFIGS = {
@@ -31,10 +30,6 @@ _CONFIGS = {
     "3": ((3, 3, 12, 5), (2, 4, 8, 16), 128, 64, 0.3, 1e-5),
 }
 WINDOW, CT_SIZE, MLP_RATIO = 7, 2, 4
-
-
-def _bnref(bn: nn.BatchNorm2d) -> BNRef:
-    return BNRef(bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps)
 
 
 class PosEmbMLPSwinv1D(nn.Module):
@@ -353,7 +348,7 @@ class HipPatchEmbed(nn.Module):
             nn.Conv2d(in_dim, dim, 3, 2, 1, bias=False), nn.BatchNorm2d(dim, eps=1e-4), nn.ReLU())
 
 
-class HipFasterViT(nn.Module):
+class HipFasterViT(HipNetwork):
     """FasterViT-{0,1,2,3} at 224 px (7x7 windows) whose forward/backward run on the MI355X kernels."""
 
     def __init__(self, variant: str = "0", num_classes: int = 1000, resolution: int = 224, drop_path_rate: float | None = None,
@@ -389,54 +384,29 @@ class HipFasterViT(nn.Module):
                 if m.bias is not None:
                     nn.init.zeros_(m.bias)
 
-    def to(self, *args, **kwargs):
-        kwargs.pop("memory_format", None)
-        args = tuple(a for a in args if not isinstance(a, torch.memory_format))
-        return super().to(*args, **kwargs) if (args or kwargs) else self
-
-    def rng(self, device: torch.device):
-        from . import kernels as K
-
-        cur = self.__dict__.get("_rng_obj")
-        if cur is None or cur.state.device != device:
-            cur = self.__dict__["_rng_obj"] = K.DeviceRng(device)
-        return cur
-
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if not x.is_cuda:
-            raise RuntimeError("HipFasterViT runs on a HIP device only (no CPU fallback); move the input with .to('cuda')")
-        # the coefficient blocks of every eval-mode BatchNorm and of every Linear's identity statistics (bias, LayerScale):
-        # one batched launch per pass instead of ~70 small ones
-        with bn_eval_batch(self.__dict__, (self.training, compute_dtype())), derived_weights(self._derived_weights(compute_dtype())):
-            return self._forward(x)
+        # in the pass scope also the coefficient blocks of every Linear's identity statistics (bias, LayerScale) are batched:
+        # one launch per pass instead of ~70 small ones
+        with self.pass_scope():
+            return self._forward(x, batched=True)
 
     def _derived_weights(self, dt: torch.dtype) -> dict:
         """{weight.data_ptr(): (w_nk, w_kn)} for the qkv / proj / fc1 / fc2 Linear of every attention block, refreshed by ONE
-        batched launch per forward pass (kernels.DerivedWeights); one cache entry per activation dtype, never freed (a
-        captured hipGraph holds raw pointers into it).  With `fp8_weights` the entries of the weights with K % 128 == 0 are
-        (kernels.MxWeight, dequantised [K][N] copy) from one batched quantisation launch (kernels.MxWeights) instead."""
+        batched launch per forward pass (HipNetwork._derived).  With `fp8_weights` the entries of the weights with K % 128 == 0
+        are (kernels.MxWeight, dequantised [K][N] copy) from one batched quantisation launch (kernels.MxWeights) instead."""
         from . import kernels as K
 
         weights = [lin.weight for m in self.modules() if isinstance(m, (WindowAttention, Mlp))
                    for lin in ((m.qkv, m.proj) if isinstance(m, WindowAttention) else (m.fc1, m.fc2))]
         fp8 = [w for w in weights if self.fp8_weights and dt == torch.bfloat16 and w.shape[1] % 128 == 0]
         plain = [w for w in weights if not any(w is q for q in fp8)]
-        caches = self.__dict__.setdefault("_derived_caches", {})
         table: dict = {}
         if plain:
-            cache = caches.get(dt)
-            if cache is None or not cache.valid_for(plain, dt):
-                with torch.inference_mode(False):
-                    cache = caches[dt] = K.DerivedWeights([(w, True, True, False) for w in plain], dt)
-            cache.refresh()
-            table.update({w.data_ptr(): pair for w, pair in zip(plain, cache.out)})
+            pairs = self._derived(dt, plain, lambda: K.DerivedWeights([(w, True, True, False) for w in plain], dt))
+            table.update({w.data_ptr(): pair for w, pair in zip(plain, pairs)})
         if fp8:
-            cache = caches.get(("mx", dt))
-            if cache is None or not cache.valid_for(fp8, dt):
-                with torch.inference_mode(False):
-                    cache = caches[("mx", dt)] = K.MxWeights(fp8, dt)
-            cache.refresh()
-            table.update({w.data_ptr(): pair for w, pair in zip(fp8, cache.out)})
+            pairs = self._derived(dt, fp8, lambda: K.MxWeights(fp8, dt), mx=True)
+            table.update({w.data_ptr(): pair for w, pair in zip(fp8, pairs)})
         return table
 
     def dp_cut_modules(self) -> list[nn.Module]:
@@ -444,23 +414,25 @@ class HipFasterViT(nn.Module):
         one tensor out; the blocks inside levels 2-3 carry a (windows, carrier tokens) pair and are not cut points)."""
         return list(self.levels)
 
-    def _forward(self, x: torch.Tensor) -> torch.Tensor:
+    def _forward(self, x: torch.Tensor, batched: bool = False) -> torch.Tensor:
+        """batched: the Linear layers' derived weights come from one launch for the network (forward()); otherwise each layer
+        prepares its own."""
+        xh = self.nhwc_input(x)
         if x.shape[2] != self.resolution or x.shape[3] != self.resolution:
             raise ValueError(f"FasterViT was built for {self.resolution}x{self.resolution} inputs, got {tuple(x.shape[2:])}")
         dt = compute_dtype()
         tr = self.training
         counters: list = []
-        xh = x.detach().float().contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
-        c = self.patch_embed.conv_down
-        h = ConvStemFunction.apply(xh, c[0].weight, None, c[1].weight, c[1].bias, ConvStemCtx(2, 1, _bnref(c[1]), dt, tr, ACT_RELU, counters))
-        h = DenseConvBNFunction.apply(h, c[3].weight, None, c[4].weight, c[4].bias, DenseConvCtx(3, 2, _bnref(c[4]), tr, ACT_RELU, counters))
-        rng = self.rng(x.device) if tr else None
-        for level in self.levels:
-            h = level(h, rng, counters)
-        cfg = TailCtx(_bnref(self.norm), 0.0, tr, counters)
-        out = TailFunction.apply(h, self.norm.weight, self.norm.bias, self.head.weight, self.head.bias, None, None, None, cfg)
-        if tr:
-            self.rng(h.device).tick(counters)
+        with derived_weights(self._derived_weights(dt) if batched else None):
+            c = self.patch_embed.conv_down
+            h = ConvStemFunction.apply(xh, c[0].weight, None, c[1].weight, c[1].bias, ConvStemCtx(2, 1, _bnref(c[1]), dt, tr, ACT_RELU, counters))
+            h = DenseConvBNFunction.apply(h, c[3].weight, None, c[4].weight, c[4].bias, DenseConvCtx(3, 2, _bnref(c[4]), tr, ACT_RELU, counters))
+            rng = self.rng(x.device) if tr else None
+            for level in self.levels:
+                h = level(h, rng, counters)
+            cfg = TailCtx(_bnref(self.norm), 0.0, tr, counters)
+            out = TailFunction.apply(h, self.norm.weight, self.norm.bias, self.head.weight, self.head.bias, None, None, None, cfg)
+        self.end_pass(counters, h.device)
         return out
 
 

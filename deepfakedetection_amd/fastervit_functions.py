@@ -27,7 +27,7 @@ import torch
 from . import kernels as K
 from ._lib import ACT_GELU, ACT_NONE, ACT_RELU
 from .functions import BNRef, _bn_state, _c
-from .vit_functions import _gemm_weight, _partial_rows, _rows, _slot, pwbn_bwd, pwbn_fwd
+from .vit_functions import _gemm_weight, _partial_rows, _prep, _rows, _slot, pwbn_bwd, pwbn_fwd
 
 _ident_cache: dict = {}
 
@@ -157,23 +157,15 @@ _derived_tls = threading.local()
 
 @contextlib.contextmanager
 def derived_weights(table: dict | None):
-    """Inside the block `_prep` serves the (w_nk, w_kn) pairs of `table` ({weight.data_ptr(): pair}, refreshed for the whole
-    network by ONE batched launch per forward pass — kernels.DerivedWeights) instead of one small launch per Linear."""
+    """Inside the block the Linear layers take the (w_nk, w_kn) pairs of `table` ({weight.data_ptr(): pair}, refreshed for the
+    whole network by ONE batched launch per forward pass — kernels.DerivedWeights) instead of one small launch each: the
+    `derived` of vit_functions._prep."""
     prev = getattr(_derived_tls, "table", None)
     _derived_tls.table = table
     try:
         yield
     finally:
         _derived_tls.table = prev
-
-
-def _prep(w: torch.Tensor, dt: torch.dtype):
-    table = getattr(_derived_tls, "table", None)
-    if table is not None:
-        hit = table.get(w.data_ptr())
-        if hit is not None and (isinstance(hit[0], K.MxWeight) or hit[0].dtype == dt):
-            return hit
-    return K.prep_weights(w, dt, True, True)
 
 
 @dataclass
@@ -239,12 +231,13 @@ def attn_sub_fwd(x, P, spec: AttnSpec, ls, row_scale):
     CoordTablesFunction."""
     H = spec.heads
     dt = x.dtype
+    derived = getattr(_derived_tls, "table", None)
     xn, lnst = K.layernorm_fwd(x, P["ln_w"], P["ln_b"], 1e-5)
-    wq_nk, wq_kn = _prep(P["qkv_w"], dt)
+    wq_nk, wq_kn = _prep(P["qkv_w"], dt, derived)
     qkv, yq, stq = lin_fwd(xn, wq_nk, P["qkv_b"])
     bias_full = P["bias"]
     O, Pm = window_attention_fwd(qkv, bias_full, H)
-    wp_nk, wp_kn = _prep(P["proj_w"], dt)
+    wp_nk, wp_kn = _prep(P["proj_w"], dt, derived)
     out, yp, stp = lin_fwd(O, wp_nk, P["proj_b"], ACT_NONE, ls, x, row_scale)
     return out, (x, xn, lnst, qkv, yq, stq, Pm, O, yp, stp, wq_kn, wp_kn, bias_full)
 
@@ -311,12 +304,13 @@ def _to_slot(val: torch.Tensor, param: torch.Tensor, need: bool):
 def mlp_sub_fwd(x, P, ls, row_scale):
     """x + [rs *] [ls *] fc2(GELU(fc1(LN(x)))).  P: ln_w, ln_b, fc1_w, fc1_b, fc2_w, fc2_b."""
     dt = x.dtype
+    derived = getattr(_derived_tls, "table", None)
     xn, lnst = K.layernorm_fwd(x, P["ln_w"], P["ln_b"], 1e-5)
-    w1_nk, w1_kn = _prep(P["fc1_w"], dt)
+    w1_nk, w1_kn = _prep(P["fc1_w"], dt, derived)
     hid = P["fc1_w"].shape[0]
     ones, ref = ident(x.device, hid)
     st1 = _bn_state(None, 0, _rows(xn), ref, ones, P["fc1_b"], False)
-    w2_nk, w2_kn = _prep(P["fc2_w"], dt)
+    w2_nk, w2_kn = _prep(P["fc2_w"], dt, derived)
     C = P["fc2_w"].shape[0]
     ones2, ref2 = ident(x.device, C)
     st2 = _bn_state(None, 0, _rows(xn), ref2, ones2, P["fc2_b"], False, None, None, ls)

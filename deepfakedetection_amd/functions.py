@@ -38,7 +38,6 @@ class BNRef:
     num_batches_tracked: torch.Tensor | None
     momentum: float
     eps: float
-    pre: torch.Tensor | None = None       # eval mode: this layer's coefficient block, already computed (kernels.EvalBNStates)
 
     def params(self, weight: torch.Tensor, bias: torch.Tensor) -> K.BNParams:
         return K.BNParams(weight, bias, self.running_mean, self.running_var, self.momentum, self.eps)
@@ -58,8 +57,11 @@ def _bn_state(parts, nparts, count: int, bn: BNRef, weight, bias, training: bool
             else:
                 bn.num_batches_tracked.add_(1)
         return K.bn_finalize(parts, nparts, count, params)
-    if bn.pre is not None and conv_bias is None and ls is None:
-        return bn.pre
+    return _bn_eval_state(params)
+
+
+def _bn_eval_state(params: K.BNParams) -> torch.Tensor:
+    """Eval-mode coefficient block: from the pass's batch (bn_eval_batch) where one is active, else one small launch."""
     batch = getattr(_bn_batch_tls, "batch", None)
     if batch is not None:
         return batch.request(params)
@@ -417,7 +419,7 @@ class HeadTailEvalFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, w_fc, b_fc, bn: BNRef, gamma, beta):
-        st = K.bn_eval_coeffs(bn.params(gamma, beta))
+        st = _bn_eval_state(bn.params(gamma, beta))
         pooled = K.pool_act(y, st, ACT_SILU)
         logits = K.linear_fwd(pooled, w_fc, b_fc)
         ctx.save_for_backward(y, st, pooled, w_fc)

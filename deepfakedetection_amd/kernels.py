@@ -907,8 +907,8 @@ def mx_gemm(aq: torch.Tensor, ascale: torch.Tensor, w: MxWeight, out_dtype: torc
 
 
 def _bn_eval_jobs(bns: list):
-    """(coefficient blocks [4][C] cut from one buffer, BnEvalJob array, AddressTable) for BatchNorm2d modules or BNParams."""
-    tens = [(bn.weight, bn.bias, getattr(bn, "conv_bias", None), getattr(bn, "ls", None), bn.running_mean, bn.running_var) for bn in bns]
+    """(coefficient blocks [4][C] cut from one buffer, BnEvalJob array, AddressTable) for a list of BNParams."""
+    tens = [(bn.weight, bn.bias, bn.conv_bias, bn.ls, bn.running_mean, bn.running_var) for bn in bns]
     with torch.inference_mode(False):
         flat = torch.empty(sum(4 * ts[4].numel() for ts in tens), dtype=torch.float32, device=tens[0][4].device)
     states, jobs, at = [], (_lib.BnEvalJob * len(bns))(), 0
@@ -964,23 +964,6 @@ class BNEvalBatch:
         elif not self.ok or self.pos != len(self.keys):
             self.keys, self.states, self._jobs, self.table = None, [], None, None      # the pass changed: record again
         self._rec = []
-
-
-class EvalBNStates:
-    """The eval-mode coefficient blocks [4][C] of every BatchNorm of a network, refreshed by one batched launch per
-    forward pass (dfd_bn_eval_coeffs_multi) instead of one small kernel per layer.  `fresh` is raised by the owning
-    network for the duration of its own forward pass: a layer run on its own never sees a stale block."""
-
-    def __init__(self, bns: list) -> None:
-        self.states, self._jobs, self.table = _bn_eval_jobs(bns)
-        self.fresh = False
-
-    def valid_for(self, bns: list) -> bool:
-        return self.table.valid_for([t for bn in bns for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)])
-
-    def refresh(self) -> None:
-        self.table.note()
-        check(_L().dfd_bn_eval_coeffs_multi(self._jobs, len(self._jobs), _stream()), "dfd_bn_eval_coeffs_multi")
 
 
 def pwconv(a: torch.Tensor, pro: Prologue | None, w_nk: torch.Tensor, residual: torch.Tensor | None = None,

@@ -45,10 +45,11 @@ def _rows(t: torch.Tensor) -> int:
 def _prep(w: torch.Tensor, dt: torch.dtype, derived, need_bwd: bool = True):
     """(w_nk, w_kn) of a 1x1 convolution weight [O, I, 1, 1] (or a 2-D GEMM weight) in the activation dtype.
     derived: {weight.data_ptr(): (w_nk, w_kn)} refreshed for the whole network by one batched launch per forward
-    (kernels.DerivedWeights), or None: prepare this layer on the spot."""
+    (kernels.DerivedWeights; w_nk a kernels.MxWeight with FasterViT's fp8 weights), or None: prepare this layer on the spot.
+    An entry of another dtype than `dt` (a table handed on into another autocast region) is not used."""
     if derived is not None:
         hit = derived.get(w.data_ptr())
-        if hit is not None:
+        if hit is not None and (isinstance(hit[0], K.MxWeight) or hit[0].dtype == dt):
             return hit
     return K.prep_weights(w, dt, True, need_bwd)
 

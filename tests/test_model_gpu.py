@@ -474,9 +474,14 @@ def test_grad_cam_hooks_on_head_conv(variant, flavour, attr):
 
 @pytest.mark.gpu
 def test_eval_batchnorm_coefficients_from_one_batched_launch_track_the_buffers():
-    """Eval forward: all 49 BatchNorm coefficient blocks come from one batched launch (kernels.EvalBNStates); the result
-    is the per-layer path's, also after running statistics and affine parameters changed in place (no stale cache),
-    and a block run on its own never uses the network's precomputed blocks."""
+    """Eval forward: all 49 BatchNorm coefficient blocks come from one batched launch (kernels.BNEvalBatch, from the second
+    pass on); the result is the per-layer path's, also after running statistics and affine parameters changed in place
+    (no stale cache), and a block run on its own never uses the network's precomputed blocks."""
+    from deepfakedetection_amd import functions
+
+    def no_active_batch():
+        return getattr(functions._bn_batch_tls, "batch", None) is None
+
     HipEfficientNet, _, _ = _hip()
     torch.manual_seed(5)
     m = HipEfficientNet("b0", "timm", 2).cuda().eval()
@@ -484,6 +489,7 @@ def test_eval_batchnorm_coefficients_from_one_batched_launch_track_the_buffers()
     with torch.inference_mode():
         a, b = m(x), m._forward(x)                        # batched coefficients vs one kernel per layer
         assert torch.equal(a, b)
+        assert no_active_batch()
     with torch.no_grad():
         for bn in [mod for mod in m.modules() if isinstance(mod, torch.nn.BatchNorm2d)][::5]:
             bn.running_mean.add_(0.3)
@@ -492,10 +498,16 @@ def test_eval_batchnorm_coefficients_from_one_batched_launch_track_the_buffers()
     with torch.inference_mode():
         c, d = m(x), m._forward(x)
         assert torch.equal(c, d) and not torch.equal(a, c)
-        assert m.__dict__["_eval_bn_cache"].fresh is False
+        assert no_active_batch()
+        # the second eval pass replayed the first one's recording: stem 1, head 1, 16 blocks of which the first has no expand BN
+        batch = m.__dict__["_bn_eval_batches"][(False, torch.float32)]
+        assert len(batch.keys) == 49 and batch.ok
         blk = m.block_list()[3]
         h = torch.randn(2, 12, 12, blk.plan.cin, device="cuda")
         assert torch.isfinite(blk(h)).all()               # standalone: per-layer path
+        with pytest.raises(RuntimeError, match="HIP device"):
+            m(x.cpu())                                    # raises inside forward(): the pass scope is left all the same
+        assert no_active_batch()
 
 
 @pytest.mark.gpu
