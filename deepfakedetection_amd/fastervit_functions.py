@@ -27,7 +27,7 @@ import torch
 from . import kernels as K
 from ._lib import ACT_GELU, ACT_NONE, ACT_RELU
 from .functions import BNRef, _bn_state, _c
-from .vit_functions import _gemm_weight, _partial_rows, _prep, _rows, _slot, pwbn_bwd, pwbn_fwd
+from .vit_functions import Layer, _gemm_weight, _partial_rows, _prep, _rows, _slot, bn_backward, cut_layers, pwbn_bwd, pwbn_fwd
 
 _ident_cache: dict = {}
 
@@ -53,17 +53,19 @@ def tok4(t: torch.Tensor) -> torch.Tensor:
 
 
 # =========================================================================== Linear on the GEMM kernels
-def lin_fwd(x, w_nk, bias, act=ACT_NONE, ls=None, residual=None, row_scale=None):
-    ones, ref = ident(x.device, w_nk.shape[0])
-    return pwbn_fwd(x, w_nk, None, ones, bias, ref, False, None, act, ls, residual, row_scale, raw_unused=True)
+def lin_layer(w, bias, ls=None, need_w=False, need_b=False, need_ls=False) -> Layer:
+    """A Linear layer as the Layer of its identity statistic: gamma is ones, beta the bias (its gradient lands in L.dbeta)."""
+    ones, ref = ident(w.device, w.shape[0])
+    return Layer(w, None, ones, bias, ref, ls, need_w, need_beta=need_b and bias is not None, need_ls=need_ls)
 
 
-def lin_bwd(g, x, y, st, w_kn, w, bias, ls, act, need_dx, need_w, need_b, need_ls=False, dx_residual=None, row_scale=None):
-    """-> (dx, dw, dbias, dls)"""
-    ones, _ = ident(x.device, w.shape[0])
-    dx, dw, _, _, dbeta, dls = pwbn_bwd(g, x, y, st, w_kn, tuple(w.shape), w, None, ones, bias, ls, act, False, need_dx, need_w,
-                                        need_b and bias is not None, need_ls, dx_residual, row_scale, identity=True)
-    return dx, dw, (dbeta if need_b else None), dls
+def lin_fwd(x, w_nk, L: Layer, act=ACT_NONE, residual=None, row_scale=None):
+    return pwbn_fwd(x, w_nk, L, False, None, act, residual, row_scale, raw_unused=True)
+
+
+def lin_bwd(g, x, y, st, w_kn, L: Layer, act, need_dx, dx_residual=None, row_scale=None):
+    """-> dx; (dw, dbeta = the bias gradient, dls) land on L"""
+    return pwbn_bwd(g, x, y, st, w_kn, L, act, False, need_dx, dx_residual, row_scale, identity=True)
 
 
 # =========================================================================== coordinate MLPs, batched per level (f32)
@@ -234,11 +236,11 @@ def attn_sub_fwd(x, P, spec: AttnSpec, ls, row_scale):
     derived = getattr(_derived_tls, "table", None)
     xn, lnst = K.layernorm_fwd(x, P["ln_w"], P["ln_b"], 1e-5)
     wq_nk, wq_kn = _prep(P["qkv_w"], dt, derived)
-    qkv, yq, stq = lin_fwd(xn, wq_nk, P["qkv_b"])
+    qkv, yq, stq = lin_fwd(xn, wq_nk, lin_layer(P["qkv_w"], P["qkv_b"]))
     bias_full = P["bias"]
     O, Pm = window_attention_fwd(qkv, bias_full, H)
     wp_nk, wp_kn = _prep(P["proj_w"], dt, derived)
-    out, yp, stp = lin_fwd(O, wp_nk, P["proj_b"], ACT_NONE, ls, x, row_scale)
+    out, yp, stp = lin_fwd(O, wp_nk, lin_layer(P["proj_w"], P["proj_b"], ls), ACT_NONE, x, row_scale)
     return out, (x, xn, lnst, qkv, yq, stq, Pm, O, yp, stp, wq_kn, wp_kn, bias_full)
 
 
@@ -249,8 +251,9 @@ def attn_sub_bwd(g, saved, P, spec: AttnSpec, ls, row_scale, need: dict, need_dx
     H = spec.heads
     grads = {}
     upstream = need_dx or any(need[k] for k in ("ln_w", "ln_b", "qkv_w", "qkv_b", "bias"))
-    dO, grads["proj_w"], grads["proj_b"], grads["ls"] = lin_bwd(g, O, yp, stp, wp_kn, P["proj_w"], P["proj_b"], ls, ACT_NONE, upstream,
-                                                                 need["proj_w"], need["proj_b"], need["ls"], None, row_scale)
+    proj = lin_layer(P["proj_w"], P["proj_b"], ls, need["proj_w"], need["proj_b"], need["ls"])
+    dO = lin_bwd(g, O, yp, stp, wp_kn, proj, ACT_NONE, upstream, None, row_scale)
+    grads["proj_w"], grads["proj_b"], grads["ls"] = proj.dw, proj.dbeta, proj.dls
     if not upstream:
         return None, grads
     need_cpb = need["bias"]
@@ -258,8 +261,9 @@ def attn_sub_bwd(g, saved, P, spec: AttnSpec, ls, row_scale, need: dict, need_dx
     if need_cpb:
         grads["bias"] = dfull.view(H, T, T)
     need_xn = need_dx or need["ln_w"] or need["ln_b"]
-    dxn, grads["qkv_w"], grads["qkv_b"], _ = lin_bwd(dqkv, xn, yq, stq, wq_kn, P["qkv_w"], P["qkv_b"], None, ACT_NONE, need_xn,
-                                                     need["qkv_w"], need["qkv_b"])
+    qkv_l = lin_layer(P["qkv_w"], P["qkv_b"], None, need["qkv_w"], need["qkv_b"])
+    dxn = lin_bwd(dqkv, xn, yq, stq, wq_kn, qkv_l, ACT_NONE, need_xn)
+    grads["qkv_w"], grads["qkv_b"] = qkv_l.dw, qkv_l.dbeta
     dx = None
     if need_xn:
         dx, grads["ln_w"], grads["ln_b"] = _ln_bwd(dxn, x, P["ln_w"], P["ln_b"], lnst, need["ln_w"], need["ln_b"],
@@ -364,10 +368,9 @@ def mlp_sub_bwd(g, saved, P, ls, row_scale, need: dict, need_dx: bool):
     D, _, _ = K.pwconv(dz2, None, w2_kn, None, stats=False)
     dz1, parts, n = K.act_bn_bwd(D, h, None, None, st1, ACT_GELU)
     if need["fc1_b"]:
-        ones1, _ = ident(dev, hid)
-        _, _, db1, _, _ = K.bn_bwd_finalize_ex(parts, n, _rows(h), ones1, P["fc1_b"], None, st1, False, True, False, False,
-                                               (None, _slot(P["fc1_b"], True, (hid,)), None, None))
-        grads["fc1_b"] = db1
+        fc1 = lin_layer(P["fc1_w"], P["fc1_b"], need_b=True)
+        bn_backward(fc1, parts, n, _rows(h), st1, False)
+        grads["fc1_b"] = fc1.dbeta
     if need["fc1_w"]:
         grads["fc1_w"] = K.pwconv_wgrad(dz1, None, xn, None, _slot(P["fc1_w"], True, (hid, C))).view(P["fc1_w"].shape)
     dx = None
@@ -570,39 +573,35 @@ class ConvBlockFunction(torch.autograd.Function):
     @K.batched_sums
     def backward(ctx, g):
         cfg: ConvBlockCtx = ctx.cfg
-        x, y1, a1, y2, st1, st2, w1_kn, w2_kn, w1, b1, g1, be1, w2, b2, g2, be2, gamma, row_scale = ctx.saved_tensors
+        x, y1, a1, y2, st1, st2, w1_kn, w2_kn, *t = ctx.saved_tensors
         need = ctx.needs_input_grad
+        c1, c2 = cut_layers(("conv1", "conv2"), t, need[1:], 0, None).values()
+        c2.ls, c2.need_ls, row_scale = t[8], need[9], t[9]
         tr = cfg.training
         N, H, W, C = x.shape
         rows = N * H * W
         g = _c(g)
         gb = K.scale_rows(g, row_scale) if row_scale is not None else g
         parts, n = K.bn_bwd_reduce(gb, y2, st2, None)
-        nb2 = need[7] or need[8]
-        outs = (_slot(g2, nb2, (C,)), _slot(be2, nb2, (C,)), _slot(gamma, need[9], (C,)), _slot(b2, need[6], (C,)))
-        coef2, dg2, dbe2, dgam, db2 = K.bn_bwd_finalize_ex(parts, n, rows, g2, be2, gamma, st2, tr, nb2, need[9] and gamma is not None,
-                                                           need[6], outs)
+        coef2 = bn_backward(c2, parts, n, rows, st2, tr)
         dz2 = K.affine2_apply(gb, y2, coef2)              # the BN-backward-mapped gradient, once for both consumers
-        dw2 = None
-        if need[5]:
+        if c2.need_w:
             dwg = K.conv_wgrad(dz2, None, a1, None, ACT_NONE, 3, 1, 1)
-            dw2 = K.conv_wgrad_from_gemm(dwg, tuple(w2.shape), _slot(w2, True, tuple(w2.shape)))
+            c2.dw = K.conv_wgrad_from_gemm(dwg, tuple(c2.w.shape), _slot(c2.w, True, tuple(c2.w.shape)))
         # data gradient of a stride-1 convolution = the forward convolution of the BN-backward-mapped gradient with the
         # flipped, transposed weight: no [M][9C] column matrix, no col2im
         da1, _, _ = K.conv_fwd(dz2, None, ACT_NONE, w2_kn, 3, 1, 1, H, W, stats=False)
         dz1, parts, n = K.act_bn_bwd(da1, y1, None, None, st1, ACT_GELU)
-        nb1 = need[3] or need[4]
-        outs = (_slot(g1, nb1, (C,)), _slot(be1, nb1, (C,)), None, _slot(b1, need[2], (C,)))
-        coef1, dg1, dbe1, _, db1 = K.bn_bwd_finalize_ex(parts, n, rows, g1, be1, None, st1, tr, nb1, False, need[2], outs)
-        dw1 = dx = None
-        dzm1 = K.affine2_apply(dz1, y1, coef1) if (need[0] or need[1]) else None
-        if need[1]:
+        coef1 = bn_backward(c1, parts, n, rows, st1, tr)
+        dx = None
+        dzm1 = K.affine2_apply(dz1, y1, coef1) if (need[0] or c1.need_w) else None
+        if c1.need_w:
             dwg = K.conv_wgrad(dzm1, None, x, None, ACT_NONE, 3, 1, 1)
-            dw1 = K.conv_wgrad_from_gemm(dwg, tuple(w1.shape), _slot(w1, True, tuple(w1.shape)))
+            c1.dw = K.conv_wgrad_from_gemm(dwg, tuple(c1.w.shape), _slot(c1.w, True, tuple(c1.w.shape)))
         if need[0]:
             dx0, _, _ = K.conv_fwd(dzm1, None, ACT_NONE, w1_kn, 3, 1, 1, H, W, stats=False)
             dx = K.add(dx0, g)
-        return (dx, dw1, db1 if need[2] else None, dg1, dbe1, dw2, db2 if need[6] else None, dg2, dbe2, dgam, None, None)
+        return (dx, *c1.grads(), *c2.grads(), c2.dls, None, None)
 
 
 def _dgrad_weight(w: torch.Tensor, dt: torch.dtype):

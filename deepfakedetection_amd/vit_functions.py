@@ -2,7 +2,8 @@
 
 One torch.autograd.Function per network stage, built from plain forward/backward helper pairs (no autograd
 inside a stage, so a tensor with several consumers gets its gradient summed by the `residual` operand of a
-GEMM launch, never by an ATen add):
+GEMM launch, never by an ATen add).  Every "conv (+bias) + BatchNorm [+ LayerScale]" layer travels through its stage
+as one `Layer` record (tensors, one need flag per tensor, the gradients its backward produced):
 
   ConvStemFunction     conv3x3 s2 on the f32 image (+bias) + BN + GELU                    timm Stem4.conv1
   DenseConvBNFunction  dense 3x3 conv (+bias) + BN [+ GELU] as im2col + MFMA GEMM         Stem4.conv2, Downsample.conv
@@ -42,6 +43,66 @@ def _rows(t: torch.Tensor) -> int:
     return t.numel() // t.shape[-1]
 
 
+@dataclass
+class Layer:
+    """One "conv (+bias) + BatchNorm [+ LayerScale]" layer of a stage: its tensors, one need flag per tensor (all False in a
+    forward, where only the tensors matter) and the gradients its backward produced.  A plain record: built afresh from the
+    arguments in `forward` and from ctx.saved_tensors in `backward`, never kept on ctx."""
+
+    w: torch.Tensor | None
+    b: torch.Tensor | None
+    gamma: torch.Tensor
+    beta: torch.Tensor | None
+    bn: BNRef | None = None
+    ls: torch.Tensor | None = None
+    need_w: bool = False
+    need_b: bool = False
+    need_gamma: bool = False
+    need_beta: bool = False
+    need_ls: bool = False
+    dw: torch.Tensor | None = None
+    db: torch.Tensor | None = None
+    dgamma: torch.Tensor | None = None
+    dbeta: torch.Tensor | None = None
+    dls: torch.Tensor | None = None
+
+    @property
+    def need_bn(self) -> bool:
+        """gamma and beta share one launch flag: the kernel writes both."""
+        return self.need_gamma or self.need_beta
+
+    @property
+    def need_any(self) -> bool:
+        return self.need_w or self.need_b or self.need_bn
+
+    def grads(self):
+        """(dw, db, dgamma, dbeta) in input order, each masked by its own flag."""
+        return (self.dw if self.need_w else None, self.db if self.need_b else None,
+                self.dgamma if self.need_gamma else None, self.dbeta if self.need_beta else None)
+
+
+def cut_layers(names, t, need, offset: int, bns) -> dict[str, Layer]:
+    """{name: Layer} for the (weight, bias, bn.weight, bn.bias) quads that start at t[offset], one per name.
+    need: the slice of ctx.needs_input_grad that lines up with t (None in a forward); bns: name -> BNRef, or None."""
+    out = {}
+    for i, nm in enumerate(names):
+        o = offset + 4 * i
+        flags = need[o: o + 4] if need is not None else ()
+        out[nm] = Layer(*t[o: o + 4], bns[nm] if bns is not None else None, None, *flags)
+    return out
+
+
+def bn_backward(L: Layer, parts, n, rows: int, st, training: bool):
+    """The BatchNorm-backward coefficients of L from the partial sums; dgamma, dbeta, dls and the convolution-bias gradient land
+    on L — in their gradient-arena slots, each claimed only when this launch really writes it."""
+    C = L.gamma.numel()
+    nb, want_ls, want_b = L.need_bn, L.need_ls and L.ls is not None, L.need_b and L.b is not None
+    outs = (_slot(L.gamma, nb, (C,)), _slot(L.beta, nb, (C,)), _slot(L.ls, want_ls, (C,)), _slot(L.b, want_b, (C,)))
+    coef, L.dgamma, L.dbeta, L.dls, L.db = K.bn_bwd_finalize_ex(parts, n, rows, L.gamma, L.beta, L.ls, st, training, nb, want_ls,
+                                                                want_b, outs)
+    return coef
+
+
 def _prep(w: torch.Tensor, dt: torch.dtype, derived, need_bwd: bool = True):
     """(w_nk, w_kn) of a 1x1 convolution weight [O, I, 1, 1] (or a 2-D GEMM weight) in the activation dtype.
     derived: {weight.data_ptr(): (w_nk, w_kn)} refreshed for the whole network by one batched launch per forward
@@ -55,8 +116,7 @@ def _prep(w: torch.Tensor, dt: torch.dtype, derived, need_bwd: bool = True):
 
 
 # =========================================================================== helper pairs (no autograd)
-def pwbn_fwd(x, w_nk, b, gamma, beta, bn: BNRef, training, counters, act=ACT_NONE, ls=None, residual=None, row_scale=None,
-             raw_unused=False):
+def pwbn_fwd(x, w_nk, L: Layer, training, counters, act=ACT_NONE, residual=None, row_scale=None, raw_unused=False):
     """1x1 conv (+bias) -> BN -> act, [* ls] [* row_scale] [+ residual]; returns (materialised out, raw y, bn state).
     raw_unused: the caller's backward never reads y (the identity-statistics Linear layers of FasterViT, whose backward is
     pwbn_bwd's `plain` path) — only then may the fused eval kernel skip writing it.  Every caller with a real BatchNorm needs y in
@@ -66,98 +126,88 @@ def pwbn_fwd(x, w_nk, b, gamma, beta, bn: BNRef, training, counters, act=ACT_NON
         # produced only where a backward reads it (activation, LayerScale); otherwise None is returned in its place — NOT `out`:
         # a block Function that kept its own output among its saved tensors would close the reference cycle that once crashed
         # hipStreamEndCapture.
-        st = _bn_state(None, 0, _rows(x), bn, gamma, beta, False, counters, conv_bias=b, ls=ls)
-        fused = K.gemm_bias_act(x, w_nk, st, act, residual, row_scale, want_raw=(not raw_unused or act != ACT_NONE or ls is not None))
+        st = _bn_state(None, 0, _rows(x), L.bn, L.gamma, L.beta, False, counters, conv_bias=L.b, ls=L.ls)
+        fused = K.gemm_bias_act(x, w_nk, st, act, residual, row_scale, want_raw=(not raw_unused or act != ACT_NONE or L.ls is not None))
         if fused is not None:
             out, raw = fused
             return out, raw, st
         y, _, _ = K.pwconv(x, None, w_nk, None, stats=False)
         return K.bn_act_apply(y, st, act, residual, row_scale), y, st
     y, parts, n = K.pwconv(x, None, w_nk, None, stats=training)
-    st = _bn_state(parts, n, _rows(y), bn, gamma, beta, training, counters, conv_bias=b, ls=ls)
+    st = _bn_state(parts, n, _rows(y), L.bn, L.gamma, L.beta, training, counters, conv_bias=L.b, ls=L.ls)
     out = K.bn_act_apply(y, st, act, residual, row_scale)
     return out, y, st
 
 
-def pwbn_bwd(g, x, y, st, w_kn, w_shape, w, b, gamma, beta, ls, act, training, need_dx, need_w, need_bn, need_ls=False,
-             dx_residual=None, row_scale=None, need_b=None, identity=False):
-    """Backward of pwbn_fwd for the gradient g of its output.  Returns (dx, dw, db, dgamma, dbeta, dls); dx already
-    includes `dx_residual` (the running sum of the other consumers' gradients of x).
+def pwbn_bwd(g, x, y, st, w_kn, L: Layer, act, training, need_dx, dx_residual=None, row_scale=None, identity=False):
+    """Backward of pwbn_fwd for the gradient g of its output.  Returns dx, which already includes `dx_residual` (the running
+    sum of the other consumers' gradients of x); the parameter gradients land on L.
     identity: the "BatchNorm" is the identity statistic of a Linear layer (fastervit_functions.ident): its backward map
     is dy = ls * dz, so the two GEMMs take dz as it is (or scaled per channel) instead of the two-operand BN-backward
     prologue, which would read y only to multiply it by zero."""
     if row_scale is not None:
         g = K.scale_rows(g, row_scale)
+    O, I = L.w.shape[0], L.w.shape[1]
     # a Linear layer without layer scale: the BatchNorm-shaped backward degenerates to dz = g and dbias = column sums of g
-    plain = act == ACT_NONE and identity and not training and ls is None and not need_ls and b is None
+    plain = act == ACT_NONE and identity and not training and L.ls is None and not L.need_ls and L.b is None
     if plain:
-        dbeta = K.bias_grad(g, None, _slot(beta, need_bn, (gamma.numel(),))) if (need_bn and beta is not None) else None
+        if L.need_bn and L.beta is not None:
+            L.dbeta = K.bias_grad(g, None, _slot(L.beta, True, (O,)))
         dx = dx_residual
         if need_dx:
             dx, _, _ = K.pwconv(g, None, w_kn, dx_residual, stats=False)
-        dw = None
-        if need_w:
-            O, I = w_shape[0], w_shape[1]
-            dw = K.pwconv_wgrad(g, None, x, None, _slot(w, True, (O, I))).view(w_shape)
-        return dx, dw, None, None, dbeta, None
+        if L.need_w:
+            L.dw = K.pwconv_wgrad(g, None, x, None, _slot(L.w, True, (O, I))).view(L.w.shape)
+        return dx
     if act == ACT_NONE:
         parts, n = K.bn_bwd_reduce(g, y, st, None)
         dz = g
     else:
         dz, parts, n = K.act_bn_bwd(g, y, None, None, st, act)
-    C = gamma.numel()
-    want_b = (need_w if need_b is None else need_b) and b is not None
-    outs = (_slot(gamma, need_bn, (C,)), _slot(beta, need_bn, (C,)), _slot(ls, need_ls, (C,)), _slot(b, want_b, (C,)))
-    coef, dgamma, dbeta, dls, db = K.bn_bwd_finalize_ex(parts, n, _rows(y), gamma, beta, ls, st, training, need_bn, need_ls,
-                                                        want_b, outs)
+    coef = bn_backward(L, parts, n, _rows(y), st, training)
     if identity and not training:
         pro_d = pro_w = None
-        if ls is not None:
+        if L.ls is not None:
             # rows 0, 1 of coef = (ls, 0): a plain per-channel scale (the GEMM kernels add a residual only behind the
             # prologues the EfficientNet path uses, so with one the two-operand form stays)
             pro_w = K.pro_affine2(y, coef)
             pro_d = K.pro_bn_act(coef, ACT_NONE) if dx_residual is None else pro_w
     else:
         pro_d = pro_w = K.pro_affine2(y, coef)
-        if need_dx and need_w and K.pwconv_bwd_fused_ok(dz, x):
+        if need_dx and L.need_w and K.pwconv_bwd_fused_ok(dz, x):
             # narrow input, wide BatchNormed output at many rows (EfficientFormerV2 stage-1 fc1: 32 -> 128 at 802,816 rows): data and
             # weight gradient from one pass over (dz, y) — csrc/dfd_pwtnw.hip, DG; bit-identical to the two kernels below
-            O, I = w_shape[0], w_shape[1]
-            dx, dw = K.pwconv_bwd_fused(dz, y, coef, x, w_kn, dx_residual, _slot(w, True, (O, I)))
-            return dx, dw.view(w_shape), db, dgamma, dbeta, dls
+            dx, dw = K.pwconv_bwd_fused(dz, y, coef, x, w_kn, dx_residual, _slot(L.w, True, (O, I)))
+            L.dw = dw.view(L.w.shape)
+            return dx
     dx = dx_residual
     if need_dx:
         dx, _, _ = K.pwconv(dz, pro_d, w_kn, dx_residual, stats=False)
-    dw = None
-    if need_w:
-        O, I = w_shape[0], w_shape[1]
-        dw = K.pwconv_wgrad(dz, pro_w, x, None, _slot(w, True, (O, I))).view(w_shape)
-    return dx, dw, db, dgamma, dbeta, dls
+    if L.need_w:
+        L.dw = K.pwconv_wgrad(dz, pro_w, x, None, _slot(L.w, True, (O, I))).view(L.w.shape)
+    return dx
 
 
-def dwbn_fwd(x, w, b, gamma, beta, bn: BNRef, training, counters, k: int, stride: int):
+def dwbn_fwd(x, L: Layer, training, counters, k: int, stride: int):
     """depthwise k x k (+bias) -> raw y and the BN state (the consumer applies it)."""
     N, H, W, C = x.shape
     p = k // 2
     Ho, Wo = (H + 2 * p - k) // stride + 1, (W + 2 * p - k) // stride + 1
-    y, parts, n = K.dwconv_fwd(x, None, ACT_NONE, w, k, stride, p, p, Ho, Wo, stats=training)
-    st = _bn_state(parts, n, N * Ho * Wo, bn, gamma, beta, training, counters, conv_bias=b)
+    y, parts, n = K.dwconv_fwd(x, None, ACT_NONE, L.w, k, stride, p, p, Ho, Wo, stats=training)
+    st = _bn_state(parts, n, N * Ho * Wo, L.bn, L.gamma, L.beta, training, counters, conv_bias=L.b)
     return y, st
 
 
-def dwbn_bwd(dz, parts, n, x, y, st, w, b, gamma, beta, training, k, stride, need_dx, need_w, need_bn):
-    """dz: gradient at the BN output (with its partial sums).  Returns (dx, dw, db, dgamma, dbeta)."""
-    C = gamma.numel()
+def dwbn_bwd(dz, parts, n, x, y, st, L: Layer, training, k, stride, need_dx):
+    """dz: gradient at the BN output (with its partial sums).  Returns dx; the parameter gradients land on L."""
     p = k // 2
-    outs = (_slot(gamma, need_bn, (C,)), _slot(beta, need_bn, (C,)), None, _slot(b, need_w, (C,)))
-    coef, dgamma, dbeta, _, db = K.bn_bwd_finalize_ex(parts, n, _rows(y), gamma, beta, None, st, training, need_bn, False,
-                                                      need_w and b is not None, outs)
-    dx = dw = None
+    coef = bn_backward(L, parts, n, _rows(y), st, training)
+    dx = None
     if need_dx:
-        dx, _, _ = K.dwconv_bwd_data(dz, y, coef, w, None, None, ACT_NONE, tuple(x.shape), k, stride, p, p)
-    if need_w:
-        dw = K.dwconv_bwd_weight(dz, y, coef, x, None, ACT_NONE, k, stride, p, p, _slot(w, True, (C, 1, k, k)))
-    return dx, dw, db, dgamma, dbeta
+        dx, _, _ = K.dwconv_bwd_data(dz, y, coef, L.w, None, None, ACT_NONE, tuple(x.shape), k, stride, p, p)
+    if L.need_w:
+        L.dw = K.dwconv_bwd_weight(dz, y, coef, x, None, ACT_NONE, k, stride, p, p, _slot(L.w, True, tuple(L.w.shape)))
+    return dx
 
 
 @dataclass
@@ -311,46 +361,37 @@ class ConvStemFunction(torch.autograd.Function):
     @K.batched_sums
     def backward(ctx, g):
         cfg: ConvStemCtx = ctx.cfg
-        x, y, st, weight, bias, gamma, beta = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        C, k = weight.shape[0], weight.shape[2]
+        x, y, st, *t = ctx.saved_tensors
+        L = cut_layers(("conv",), t, ctx.needs_input_grad[1:], 0, None)["conv"]
         dz, parts, n = K.act_bn_bwd(_c(g), y, None, None, st, cfg.act)
-        need_bn = need[3] or need[4]
-        outs = (_slot(gamma, need_bn, (C,)), _slot(beta, need_bn, (C,)), None, _slot(bias, need[2], (C,)))
-        coef, dgamma, dbeta, _, db = K.bn_bwd_finalize_ex(parts, n, _rows(y), gamma, beta, None, st, cfg.training, need_bn,
-                                                          False, need[2], outs)
-        dw = None
-        if need[1]:
-            dw = K.stem_conv_wgrad(x, dz, y, coef, k, cfg.stride, cfg.pad, cfg.pad, _slot(weight, True, tuple(weight.shape)))
-        return None, dw, db, dgamma, dbeta, None
+        coef = bn_backward(L, parts, n, _rows(y), st, cfg.training)
+        if L.need_w:
+            L.dw = K.stem_conv_wgrad(x, dz, y, coef, L.w.shape[2], cfg.stride, cfg.pad, cfg.pad, _slot(L.w, True, tuple(L.w.shape)))
+        return (None, *L.grads(), None)
 
 
 # =========================================================================== dense conv + BN (+ act)
-def dense_conv_fwd(x, wg_nk, b, gamma, beta, bn: BNRef, training, counters, k, stride):
+def dense_conv_fwd(x, wg_nk, L: Layer, training, counters, k, stride):
     N, H, W, C = x.shape
     p = k // 2
     Ho, Wo = (H + 2 * p - k) // stride + 1, (W + 2 * p - k) // stride + 1
     y, parts, n = K.conv_fwd(x, None, ACT_NONE, wg_nk, k, stride, p, Ho, Wo, stats=training)
-    st = _bn_state(parts, n, N * Ho * Wo, bn, gamma, beta, training, counters, conv_bias=b)
+    st = _bn_state(parts, n, N * Ho * Wo, L.bn, L.gamma, L.beta, training, counters, conv_bias=L.b)
     return y, st
 
 
-def dense_conv_bwd(dz, parts, n, x, y, st, wg_kn, w, b, gamma, beta, training, k, stride, need_dx, need_w, need_bn):
-    """dz: gradient at the BN output.  The im2col matrix is rebuilt instead of kept (9x the input)."""
-    C = gamma.numel()
+def dense_conv_bwd(dz, parts, n, x, y, st, wg_kn, L: Layer, training, k, stride, need_dx):
+    """dz: gradient at the BN output.  The im2col matrix is rebuilt instead of kept (9x the input).  Returns dx."""
     p = k // 2
-    outs = (_slot(gamma, need_bn, (C,)), _slot(beta, need_bn, (C,)), None, _slot(b, need_w, (C,)))
-    coef, dgamma, dbeta, _, db = K.bn_bwd_finalize_ex(parts, n, _rows(y), gamma, beta, None, st, training, need_bn, False,
-                                                      need_w and b is not None, outs)
-    pro = K.pro_affine2(y, coef)
-    dx = dw = None
+    pro = K.pro_affine2(y, bn_backward(L, parts, n, _rows(y), st, training))
+    dx = None
     if need_dx:
         dcol, _, _ = K.pwconv(dz, pro, wg_kn, None, stats=False)
         dx = K.col2im(dcol, tuple(x.shape), k, stride, p)
-    if need_w:
+    if L.need_w:
         dwg = K.conv_wgrad(dz, pro, x, None, ACT_NONE, k, stride, p)
-        dw = K.conv_wgrad_from_gemm(dwg, tuple(w.shape), _slot(w, True, tuple(w.shape)))
-    return dx, dw, db, dgamma, dbeta
+        L.dw = K.conv_wgrad_from_gemm(dwg, tuple(L.w.shape), _slot(L.w, True, tuple(L.w.shape)))
+    return dx
 
 
 def _gemm_weight(w: torch.Tensor, dt: torch.dtype, need_bwd: bool):
@@ -375,7 +416,7 @@ class DenseConvBNFunction(torch.autograd.Function):
     def forward(ctx, x, weight, bias, gamma, beta, cfg: DenseConvCtx):
         need_bwd = any(ctx.needs_input_grad)
         wg_nk, wg_kn = _gemm_weight(weight, x.dtype, need_bwd)
-        y, st = dense_conv_fwd(x, wg_nk, bias, gamma, beta, cfg.bn, cfg.training, cfg.counters, cfg.k, cfg.stride)
+        y, st = dense_conv_fwd(x, wg_nk, Layer(weight, bias, gamma, beta, cfg.bn), cfg.training, cfg.counters, cfg.k, cfg.stride)
         out = K.bn_act_apply(y, st, cfg.act)
         ctx.cfg = cfg
         ctx.save_for_backward(x, y, st, wg_kn, weight, bias, gamma, beta)
@@ -385,17 +426,17 @@ class DenseConvBNFunction(torch.autograd.Function):
     @K.batched_sums
     def backward(ctx, g):
         cfg: DenseConvCtx = ctx.cfg
-        x, y, st, wg_kn, weight, bias, gamma, beta = ctx.saved_tensors
+        x, y, st, wg_kn, *t = ctx.saved_tensors
         need = ctx.needs_input_grad
+        L = cut_layers(("conv",), t, need[1:], 0, None)["conv"]
         g = _c(g)
         if cfg.act == ACT_NONE:
             parts, n = K.bn_bwd_reduce(g, y, st, None)
             dz = g
         else:
             dz, parts, n = K.act_bn_bwd(g, y, None, None, st, cfg.act)
-        dx, dw, db, dgamma, dbeta = dense_conv_bwd(dz, parts, n, x, y, st, wg_kn, weight, bias, gamma, beta, cfg.training, cfg.k,
-                                                   cfg.stride, need[0], need[1], need[3] or need[4])
-        return dx, dw, db if need[2] else None, dgamma, dbeta, None
+        dx = dense_conv_bwd(dz, parts, n, x, y, st, wg_kn, L, cfg.training, cfg.k, cfg.stride, need[0])
+        return (dx, *L.grads(), None)
 
 
 # =========================================================================== ConvMlp block
@@ -449,9 +490,10 @@ class ConvMlpFunction(torch.autograd.Function):
     @staticmethod
     def _backward(ctx, g):
         cfg: ConvMlpCtx = ctx.cfg
-        (x, y1, a1, y2, a2, y3, st1, st2, st3, w1_kn, w2_kn, w1, b1, g1, be1, wd, bd, gd, bed, w2, b2, g2, be2, ls,
-         row_scale) = ctx.saved_tensors
+        x, y1, a1, y2, a2, y3, st1, st2, st3, w1_kn, w2_kn, *t = ctx.saved_tensors
         need = ctx.needs_input_grad
+        fc1, dw, fc2 = cut_layers(("fc1", "dw", "fc2"), t, need[1:], 0, None).values()
+        fc2.ls, fc2.need_ls, row_scale = t[12], need[13], t[13]
         tr = cfg.training
         rows = _rows(y1)
         C, Cm = x.shape[3], y1.shape[3]
@@ -459,40 +501,32 @@ class ConvMlpFunction(torch.autograd.Function):
         gb = K.scale_rows(g, row_scale) if ctx.has_rs else g
         # ---- fc2's BN (+ LayerScale) backward, folded into the two GEMMs that consume dy3
         parts, n = K.bn_bwd_reduce(gb, y3, st3, None)
-        nb2 = need[11] or need[12]
-        outs = (_slot(g2, nb2, (C,)), _slot(be2, nb2, (C,)), _slot(ls, need[13], (C,)), _slot(b2, need[10], (C,)))
-        coef3, dg2, dbe2, dls, db2 = K.bn_bwd_finalize_ex(parts, n, rows, g2, be2, ls, st3, tr, nb2, need[13], need[10], outs)
+        coef3 = bn_backward(fc2, parts, n, rows, st3, tr)
         # the mapped gradient [rows][C] is materialised once for its two GEMMs (as a prologue it is re-evaluated per 128-column
         # tile of the Cm-wide data gradient; S1: 18.48 -> 18.35 ms).  The Cm-wide one below stays a prologue (measured neutral)
         gm3 = K.affine2_apply(gb, y3, coef3)
         D, _, _ = K.pwconv(gm3, None, w2_kn, None, stats=False)
-        dw2 = None
-        if need[9]:
-            dw2 = K.pwconv_wgrad(gm3, None, a2, None, _slot(w2, True, (C, Cm))).view(C, Cm, 1, 1)
+        if fc2.need_w:
+            fc2.dw = K.pwconv_wgrad(gm3, None, a2, None, _slot(fc2.w, True, (C, Cm))).view(C, Cm, 1, 1)
         # ---- GELU' and the depthwise BN backward
         dz2, parts, n = K.act_bn_bwd(D, y2, None, None, st2, ACT_GELU)
-        nbd = need[7] or need[8]
-        outs = (_slot(gd, nbd, (Cm,)), _slot(bed, nbd, (Cm,)), None, _slot(bd, need[6], (Cm,)))
-        coef2, dgd, dbed, _, dbd = K.bn_bwd_finalize_ex(parts, n, rows, gd, bed, None, st2, tr, nbd, False, need[6], outs)
-        dwd = None
-        dz1, parts, n = K.dwconv_bwd_data(dz2, y2, coef2, wd, y1, st1, ACT_GELU, tuple(y1.shape), 3, 1, 1, 1)
-        nb1 = need[3] or need[4]
-        outs = (_slot(g1, nb1, (Cm,)), _slot(be1, nb1, (Cm,)), None, _slot(b1, need[2], (Cm,)))
-        coef1, dg1, dbe1, _, db1 = K.bn_bwd_finalize_ex(parts, n, rows, g1, be1, None, st1, tr, nb1, False, need[2], outs)
-        if need[5]:
-            dwd = K.dwconv_bwd_weight(dz2, y2, coef2, a1, None, ACT_NONE, 3, 1, 1, 1, _slot(wd, True, (Cm, 1, 3, 3)))
+        coef2 = bn_backward(dw, parts, n, rows, st2, tr)
+        dz1, parts, n = K.dwconv_bwd_data(dz2, y2, coef2, dw.w, y1, st1, ACT_GELU, tuple(y1.shape), 3, 1, 1, 1)
+        coef1 = bn_backward(fc1, parts, n, rows, st1, tr)
+        if dw.need_w:
+            dw.dw = K.dwconv_bwd_weight(dz2, y2, coef2, a1, None, ACT_NONE, 3, 1, 1, 1, _slot(dw.w, True, (Cm, 1, 3, 3)))
         pro1 = K.pro_affine2(y1, coef1)
-        dw1 = dx = None
-        if need[0] and need[1] and K.pwconv_bwd_fused_ok(dz1, x):
+        dx = None
+        if need[0] and fc1.need_w and K.pwconv_bwd_fused_ok(dz1, x):
             # fc1 of the early stages (32 -> 128 at 802,816 rows): both gradients from ONE pass over (dz1, y1) — csrc/dfd_pwtnw.hip, DG
-            dx, dw1 = K.pwconv_bwd_fused(dz1, y1, coef1, x, w1_kn, g, _slot(w1, True, (Cm, C)))
-            dw1 = dw1.view(Cm, C, 1, 1)
+            dx, dw1 = K.pwconv_bwd_fused(dz1, y1, coef1, x, w1_kn, g, _slot(fc1.w, True, (Cm, C)))
+            fc1.dw = dw1.view(Cm, C, 1, 1)
         else:
-            if need[1]:
-                dw1 = K.pwconv_wgrad(dz1, pro1, x, None, _slot(w1, True, (Cm, C))).view(Cm, C, 1, 1)
+            if fc1.need_w:
+                fc1.dw = K.pwconv_wgrad(dz1, pro1, x, None, _slot(fc1.w, True, (Cm, C))).view(Cm, C, 1, 1)
             if need[0]:
                 dx, _, _ = K.pwconv(dz1, pro1, w1_kn, g, stats=False)
-        return (dx, dw1, db1, dg1, dbe1, dwd, dbd, dgd, dbed, dw2, db2, dg2, dbe2, dls, None, None)
+        return (dx, *fc1.grads(), *dw.grads(), *fc2.grads(), fc2.dls, None, None)
 
 
 # =========================================================================== attention block
@@ -510,6 +544,10 @@ class AttentionCtx:
 _ATT_ORDER = ("stride_conv", "q", "k", "v", "v_local", "proj")
 
 
+def _att_names(cfg) -> tuple:
+    return _ATT_ORDER if cfg.stride is not None else _ATT_ORDER[1:]
+
+
 class AttentionFunction(torch.autograd.Function):
     """x + [row_scale *] ls1 * Attention2d(x).  Tensor inputs after x, in order:
     for name in (stride_conv?, q, k, v, v_local, proj): weight, bias, bn.weight, bn.bias;
@@ -518,42 +556,34 @@ class AttentionFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, cfg: AttentionCtx, *t):
         tr, cn, geo = cfg.training, cfg.counters, cfg.geo
-        names = [nm for nm in _ATT_ORDER if nm != "stride_conv" or cfg.stride is not None]
-        P4 = {nm: t[4 * i: 4 * i + 4] for i, nm in enumerate(names)}
-        at = 4 * len(names)
-        th_w1, th_b1, th_w2, th_b2, table, ls, row_scale = t[at: at + 7]
+        Ls = cut_layers(_att_names(cfg), t, None, 0, cfg.bns)
+        th_w1, th_b1, th_w2, th_b2, table, Ls["proj"].ls, row_scale = t[4 * len(Ls):]
         H = geo.heads
         th = (th_w1.reshape(H, H), th_b1, th_w2.reshape(H, H), th_b2)
         dt = x.dtype
         xs, ys, sts = x, None, None
         if cfg.stride is not None:
-            w, b, gm, be = P4["stride_conv"]
-            ys, sts = dwbn_fwd(x, w, b, gm, be, cfg.bns["stride_conv"], tr, cn, 3, cfg.stride)
+            ys, sts = dwbn_fwd(x, Ls["stride_conv"], tr, cn, 3, cfg.stride)
             xs = K.bn_act_apply(ys, sts, ACT_NONE)
         kn = {}
         mats = {}
         for nm in ("q", "k", "v"):
-            w, b, gm, be = P4[nm]
-            w_nk, kn[nm] = _prep(w, dt, cfg.derived)
-            mats[nm] = pwbn_fwd(xs, w_nk, b, gm, be, cfg.bns[nm], tr, cn)
+            w_nk, kn[nm] = _prep(Ls[nm].w, dt, cfg.derived)
+            mats[nm] = pwbn_fwd(xs, w_nk, Ls[nm], tr, cn)
         q, yq, stq = mats["q"]
         k, yk, stk = mats["k"]
         v, yv, stv = mats["v"]
         O, S, P, T2 = attn_core_fwd(q, k, v, table, cfg.idx, th, geo)
-        w, b, gm, be = P4["v_local"]
-        yl, stl = dwbn_fwd(v, w, b, gm, be, cfg.bns["v_local"], tr, cn, 3, 1)
+        yl, stl = dwbn_fwd(v, Ls["v_local"], tr, cn, 3, 1)
         if cfg.stride is not None:
             s = K.bn_add_act(yl, stl, O, ACT_NONE)
             a = K.up2_act_fwd(s, ACT_GELU)
         else:
             s = None
             a = K.bn_add_act(yl, stl, O, ACT_GELU)
-        w, b, gm, be = P4["proj"]
-        w_nk, kn["proj"] = _prep(w, dt, cfg.derived)
-        out, yp, stp = pwbn_fwd(a, w_nk, b, gm, be, cfg.bns["proj"], tr, cn, ACT_NONE, ls, x, row_scale)
+        w_nk, kn["proj"] = _prep(Ls["proj"].w, dt, cfg.derived)
+        out, yp, stp = pwbn_fwd(a, w_nk, Ls["proj"], tr, cn, ACT_NONE, x, row_scale)
         ctx.cfg = cfg
-        ctx.names = names
-        ctx.nt = len(t)
         ctx.save_for_backward(x, xs, ys, sts, q, yq, stq, k, yk, stk, v, yv, stv, S, P, T2, O, yl, stl, s, a, yp, stp,
                               kn["q"], kn["k"], kn["v"], kn["proj"], *t)
         return out
@@ -562,30 +592,22 @@ class AttentionFunction(torch.autograd.Function):
     @K.batched_sums
     def backward(ctx, g):
         cfg: AttentionCtx = ctx.cfg
-        sv = ctx.saved_tensors
-        (x, xs, ys, sts, q, yq, stq, k, yk, stk, v, yv, stv, S, P, T2, O, yl, stl, s, a, yp, stp, knq, knk, knv, knp) = sv[:27]
-        t = sv[27:]
-        names = ctx.names
+        (x, xs, ys, sts, q, yq, stq, k, yk, stk, v, yv, stv, S, P, T2, O, yl, stl, s, a, yp, stp, knq, knk, knv, knp,
+         *t) = ctx.saved_tensors
         need = ctx.needs_input_grad                       # [x, cfg, *t]
-        nt = {nm: need[2 + 4 * i: 2 + 4 * i + 4] for i, nm in enumerate(names)}
-        P4 = {nm: t[4 * i: 4 * i + 4] for i, nm in enumerate(names)}
-        at = 4 * len(names)
-        th_w1, th_b1, th_w2, th_b2, table, ls, row_scale = t[at: at + 7]
-        n_th = need[2 + at: 2 + at + 4]
-        n_table, n_ls = need[2 + at + 4], need[2 + at + 5]
+        Ls = cut_layers(_att_names(cfg), t, need[2:], 0, None)
+        at = 4 * len(Ls)
+        th_w1, th_b1, th_w2, th_b2, table, Ls["proj"].ls, row_scale = t[at:]
+        *n_th, n_table, Ls["proj"].need_ls, _ = need[2 + at:]
         tr, geo = cfg.training, cfg.geo
         H = geo.heads
         th = (th_w1.reshape(H, H), th_b1, th_w2.reshape(H, H), th_b2)
-        grads: dict = {}
         g = _c(g)
         # ---- proj (1x1 + BN, LayerScale, drop-path scale); its input gradient is needed by everything upstream
-        upstream = need[0] or any(any(nt[nm]) for nm in names if nm != "proj") or any(n_th) or n_table
-        w, b, gm, be = P4["proj"]
-        da, dw, db, dgm, dbe, dls = pwbn_bwd(g, a, yp, stp, knp, tuple(w.shape), w, b, gm, be, ls, ACT_NONE, tr, upstream,
-                                             nt["proj"][0], nt["proj"][2] or nt["proj"][3], n_ls, None, row_scale)
-        grads["proj"] = (dw, db if nt["proj"][1] else None, dgm, dbe)
+        upstream = need[0] or any(L.need_any for nm, L in Ls.items() if nm != "proj") or any(n_th) or n_table
+        da = pwbn_bwd(g, a, yp, stp, knp, Ls["proj"], ACT_NONE, tr, upstream, None, row_scale)
         dx = None
-        dth = None
+        dth = (None, None, None, None)
         dtable = None
         if upstream:
             # ---- GELU [+ upsample] and the sum O + BN(v_local)
@@ -594,49 +616,26 @@ class AttentionFunction(torch.autograd.Function):
                 parts, n = K.bn_bwd_reduce(d, yl, stl, None)
             else:
                 d, parts, n = K.bn_add_act_bwd(da, yl, stl, O, ACT_GELU)
-            w, b, gm, be = P4["v_local"]
-            nv = nt["v_local"]
-            dv_loc, dw, db, dgm, dbe = dwbn_bwd(d, parts, n, v, yl, stl, w, b, gm, be, tr, 3, 1, True, nv[0], nv[2] or nv[3])
-            grads["v_local"] = (dw, db if nv[1] else None, dgm, dbe)
+            dv_loc = dwbn_bwd(d, parts, n, v, yl, stl, Ls["v_local"], tr, 3, 1, True)
             # ---- attention core
-            dQ, dK, dV, dtable, dth = attn_core_bwd(d, q, k, v, S, P, T2, table, cfg.idx, th, geo, n_table, any(n_th),
-                                                    (th_w1, th_b1, th_w2, th_b2))
+            dQ, dK, dV, dtable, dth_ = attn_core_bwd(d, q, k, v, S, P, T2, table, cfg.idx, th, geo, n_table, any(n_th),
+                                                     (th_w1, th_b1, th_w2, th_b2))
+            if dth_ is not None:
+                dth = tuple(d_ if nd else None for d_, nd in zip(dth_, n_th))
             dVt = K.add(dV, dv_loc)
             # ---- q, k, v projections: the gradient of their common input accumulates through `residual`
-            need_xs = need[0] or (cfg.stride is not None and any(nt["stride_conv"]))
+            need_xs = need[0] or (cfg.stride is not None and Ls["stride_conv"].need_any)
             acc = g if (cfg.stride is None and need[0]) else None          # the skip connection's share of dx
             for nm, dz, y_, st_, kn_ in (("q", dQ, yq, stq, knq), ("k", dK, yk, stk, knk), ("v", dVt, yv, stv, knv)):
-                w, b, gm, be = P4[nm]
-                nn_ = nt[nm]
-                acc, dw, db, dgm, dbe, _ = pwbn_bwd(dz, xs, y_, st_, kn_, tuple(w.shape), w, b, gm, be, None, ACT_NONE, tr,
-                                                    need_xs, nn_[0], nn_[2] or nn_[3], False, acc, None)
-                grads[nm] = (dw, db if nn_[1] else None, dgm, dbe)
-            if cfg.stride is not None:
-                w, b, gm, be = P4["stride_conv"]
-                ns = nt["stride_conv"]
-                if need_xs:
-                    parts, n = K.bn_bwd_reduce(acc, ys, sts, None)
-                    dxs, dw, db, dgm, dbe = dwbn_bwd(acc, parts, n, x, ys, sts, w, b, gm, be, tr, 3, cfg.stride, need[0], ns[0],
-                                                     ns[2] or ns[3])
-                    grads["stride_conv"] = (dw, db if ns[1] else None, dgm, dbe)
-                    dx = K.add(dxs, g) if need[0] else None
-                else:
-                    grads["stride_conv"] = (None, None, None, None)
-            else:
+                acc = pwbn_bwd(dz, xs, y_, st_, kn_, Ls[nm], ACT_NONE, tr, need_xs, acc)
+            if cfg.stride is None:
                 dx = acc if need[0] else None
-        else:
-            for nm in names:
-                grads.setdefault(nm, (None, None, None, None))
-        flat = []
-        for nm in names:
-            flat.extend(grads.get(nm, (None, None, None, None)))
-        if dth is not None:
-            dw1, db1, dw2, db2 = dth
-            flat.extend([dw1 if n_th[0] else None, db1 if n_th[1] else None, dw2 if n_th[2] else None, db2 if n_th[3] else None])
-        else:
-            flat.extend([None, None, None, None])
-        flat.extend([dtable, dls, None])
-        return (dx, None, *flat)
+            elif need_xs:
+                parts, n = K.bn_bwd_reduce(acc, ys, sts, None)
+                dxs = dwbn_bwd(acc, parts, n, x, ys, sts, Ls["stride_conv"], tr, 3, cfg.stride, need[0])
+                dx = K.add(dxs, g) if need[0] else None
+        flat = [gr for L in Ls.values() for gr in L.grads()]
+        return (dx, None, *flat, *dth, dtable, Ls["proj"].dls, None)
 
 
 # =========================================================================== downsample (conv [+ attention branch])
@@ -664,40 +663,34 @@ class DownsampleFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, cfg: DownsampleCtx, *t):
         tr, cn = cfg.training, cfg.counters
-        wc, bc, gc, bec = t[:4]
+        conv = cut_layers(("conv",), t, None, 0, {"conv": cfg.bn_conv})["conv"]
         need_bwd = any(ctx.needs_input_grad)
-        wg_nk, wg_kn = _gemm_weight(wc, x.dtype, need_bwd)
-        yc, stc = dense_conv_fwd(x, wg_nk, bc, gc, bec, cfg.bn_conv, tr, cn, 3, 2)
+        wg_nk, wg_kn = _gemm_weight(conv.w, x.dtype, need_bwd)
+        yc, stc = dense_conv_fwd(x, wg_nk, conv, tr, cn, 3, 2)
         conv_out = K.bn_act_apply(yc, stc, ACT_NONE)
         ctx.cfg = cfg
         if not cfg.attn:
             ctx.save_for_backward(x, yc, stc, wg_kn, *t)
             return conv_out
         geo = cfg.geo
-        wl, bl = t[4:6]
-        P4 = {nm: t[6 + 4 * i: 6 + 4 * i + 4] for i, nm in enumerate(_DS_ORDER)}
-        table = t[6 + 4 * len(_DS_ORDER)]
+        wl, bl, table = t[4], t[5], t[6 + 4 * len(_DS_ORDER)]
+        Ls = cut_layers(_DS_ORDER, t, None, 6, cfg.bns)
         dt = x.dtype
         N, H, W, C = x.shape
         lq, _, _ = K.dwconv_fwd(x, None, ACT_NONE, wl, 3, 2, 1, 1, (H + 1) // 2, (W + 1) // 2, stats=False)
         qin = K.subsample_add(lq, bl, x, 2)
-        kn = {}
-        w, b, gm, be = P4["q_proj"]
-        w_nk, kn["q_proj"] = _prep(w, dt, cfg.derived)
-        q, yq, stq = pwbn_fwd(qin, w_nk, b, gm, be, cfg.bns["q_proj"], tr, cn)
-        w, b, gm, be = P4["k"]
-        w_nk, kn["k"] = _prep(w, dt, cfg.derived)
-        k, yk, stk = pwbn_fwd(x, w_nk, b, gm, be, cfg.bns["k"], tr, cn)
-        w, b, gm, be = P4["v"]
-        w_nk, kn["v"] = _prep(w, dt, cfg.derived)
-        v, yv, stv = pwbn_fwd(x, w_nk, b, gm, be, cfg.bns["v"], tr, cn)
+        kn, mats = {}, {}
+        for nm, x_ in (("q_proj", qin), ("k", x), ("v", x)):
+            w_nk, kn[nm] = _prep(Ls[nm].w, dt, cfg.derived)
+            mats[nm] = pwbn_fwd(x_, w_nk, Ls[nm], tr, cn)
+        q, yq, stq = mats["q_proj"]
+        k, yk, stk = mats["k"]
+        v, yv, stv = mats["v"]
         O, S, P, T2 = attn_core_fwd(q, k, v, table, cfg.idx, None, geo)
-        w, b, gm, be = P4["v_local"]
-        yl, stl = dwbn_fwd(v, w, b, gm, be, cfg.bns["v_local"], tr, cn, 3, 2)
+        yl, stl = dwbn_fwd(v, Ls["v_local"], tr, cn, 3, 2)
         a = K.bn_add_act(yl, stl, O, ACT_GELU)
-        w, b, gm, be = P4["proj"]
-        w_nk, kn["proj"] = _prep(w, dt, cfg.derived)
-        out, yp, stp = pwbn_fwd(a, w_nk, b, gm, be, cfg.bns["proj"], tr, cn, ACT_NONE, None, conv_out, None)
+        w_nk, kn["proj"] = _prep(Ls["proj"].w, dt, cfg.derived)
+        out, yp, stp = pwbn_fwd(a, w_nk, Ls["proj"], tr, cn, ACT_NONE, conv_out, None)
         ctx.save_for_backward(x, yc, stc, wg_kn, qin, q, yq, stq, k, yk, stk, v, yv, stv, S, P, O, yl, stl, a, yp, stp,
                               kn["q_proj"], kn["k"], kn["v"], kn["proj"], *t)
         return out
@@ -706,57 +699,37 @@ class DownsampleFunction(torch.autograd.Function):
     @K.batched_sums
     def backward(ctx, g):
         cfg: DownsampleCtx = ctx.cfg
-        sv = ctx.saved_tensors
         need = ctx.needs_input_grad                   # [x, cfg, *t]
         tr = cfg.training
         g = _c(g)
         if not cfg.attn:
-            x, yc, stc, wg_kn = sv[:4]
-            wc, bc, gc, bec = sv[4:8]
+            x, yc, stc, wg_kn, *t = ctx.saved_tensors
+            conv = cut_layers(("conv",), t, need[2:], 0, None)["conv"]
             parts, n = K.bn_bwd_reduce(g, yc, stc, None)
-            dx, dw, db, dgm, dbe = dense_conv_bwd(g, parts, n, x, yc, stc, wg_kn, wc, bc, gc, bec, tr, 3, 2, need[0], need[2],
-                                                  need[4] or need[5])
-            return (dx, None, dw, db if need[3] else None, dgm, dbe)
-        (x, yc, stc, wg_kn, qin, q, yq, stq, k, yk, stk, v, yv, stv, S, P, O, yl, stl, a, yp, stp, knq, knk, knv, knp) = sv[:26]
-        t = sv[26:]
-        wc, bc, gc, bec = t[:4]
-        wl, bl = t[4:6]
-        P4 = {nm: t[6 + 4 * i: 6 + 4 * i + 4] for i, nm in enumerate(_DS_ORDER)}
-        nt = {nm: need[2 + 6 + 4 * i: 2 + 6 + 4 * i + 4] for i, nm in enumerate(_DS_ORDER)}
-        table = t[6 + 4 * len(_DS_ORDER)]
-        n_table = need[2 + 6 + 4 * len(_DS_ORDER)]
-        n_local = need[2 + 4: 2 + 6]
+            dx = dense_conv_bwd(g, parts, n, x, yc, stc, wg_kn, conv, tr, 3, 2, need[0])
+            return (dx, None, *conv.grads())
+        (x, yc, stc, wg_kn, qin, q, yq, stq, k, yk, stk, v, yv, stv, S, P, O, yl, stl, a, yp, stp, knq, knk, knv, knp,
+         *t) = ctx.saved_tensors
+        conv = cut_layers(("conv",), t, need[2:], 0, None)["conv"]
+        Ls = cut_layers(_DS_ORDER, t, need[2:], 6, None)
+        at = 6 + 4 * len(Ls)
+        wl, bl, table = t[4], t[5], t[at]
+        n_local, n_table = need[2 + 4: 2 + 6], need[2 + at]
         geo = cfg.geo
-        grads = {}
         # ---- conv branch (its BN output was the `residual` of the attention branch's last apply: gradient g)
         parts, n = K.bn_bwd_reduce(g, yc, stc, None)
-        dx, dwc, dbc, dgc, dbec = dense_conv_bwd(g, parts, n, x, yc, stc, wg_kn, wc, bc, gc, bec, tr, 3, 2, need[0], need[2],
-                                                 need[4] or need[5])
+        dx = dense_conv_bwd(g, parts, n, x, yc, stc, wg_kn, conv, tr, 3, 2, need[0])
         # ---- attention branch
-        w, b, gm, be = P4["proj"]
-        da, dw, db, dgm, dbe, _ = pwbn_bwd(g, a, yp, stp, knp, tuple(w.shape), w, b, gm, be, None, ACT_NONE, tr, True,
-                                           nt["proj"][0], nt["proj"][2] or nt["proj"][3])
-        grads["proj"] = (dw, db if nt["proj"][1] else None, dgm, dbe)
+        da = pwbn_bwd(g, a, yp, stp, knp, Ls["proj"], ACT_NONE, tr, True)
         d, parts, n = K.bn_add_act_bwd(da, yl, stl, O, ACT_GELU)
-        w, b, gm, be = P4["v_local"]
-        nv = nt["v_local"]
-        dv_loc, dw, db, dgm, dbe = dwbn_bwd(d, parts, n, v, yl, stl, w, b, gm, be, tr, 3, 2, True, nv[0], nv[2] or nv[3])
-        grads["v_local"] = (dw, db if nv[1] else None, dgm, dbe)
+        dv_loc = dwbn_bwd(d, parts, n, v, yl, stl, Ls["v_local"], tr, 3, 2, True)
         dQ, dK, dV, dtable, _ = attn_core_bwd(d, q, k, v, S, P, P, table, cfg.idx, None, geo, n_table, False)
         dVt = K.add(dV, dv_loc)
         acc = dx                                       # running sum of dx over the consumers of x
         for nm, dz, y_, st_, kn_ in (("k", dK, yk, stk, knk), ("v", dVt, yv, stv, knv)):
-            w, b, gm, be = P4[nm]
-            nn_ = nt[nm]
-            acc, dw, db, dgm, dbe, _ = pwbn_bwd(dz, x, y_, st_, kn_, tuple(w.shape), w, b, gm, be, None, ACT_NONE, tr, need[0],
-                                                nn_[0], nn_[2] or nn_[3], False, acc, None)
-            grads[nm] = (dw, db if nn_[1] else None, dgm, dbe)
-        w, b, gm, be = P4["q_proj"]
-        nq = nt["q_proj"]
+            acc = pwbn_bwd(dz, x, y_, st_, kn_, Ls[nm], ACT_NONE, tr, need[0], acc)
         need_qin = need[0] or any(n_local)
-        dqin, dw, db, dgm, dbe, _ = pwbn_bwd(dQ, qin, yq, stq, knq, tuple(w.shape), w, b, gm, be, None, ACT_NONE, tr, need_qin,
-                                             nq[0], nq[2] or nq[3])
-        grads["q_proj"] = (dw, db if nq[1] else None, dgm, dbe)
+        dqin = pwbn_bwd(dQ, qin, yq, stq, knq, Ls["q_proj"], ACT_NONE, tr, need_qin)
         dwl = dbl = None
         C = x.shape[3]
         if need_qin:
@@ -772,11 +745,8 @@ class DownsampleFunction(torch.autograd.Function):
                 K.sum_rows(parts, n, 2 * C, both)
                 slot = _slot(bl, True, (C,))
                 dbl = K.axpby(both[:C], None, 1.0, 0.0, out=slot) if slot is not None else both[:C]
-        flat = [dwc if need[2] else None, dbc if need[3] else None, dgc, dbec, dwl, dbl]
-        for nm in _DS_ORDER:
-            flat.extend(grads[nm])
-        flat.append(dtable)
-        return (acc if need[0] else None, None, *flat)
+        flat = [gr for L in Ls.values() for gr in L.grads()]
+        return (acc if need[0] else None, None, *conv.grads(), dwl, dbl, *flat, dtable)
 
 
 # =========================================================================== tail
@@ -819,21 +789,24 @@ class TailFunction(torch.autograd.Function):
         backbone = need[0] or need[1] or need[2]
         two = w_d is not None
         half = K.axpby(_c(dlogits.float()), None, 0.5, 0.0) if two else _c(dlogits.float())
-        d1, dw_h, db_h = K.linear_bwd(half, feat, w_h, backbone, need[3], need[4], _slot(w_h, need[3], (J, C)), _slot(b_h, need[4], (J,)))
+        # K.linear_bwd writes a bias gradient only next to the weight gradient: a head whose bias alone is trained asks for both
+        # (the weight gradient goes to a temporary and is dropped)
+        d1, dw_h, db_h = K.linear_bwd(half, feat, w_h, backbone, need[3] or need[4], need[4], _slot(w_h, need[3], (J, C)),
+                                      _slot(b_h, need[4], (J,)))
         d2 = dw_d = db_d = None
         if two:
-            d2, dw_d, db_d = K.linear_bwd(half, feat, w_d, backbone, need[5], need[6], _slot(w_d, need[5], (J, C)), _slot(b_d, need[6], (J,)))
-        dx = dgamma = dbeta = None
+            d2, dw_d, db_d = K.linear_bwd(half, feat, w_d, backbone, need[5] or need[6], need[6], _slot(w_d, need[5], (J, C)),
+                                          _slot(b_d, need[6], (J,)))
+        dx = None
+        norm = Layer(None, None, gamma, beta, need_gamma=need[1], need_beta=need[2])
         if backbone:
             dfeat = K.axpby(d1, d2, 1.0, 1.0) if two else d1
             dpooled = K.dropout(dfeat, drop_u, cfg.dropout) if drop_u is not None else dfeat
             dz, parts, n = K.act_bn_bwd(None, x, None, dpooled, st, ACT_NONE)
-            nb = need[1] or need[2]
-            coef, dgamma, dbeta, _, _ = K.bn_bwd_finalize_ex(parts, n, N * H * W, gamma, beta, None, st, cfg.training, nb, False,
-                                                             False, (_slot(gamma, nb, (C,)), _slot(beta, nb, (C,)), None, None))
+            coef = bn_backward(norm, parts, n, N * H * W, st, cfg.training)
             if need[0]:
                 dx = K.affine2_apply(dz, x, coef)
-        return dx, dgamma, dbeta, dw_h, db_h, dw_d, db_d, None, None
+        return dx, *norm.grads()[2:], dw_h if need[3] else None, db_h, dw_d if need[5] else None, db_d, None, None
 
 
 __all__ = ["AttentionCtx", "AttentionFunction", "AttnGeom", "ConvMlpCtx", "ConvMlpFunction", "ConvStemCtx", "ConvStemFunction",

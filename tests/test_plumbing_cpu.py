@@ -433,3 +433,49 @@ def test_bench_plain_run_leaves_the_side_measurements_to_full():
     assert full.full is True and full.eval_steps > 0 and full.profile_steps > 0 and full.extra_models
     cmd = bench.extra_model_cmd("efficientformerv2_s1", full)
     assert "--full" in cmd and cmd[cmd.index("--extra-models") + 1] == "" and cmd[cmd.index("--eval-steps") + 1] == "0"
+
+
+_STAGE_LAYOUTS = [
+    # (stage, layer names in the order the Function's docstring lists their weight / bias / bn.weight / bn.bias quads, index of the
+    #  first quad among the tensor inputs, tensor inputs in all)
+    ("ConvStemFunction", ("conv",), 0, 4),
+    ("DenseConvBNFunction", ("conv",), 0, 4),
+    ("ConvMlpFunction", ("fc1", "dw", "fc2"), 0, 14),                                            # ..., ls, row_scale
+    ("AttentionFunction", ("q", "k", "v", "v_local", "proj"), 0, 27),                            # ..., 4 talking-head, table, ls, row_scale
+    ("AttentionFunction stride 2", ("stride_conv", "q", "k", "v", "v_local", "proj"), 0, 31),
+    ("DownsampleFunction", ("conv",), 0, 4),
+    ("DownsampleFunction attention", ("q_proj", "k", "v", "v_local", "proj"), 6, 27),            # conv quad, q.local.weight, .bias first
+    ("ConvBlockFunction", ("conv1", "conv2"), 0, 10),                                            # ..., gamma, row_scale
+]
+
+
+@pytest.mark.parametrize("stage,names,offset,total", _STAGE_LAYOUTS, ids=[s[0] for s in _STAGE_LAYOUTS])
+def test_layer_records_are_cut_in_the_stages_input_order(stage, names, offset, total):
+    """vit_functions.cut_layers on labelled dummies: every name gets the four tensors and the four need flags at its place in
+    the stage's input order, and Layer.grads() masks each gradient by its own flag."""
+    from deepfakedetection_amd import vit_functions as V
+    from deepfakedetection_amd.fastervit_functions import ConvBlockFunction  # noqa: F401  (the layouts above name it)
+
+    if "Attention" in stage:
+        assert names == (V._ATT_ORDER if "stride" in stage else V._ATT_ORDER[1:])
+    if stage == "DownsampleFunction attention":
+        assert names == V._DS_ORDER
+    t = tuple(torch.tensor(float(i)) for i in range(total))
+    need = tuple((i * 7 + i // 4) % 3 != 0 for i in range(total))             # no period of 4: every quad gets its own pattern
+    bns = {nm: object() for nm in names}
+    layers = V.cut_layers(names, t, need, offset, bns)
+    assert tuple(layers) == tuple(names)
+    for i, nm in enumerate(names):
+        L, o = layers[nm], offset + 4 * i
+        assert [float(v) for v in (L.w, L.b, L.gamma, L.beta)] == [o, o + 1, o + 2, o + 3], nm
+        assert (L.need_w, L.need_b, L.need_gamma, L.need_beta) == need[o:o + 4], nm
+        assert L.bn is bns[nm] and L.ls is None and L.need_ls is False
+        assert L.need_bn == (need[o + 2] or need[o + 3])
+        assert L.grads() == (None, None, None, None)                           # nothing produced yet
+        L.dw, L.db, L.dgamma, L.dbeta = "dw", "db", "dgamma", "dbeta"
+        assert L.grads() == tuple(g if f else None for g, f in zip(("dw", "db", "dgamma", "dbeta"), need[o:o + 4])), nm
+    forward = V.cut_layers(names, t, None, offset, None)                       # a forward: tensors only, every flag False
+    for i, nm in enumerate(names):
+        L = forward[nm]
+        assert float(L.w) == offset + 4 * i and L.bn is None
+        assert not (L.need_w or L.need_b or L.need_gamma or L.need_beta or L.need_ls or L.need_any)

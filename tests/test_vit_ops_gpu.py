@@ -888,7 +888,7 @@ def test_eval_mode_backward_of_a_batchnormed_1x1_at_a_fused_shape():
     must be returned and the backward must match the eval-mode BatchNorm arithmetic."""
     from deepfakedetection_amd._lib import load
     from deepfakedetection_amd.functions import BNRef
-    from deepfakedetection_amd.vit_functions import pwbn_bwd, pwbn_fwd
+    from deepfakedetection_amd.vit_functions import Layer, pwbn_bwd, pwbn_fwd
 
     K = _k()
     n, T, Kd, N = 160, 128, 128, 256
@@ -900,10 +900,12 @@ def test_eval_mode_backward_of_a_batchnormed_1x1_at_a_fused_shape():
     rm, rv = (torch.randn(N, generator=g0) * 0.1).cuda(), (0.5 + torch.rand(N, generator=g0)).cuda()
     bn = BNRef(rm, rv, None, 0.1, 1e-5)
     w_nk, w_kn = K.prep_weights(w, torch.bfloat16, True, True)
-    out, y, st = pwbn_fwd(x, w_nk, None, gamma, beta, bn, False, None)
+    L = Layer(w, None, gamma, beta, bn, need_w=True, need_gamma=True, need_beta=True)
+    out, y, st = pwbn_fwd(x, w_nk, L, False, None)
     assert y is not None, "a BatchNormed layer lost its raw product: its eval-mode backward would dereference None"
     g = torch.randn(out.shape, generator=g0).to(torch.bfloat16).cuda()
-    dx, dw, _, dgamma, dbeta, _ = pwbn_bwd(g, x, y, st, w_kn, tuple(w.shape), w, None, gamma, beta, None, R.ACT_NONE, False, True, True, True)
+    dx = pwbn_bwd(g, x, y, st, w_kn, L, R.ACT_NONE, False, True)
+    dw, _, dgamma, dbeta = L.grads()
     # reference: eval BatchNorm is the affine map out = a * y + c with a = gamma * rstd
     xf, wf, gf = x.float().view(-1, Kd), w.view(N, Kd).to(torch.bfloat16).float(), g.float().view(-1, N)
     yf = xf @ wf.t()
