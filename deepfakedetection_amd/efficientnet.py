@@ -94,7 +94,7 @@ class HipMBConv(nn.Module):
             mod = getattr(mod, piece)
         return mod
 
-    def forward(self, x: torch.Tensor, derived: tuple | None = None, rng=None, counters: list | None = None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, derived: dict | None = None, rng=None, counters: list | None = None) -> torch.Tensor:
         """x: NHWC.  Drop-connect (efficientnet_pytorch utils.drop_connect): per-sample Bernoulli(keep) / keep, drawn
         by the Philox kernel from the owning network's device-resident state."""
         p = self.plan
@@ -104,7 +104,7 @@ class HipMBConv(nn.Module):
             row_scale = rng.drop_path_scale(x.shape[0], 1.0 - p.drop_connect, stream_id=p.index)
         return self.run(x, row_scale, derived, counters)
 
-    def run(self, x: torch.Tensor, row_scale: torch.Tensor | None, derived: tuple | None = None,
+    def run(self, x: torch.Tensor, row_scale: torch.Tensor | None, derived: dict | None = None,
             counters: list | None = None) -> torch.Tensor:
         p = self.plan
         dw, dw_bn = self.part("dw"), self.part("dw_bn")
@@ -190,49 +190,37 @@ class HipEfficientNet(HipNetwork):
         one tensor in, one tensor out, in forward order."""
         return list(self.block_list())
 
-    def forward_features_nhwc(self, x: torch.Tensor, drop_masks=None, counters: list | None = None):
-        """-> (the last block's output, the head convolution's derived (w_nk, w_kn) pair of this pass)."""
+    def forward_features_nhwc(self, x: torch.Tensor, drop_masks=None, counters: list | None = None,
+                              derived: dict | None = None) -> torch.Tensor:
+        """derived: an empty dict that receives this pass's derived-weight table (_forward hands it on to the head)."""
         stem, stem_bn, blocks, _, _, _ = self._parts()
         xh = self.nhwc_input(x)
         dt = compute_dtype()
         h = StemFunction.apply(xh, stem.weight, stem_bn.weight, stem_bn.bias,
                                StemCtx(self.plan.stem, _bnref(stem_bn), dt, self.training, counters))
-        derived = self._derived_weights(dt)
+        derived = derived if derived is not None else {}
+        derived.update(self._derived_weights(dt))
         rng = self.rng(x.device) if self.training else None
         for i, blk in enumerate(blocks):
-            h = blk(h, derived[i], rng, counters) if drop_masks is None else blk.run(h, drop_masks[i], derived[i], counters)
-        return h, derived[len(blocks)]
+            h = blk(h, derived, rng, counters) if drop_masks is None else blk.run(h, drop_masks[i], derived, counters)
+        return h
 
-    def _derived_weights(self, dt: torch.dtype) -> list:
-        """One batched launch per forward refreshes every derived weight of the network (1x1 conv weights in
-        the activation dtype as [N][K] and [K][N], [R][C] copies of the squeeze-excite expand weights);
-        returns, per block, ((wexp_nk, wexp_kn) | None, (wproj_nk, wproj_kn), se_w2t) and last the head's pair.
-        The buffers and the job list are rebuilt only when a parameter moved (e.g. after .to())."""
+    def _derived_weights(self, dt: torch.dtype) -> dict:
+        """{weight.data_ptr(): (w_nk, w_kn)} for every expand, project and head 1x1 convolution in the activation dtype, and
+        (None, the f32 [R][C] copy) for every squeeze-excite expand weight, refreshed by ONE batched launch per forward pass
+        (HipNetwork._derived).  The buffers and the job list are rebuilt only when a parameter moved (e.g. after .to())."""
         from . import kernels as K
 
         _, _, blocks, head, _, _ = self._parts()
-        items, layout = [], []
+        items = []
         for blk in blocks:
-            p = blk.plan
-            if p.expand:
+            if blk.plan.expand:
                 items.append((blk.part("expand").weight, True, True, False))
             items.append((blk.part("project").weight, True, True, False))
             items.append((blk.part("se_expand").weight, False, True, True))
-            layout.append(p.expand)
         items.append((head.weight, True, True, False))
         pairs = self._derived(dt, [it[0] for it in items], lambda: K.DerivedWeights(items, dt))
-        out, at = [], 0
-        for has_exp in layout:
-            exp = None
-            if has_exp:
-                exp = pairs[at]
-                at += 1
-            proj = pairs[at]
-            w2t = pairs[at + 1][1]
-            at += 2
-            out.append((exp, proj, w2t))
-        out.append(pairs[at])
-        return out
+        return {it[0].data_ptr(): pair for it, pair in zip(items, pairs)}
 
     def forward(self, x: torch.Tensor, drop_masks=None, dropout_u: torch.Tensor | None = None) -> torch.Tensor:
         """drop_masks / dropout_u let a test inject the stochastic-depth masks (already
@@ -243,14 +231,15 @@ class HipEfficientNet(HipNetwork):
     def _forward(self, x: torch.Tensor, drop_masks=None, dropout_u: torch.Tensor | None = None) -> torch.Tensor:
         _, _, _, head, head_bn, fc = self._parts()
         counters: list = []                 # owned by this call: num_batches_tracked of every BatchNorm that ran
-        h, head_derived = self.forward_features_nhwc(x, drop_masks, counters)
+        derived: dict = {}
+        h = self.forward_features_nhwc(x, drop_masks, counters, derived)
         u = dropout_u
         if u is None and self.training and self.drop_rate > 0 and drop_masks is None:
             u = self.rng(h.device).uniform(h.shape[0] * head.out_channels, stream_id=1 << 20).view(h.shape[0], head.out_channels)
         if head._forward_hooks or head._forward_pre_hooks:
             out = self._hooked_head(h, head, head_bn, fc)
         else:
-            cfg = HeadCtx(_bnref(head_bn), self.drop_rate, self.training, head_derived, counters)
+            cfg = HeadCtx(_bnref(head_bn), self.drop_rate, self.training, derived, counters)
             out = HeadFunction.apply(h, head.weight, head_bn.weight, head_bn.bias, fc.weight, fc.bias, u, cfg)
         self.end_pass(counters, h.device)
         return out

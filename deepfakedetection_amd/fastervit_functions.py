@@ -26,8 +26,8 @@ import torch
 
 from . import kernels as K
 from ._lib import ACT_GELU, ACT_NONE, ACT_RELU
-from .functions import BNRef, _bn_state, _c
-from .vit_functions import Layer, _gemm_weight, _partial_rows, _prep, _rows, _slot, bn_backward, cut_layers, pwbn_bwd, pwbn_fwd
+from .functions import BNRef, Layer, _bn_state, _c, _prep, _rows, _slot, bn_backward, cut_layers
+from .vit_functions import _gemm_weight, _partial_rows, pwbn_bwd, pwbn_fwd
 
 _ident_cache: dict = {}
 
@@ -356,8 +356,8 @@ def mlp_sub_bwd(g, saved, P, ls, row_scale, need: dict, need_dx: bool):
         parts, n = K.bn_bwd_reduce(gb, y2, st2, None)
         ones2, _ = ident(dev, C)
         outs = (None, _slot(P["fc2_b"], need["fc2_b"], (C,)), _slot(ls, need["ls"], (C,)), None)
-        coef2, _, db2, dls, _ = K.bn_bwd_finalize_ex(parts, n, _rows(y2), ones2, P["fc2_b"], ls, st2, False, need["fc2_b"] or True,
-                                                     need["ls"], False, outs)
+        coef2, _, db2, dls, _ = K.bn_bwd_finalize(parts, n, _rows(y2), ones2, P["fc2_b"], ls, st2, False, need["fc2_b"] or True,
+                                                  need["ls"], False, outs)
         grads["fc2_b"], grads["ls"] = (db2 if need["fc2_b"] else None), dls
         dz2 = K.affine2_apply(gb, y2, coef2)
     upstream = need_dx or any(need[k] for k in ("ln_w", "ln_b", "fc1_w", "fc1_b"))

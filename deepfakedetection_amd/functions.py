@@ -9,6 +9,10 @@ re-derives activations from the saved raw tensors the same way and uses the iden
     d(conv out) = a[c]*dz + b[c]*y + c[c]
 for training-mode BatchNorm, so BN-backward is also folded into the consumers.
 
+This module also holds what the stages of all three families share (vit_functions.py and fastervit_functions.py import it):
+the `Layer` record of one "conv (+bias) + BatchNorm [+ LayerScale]" layer, `cut_layers` which cuts a stage's tensor inputs
+into such records, `bn_backward`, the gradient-arena look-up `_slot` and the derived-weight look-up `_prep`.
+
 Stage arithmetic mirrors efficientnet_pytorch 0.7.1 `MBConvBlock.forward` /
 timm 1.0.20 `InvertedResidual.forward` (reference call sites:
 trainers/efficientnet.py:297,302; orchestration/orchestrator.py:529,590).
@@ -109,16 +113,92 @@ def _c(t: torch.Tensor) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
-def _ptrs(*tensors) -> tuple[int, ...]:
-    """Addresses of a Function's tensor inputs: keys into the gradient arena."""
-    return tuple(t.data_ptr() if isinstance(t, torch.Tensor) else 0 for t in tensors)
-
-
-def _dest(ctx, index: int, shape):
-    """Arena slot for input `index` if that input wants a gradient and owns a free slot."""
-    if not ctx.needs_input_grad[index] or not ctx.pptr[index]:
+def _slot(t: torch.Tensor | None, need: bool, shape):
+    """Gradient-arena slot of parameter `t` if it wants a gradient and its slot is free."""
+    if not need or t is None:
         return None
-    return grad_dest(ctx.pptr[index], shape)
+    return grad_dest(t.data_ptr(), shape)
+
+
+def _rows(t: torch.Tensor) -> int:
+    return t.numel() // t.shape[-1]
+
+
+@dataclass
+class Layer:
+    """One "conv (+bias) + BatchNorm [+ LayerScale]" layer of a stage: its tensors, one need flag per tensor (all False in a
+    forward, where only the tensors matter) and the gradients its backward produced.  A plain record: built afresh from the
+    arguments in `forward` and from ctx.saved_tensors in `backward`, never kept on ctx."""
+
+    w: torch.Tensor | None
+    b: torch.Tensor | None
+    gamma: torch.Tensor
+    beta: torch.Tensor | None
+    bn: BNRef | None = None
+    ls: torch.Tensor | None = None
+    need_w: bool = False
+    need_b: bool = False
+    need_gamma: bool = False
+    need_beta: bool = False
+    need_ls: bool = False
+    dw: torch.Tensor | None = None
+    db: torch.Tensor | None = None
+    dgamma: torch.Tensor | None = None
+    dbeta: torch.Tensor | None = None
+    dls: torch.Tensor | None = None
+
+    @property
+    def need_bn(self) -> bool:
+        """gamma and beta share one launch flag: the kernel writes both."""
+        return self.need_gamma or self.need_beta
+
+    @property
+    def need_any(self) -> bool:
+        return self.need_w or self.need_b or self.need_bn
+
+    def grads(self, bias: bool = True):
+        """(dw, db, dgamma, dbeta) in input order, each masked by its own flag; bias=False: without db (see cut_layers)."""
+        db = (self.db if self.need_b else None,) if bias else ()
+        return (self.dw if self.need_w else None, *db,
+                self.dgamma if self.need_gamma else None, self.dbeta if self.need_beta else None)
+
+
+def cut_layers(names, t, need, offset: int, bns, bias: bool = True) -> dict[str, Layer]:
+    """{name: Layer} for the (weight, bias, bn.weight, bn.bias) quads that start at t[offset], one per name.
+    need: the slice of ctx.needs_input_grad that lines up with t (None in a forward); bns: name -> BNRef, or None.
+    bias=False: the stage's convolutions have no bias and its inputs are (weight, bn.weight, bn.bias) triples; Layer.b is None."""
+    out, width = {}, 4 if bias else 3
+    for i, nm in enumerate(names):
+        o = offset + width * i
+        q, flags = list(t[o: o + width]), list(need[o: o + width]) if need is not None else [False] * width
+        if not bias:
+            q.insert(1, None)
+            flags.insert(1, False)
+        out[nm] = Layer(*q, bns[nm] if bns is not None else None, None, *flags)
+    return out
+
+
+def bn_backward(L: Layer, parts, n, rows: int, st, training: bool):
+    """The BatchNorm-backward coefficients of L from the partial sums; dgamma, dbeta, dls and the convolution-bias gradient land
+    on L — in their gradient-arena slots, each claimed only when this launch really writes it."""
+    C = L.gamma.numel()
+    nb, want_ls, want_b = L.need_bn, L.need_ls and L.ls is not None, L.need_b and L.b is not None
+    outs = (_slot(L.gamma, nb, (C,)), _slot(L.beta, nb, (C,)), _slot(L.ls, want_ls, (C,)), _slot(L.b, want_b, (C,)))
+    coef, L.dgamma, L.dbeta, L.dls, L.db = K.bn_bwd_finalize(parts, n, rows, L.gamma, L.beta, L.ls, st, training, nb, want_ls,
+                                                             want_b, outs)
+    return coef
+
+
+def _prep(w: torch.Tensor, dt: torch.dtype, derived, need_bwd: bool = True):
+    """(w_nk, w_kn) of a 1x1 convolution weight [O, I, 1, 1] (or a 2-D GEMM weight) in the activation dtype.
+    derived: {weight.data_ptr(): (w_nk, w_kn)} refreshed for the whole network by one batched launch per forward
+    (kernels.DerivedWeights; w_nk a kernels.MxWeight with FasterViT's fp8 weights), or None: prepare this layer on the spot.
+    An entry of another dtype than `dt` (a table handed on into another autocast region) is not used."""
+    if derived is not None:
+        hit = derived.get(w.data_ptr())
+        if hit is not None and (isinstance(hit[0], K.MxWeight) or hit[0].dtype == dt):
+            return hit
+    return K.prep_weights(w, dt, True, need_bwd)
 
 
 # =========================================================================== stem
@@ -143,26 +223,21 @@ class StemFunction(torch.autograd.Function):
         st = _bn_state(parts, n, N * Ho * Wo, cfg.bn, gamma, beta, cfg.training, cfg.counters)
         out = K.bn_act_apply(y, st, ACT_SILU)
         ctx.cfg = cfg
-        ctx.pptr = _ptrs(x, weight, gamma, beta)
-        ctx.save_for_backward(x, y, st, gamma)
+        ctx.save_for_backward(x, y, st, weight, gamma, beta)
         return out
 
     @staticmethod
     def backward(ctx, g):
         cfg: StemCtx = ctx.cfg
-        x, y, st, gamma = ctx.saved_tensors
+        x, y, st, *t = ctx.saved_tensors
+        L = cut_layers(("conv",), t, ctx.needs_input_grad[1:], 0, None, bias=False)["conv"]
         geom = cfg.geom
-        N, Ho, Wo, _ = y.shape
         dz, parts, n = K.act_bn_bwd(_c(g), y, None, None, st, ACT_SILU)
-        want_bn = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
-        C = gamma.numel()
-        coef, dgamma, dbeta = K.bn_bwd_finalize(parts, n, N * Ho * Wo, gamma, st, cfg.training, want_bn,
-                                                _dest(ctx, 2, (C,)), _dest(ctx, 3, (C,)))
-        dw = None
-        if ctx.needs_input_grad[1]:
-            dw = K.stem_conv_wgrad(x, dz, y, coef, geom.kernel, geom.stride, geom.pad_lead, geom.pad_lead,
-                                   _dest(ctx, 1, (C, 3, geom.kernel, geom.kernel)))
-        return None, dw, dgamma, dbeta, None
+        coef = bn_backward(L, parts, n, _rows(y), st, cfg.training)
+        if L.need_w:
+            L.dw = K.stem_conv_wgrad(x, dz, y, coef, geom.kernel, geom.stride, geom.pad_lead, geom.pad_lead,
+                                     _slot(L.w, True, tuple(L.w.shape)))
+        return (None, *L.grads(bias=False), None)
 
 
 # =========================================================================== MBConv
@@ -175,13 +250,30 @@ class MBConvCtx:
     bn_dw: BNRef
     bn_project: BNRef
     training: bool
-    # derived weights prepared for the whole network in one launch (kernels.DerivedWeights):
-    # ((wexp_nk, wexp_kn) | None, (wproj_nk, wproj_kn), se_w2t); None: prepare per layer
-    derived: tuple | None = None
+    derived: dict | None = None           # see _prep; the squeeze-excite expand weight's entry is (None, se_w2t): _se_w2t
     counters: list | None = None          # see _bn_state
     # autograd state at the call site (inside Function.forward grad mode is always off, and needs_input_grad reflects
     # requires_grad alone): False under no_grad / inference_mode, where nothing has to be kept for a backward pass
     grad_enabled: bool = True
+
+
+def _mb_layers(t, need, cfg: MBConvCtx):
+    """(expand, dw, project) records and the four squeeze-excite tensors of MBConvFunction's tensor inputs `t` behind x."""
+    bns = {"expand": cfg.bn_expand, "dw": cfg.bn_dw, "project": cfg.bn_project}
+    Ls = cut_layers(("expand", "dw"), t, need, 0, bns, bias=False) | cut_layers(("project",), t, need, 10, bns, bias=False)
+    return *Ls.values(), t[6:10]
+
+
+def _se_mats(se):
+    """The squeeze-excite weights [R, C, 1, 1], [C, R, 1, 1] as matrices, with their biases."""
+    return se[0].reshape(se[0].shape[0], -1), se[1], se[2].reshape(se[2].shape[0], -1), se[3]
+
+
+def _se_w2t(w: torch.Tensor, derived) -> torch.Tensor | None:
+    """The f32 [R][C] copy of the squeeze-excite expand weight from the network's derived-weight table (see _prep; its entry
+    holds no w_nk); None: kernels.se_fwd makes it."""
+    hit = derived.get(w.data_ptr()) if derived is not None else None
+    return hit[1] if hit is not None else None
 
 
 class MBConvFunction(torch.autograd.Function):
@@ -194,6 +286,8 @@ class MBConvFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w_exp, g_exp, b_exp, w_dw, g_dw, b_dw, se_w1, se_b1, se_w2, se_b2, w_proj, g_proj, b_proj,
                 row_scale, cfg: MBConvCtx):
+        t = (w_exp, g_exp, b_exp, w_dw, g_dw, b_dw, se_w1, se_b1, se_w2, se_b2, w_proj, g_proj, b_proj)
+        exp, dw, proj, se = _mb_layers(t, None, cfg)
         tr = cfg.training
         N, H, W, Cin = x.shape
         dt = x.dtype
@@ -201,38 +295,33 @@ class MBConvFunction(torch.autograd.Function):
         Ho, Wo = geom.out_size(H), geom.out_size(W)
         need_bwd = any(ctx.needs_input_grad)   # grad mode is off inside forward(); this is the autograd view
         if not tr and not (need_bwd and cfg.grad_enabled) and eval_fused_enabled(
-                N * H * W * (w_exp.shape[0] if cfg.expand else Cin), dt):
-            return MBConvFunction._forward_eval(x, w_exp, g_exp, b_exp, w_dw, g_dw, b_dw, se_w1, se_b1, se_w2, se_b2, w_proj,
-                                                g_proj, b_proj, cfg, Ho, Wo)
+                N * H * W * (exp.w.shape[0] if cfg.expand else Cin), dt):
+            return MBConvFunction._forward_eval(x, exp, dw, proj, se, cfg, Ho, Wo)
         if cfg.expand:
-            wexp_nk, wexp_kn = cfg.derived[0] if cfg.derived is not None else K.prep_weights(w_exp, dt, True, need_bwd)
+            wexp_nk, wexp_kn = _prep(exp.w, dt, cfg.derived, need_bwd)
             y1, parts, n = K.pwconv(x, None, wexp_nk, None, stats=tr)
-            st1 = _bn_state(parts, n, N * H * W, cfg.bn_expand, g_exp, b_exp, tr, cfg.counters)
-            y2, parts, n = K.dwconv_fwd(y1, st1, ACT_SILU, w_dw, geom.kernel, geom.stride, geom.pad_lead, geom.pad_lead,
+            st1 = _bn_state(parts, n, N * H * W, exp.bn, exp.gamma, exp.beta, tr, cfg.counters)
+            y2, parts, n = K.dwconv_fwd(y1, st1, ACT_SILU, dw.w, geom.kernel, geom.stride, geom.pad_lead, geom.pad_lead,
                                         Ho, Wo, stats=tr)
         else:
             wexp_kn, y1, st1 = None, None, None
-            y2, parts, n = K.dwconv_fwd(x, None, ACT_NONE, w_dw, geom.kernel, geom.stride, geom.pad_lead, geom.pad_lead,
+            y2, parts, n = K.dwconv_fwd(x, None, ACT_NONE, dw.w, geom.kernel, geom.stride, geom.pad_lead, geom.pad_lead,
                                         Ho, Wo, stats=tr)
-        st2 = _bn_state(parts, n, N * Ho * Wo, cfg.bn_dw, g_dw, b_dw, tr, cfg.counters)
-        w1, w2 = se_w1.reshape(se_w1.shape[0], -1), se_w2.reshape(se_w2.shape[0], -1)
-        pooled, hpre, gate, w2t = K.se_fwd(y2, st2, ACT_SILU, w1, se_b1, w2, se_b2, ACT_SILU,
-                                           cfg.derived[2] if cfg.derived is not None else None)
-        wproj_nk, wproj_kn = cfg.derived[1] if cfg.derived is not None else K.prep_weights(w_proj, dt, True, need_bwd)
+        st2 = _bn_state(parts, n, N * Ho * Wo, dw.bn, dw.gamma, dw.beta, tr, cfg.counters)
+        pooled, hpre, gate, w2t = K.se_fwd(y2, st2, ACT_SILU, *_se_mats(se), ACT_SILU, _se_w2t(se[2], cfg.derived))
+        wproj_nk, wproj_kn = _prep(proj.w, dt, cfg.derived, need_bwd)
         pro = K.pro_bn_act_gate(st2, ACT_SILU, gate, Ho * Wo)
         y3, parts, n = K.pwconv(y2, pro, wproj_nk, None, stats=tr)
-        st3 = _bn_state(parts, n, N * Ho * Wo, cfg.bn_project, g_proj, b_proj, tr, cfg.counters)
+        st3 = _bn_state(parts, n, N * Ho * Wo, proj.bn, proj.gamma, proj.beta, tr, cfg.counters)
         out = K.bn_act_apply(y3, st3, ACT_NONE, x if cfg.skip else None, row_scale if cfg.skip else None)
         ctx.cfg = cfg
-        ctx.pptr = _ptrs(x, w_exp, g_exp, b_exp, w_dw, g_dw, b_dw, se_w1, se_b1, se_w2, se_b2, w_proj, g_proj, b_proj)
-        ctx.in_shape = (N, H, W, Cin)
         ctx.has_rs = cfg.skip and row_scale is not None
-        ctx.save_for_backward(x, y1, y2, y3, st1, st2, st3, pooled, hpre, gate, wexp_kn, wproj_kn, w_dw, w1, w2t,
-                              g_exp, g_dw, g_proj, row_scale if ctx.has_rs else None)
+        ctx.save_for_backward(x, y1, y2, y3, st1, st2, st3, pooled, hpre, gate, wexp_kn, wproj_kn, w2t, *t,
+                              row_scale if ctx.has_rs else None)
         return out
 
     @staticmethod
-    def _forward_eval(x, w_exp, g_exp, b_exp, w_dw, g_dw, b_dw, se_w1, se_b1, se_w2, se_b2, w_proj, g_proj, b_proj, cfg, Ho, Wo):
+    def _forward_eval(x, exp: Layer, dw: Layer, proj: Layer, se, cfg, Ho, Wo):
         """Inference form (running statistics, nothing kept for a backward pass): every BatchNorm is an affine map known up
         front, so each PRODUCER stores its activated output and the depthwise kernel also leaves the squeeze-excite channel
         sums — no consumer prologues, no pooling pass.  Per stage the values are those of the reference's autocast graph
@@ -243,97 +332,84 @@ class MBConvFunction(torch.autograd.Function):
         geom = cfg.dw
         a1 = x
         if cfg.expand:
-            wexp_nk, _ = cfg.derived[0] if cfg.derived is not None else K.prep_weights(w_exp, dt, True, False)
-            st1 = _bn_state(None, 0, N * H * W, cfg.bn_expand, g_exp, b_exp, False, cfg.counters)
+            wexp_nk, _ = _prep(exp.w, dt, cfg.derived, False)
+            st1 = _bn_state(None, 0, N * H * W, exp.bn, exp.gamma, exp.beta, False, cfg.counters)
             a1 = K.pwconv_eval(x, wexp_nk, st1, ACT_SILU)
-        st2 = _bn_state(None, 0, N * Ho * Wo, cfg.bn_dw, g_dw, b_dw, False, cfg.counters)
-        a2, pool_parts, _ = K.dwconv_eval(a1, w_dw, st2, ACT_SILU, geom.kernel, geom.stride, geom.pad_lead, geom.pad_lead, Ho, Wo)
-        w1, w2 = se_w1.reshape(se_w1.shape[0], -1), se_w2.reshape(se_w2.shape[0], -1)
-        _, gate, _ = K.se_fwd_parts(pool_parts, Ho * Wo, w1, se_b1, w2, se_b2, ACT_SILU,
-                                    cfg.derived[2] if cfg.derived is not None else None)
-        wproj_nk, _ = cfg.derived[1] if cfg.derived is not None else K.prep_weights(w_proj, dt, True, False)
+        st2 = _bn_state(None, 0, N * Ho * Wo, dw.bn, dw.gamma, dw.beta, False, cfg.counters)
+        a2, pool_parts, _ = K.dwconv_eval(a1, dw.w, st2, ACT_SILU, geom.kernel, geom.stride, geom.pad_lead, geom.pad_lead, Ho, Wo)
+        _, gate, _ = K.se_fwd_parts(pool_parts, Ho * Wo, *_se_mats(se), ACT_SILU, _se_w2t(se[2], cfg.derived))
+        wproj_nk, _ = _prep(proj.w, dt, cfg.derived, False)
         pro = K.pro_bn_act_gate(K.identity_state(x.device, a2.shape[3]), ACT_NONE, gate, Ho * Wo)     # gate only
         y3, _, _ = K.pwconv(a2, pro, wproj_nk, None, stats=False)
-        st3 = _bn_state(None, 0, N * Ho * Wo, cfg.bn_project, g_proj, b_proj, False, cfg.counters)
+        st3 = _bn_state(None, 0, N * Ho * Wo, proj.bn, proj.gamma, proj.beta, False, cfg.counters)
         return K.bn_act_apply(y3, st3, ACT_NONE, x if cfg.skip else None, None)
 
     @staticmethod
+    @K.batched_sums                 # the three weight gradients' final sums: one pair of launches at the end of the block
     def backward(ctx, g):
         cfg: MBConvCtx = ctx.cfg
-        (x, y1, y2, y3, st1, st2, st3, pooled, hpre, gate, wexp_kn, wproj_kn, w_dw, w1, w2t,
-         g_exp, g_dw, g_proj, row_scale) = ctx.saved_tensors
+        x, y1, y2, y3, st1, st2, st3, pooled, hpre, gate, wexp_kn, wproj_kn, w2t, *t, row_scale = ctx.saved_tensors
         need = ctx.needs_input_grad
+        exp, dw, proj, se = _mb_layers(t, need[1:], cfg)
         tr = cfg.training
         geom = cfg.dw
-        N, H, W, Cin = ctx.in_shape
+        N, H, W, Cin = x.shape
         _, Ho, Wo, Cmid = y2.shape
-        with K.sum_batch():        # the three weight gradients' final sums: one pair of launches at the end of the block
-            return MBConvFunction._backward(ctx, g, cfg, x, y1, y2, y3, st1, st2, st3, pooled, hpre, gate, wexp_kn, wproj_kn,
-                                            w_dw, w1, w2t, g_exp, g_dw, g_proj, row_scale, need, tr, geom, N, H, W, Cin, Ho, Wo, Cmid)
-
-    @staticmethod
-    def _backward(ctx, g, cfg, x, y1, y2, y3, st1, st2, st3, pooled, hpre, gate, wexp_kn, wproj_kn, w_dw, w1, w2t, g_exp, g_dw,
-                  g_proj, row_scale, need, tr, geom, N, H, W, Cin, Ho, Wo, Cmid):
         g = _c(g)
         gb = K.scale_rows(g, row_scale) if ctx.has_rs else g
         # ---- project BN backward, folded into the two GEMMs that consume dy3
         parts, n = K.bn_bwd_reduce(gb, y3, st3, None)
-        Cout, R = y3.shape[3], w1.shape[0]
-        coef3, dg_proj, db_proj = K.bn_bwd_finalize(parts, n, N * Ho * Wo, g_proj, st3, tr, need[12] or need[13],
-                                                    _dest(ctx, 12, (Cout,)), _dest(ctx, 13, (Cout,)))
+        Cout, R = y3.shape[3], se[0].shape[0]
+        w1 = se[0].reshape(R, -1)
+        coef3 = bn_backward(proj, parts, n, N * Ho * Wo, st3, tr)
         # the BN-backward-mapped gradient [rows][Cout] is materialised once for its two GEMMs: as a prologue it is re-evaluated
         # (and y3 re-read) per 128-column tile of the Cmid-wide data gradient (B0: 13.99 -> 13.90 ms per step; same bits)
         gm3 = K.affine2_apply(gb, y3, coef3)
         D, _, _ = K.pwconv(gm3, None, wproj_kn, None, stats=False)                   # d(act*gate) [.., Cmid]
-        dw_proj = None
-        if need[11]:
+        if proj.need_w:
             pro_q = K.pro_bn_act_gate(st2, ACT_SILU, gate, Ho * Wo)
-            dw_proj = K.pwconv_wgrad(gm3, None, y2, pro_q, _dest(ctx, 11, (Cout, Cmid))).view(Cout, Cmid, 1, 1)
+            proj.dw = K.pwconv_wgrad(gm3, None, y2, pro_q, _slot(proj.w, True, (Cout, Cmid))).view(Cout, Cmid, 1, 1)
         # ---- squeeze-excite backward
-        want_se = need[7] or need[8] or need[9] or need[10]
-        se_outs = (_dest(ctx, 7, (R, Cmid)), _dest(ctx, 8, (R,)), _dest(ctx, 9, (Cmid, R)), _dest(ctx, 10, (Cmid,)))
+        need_se = need[7:11]
+        se_outs = tuple(_slot(p, nd, shape) for p, nd, shape in zip(se, need_se, ((R, Cmid), (R,), (Cmid, R), (Cmid,))))
         # the FC weight gradients (read by the optimizer only) ride along with the next launch instead of being one of their own
-        se_res = K.se_bwd(D, y2, st2, ACT_SILU, gate, hpre, pooled, w1, w2t, ACT_SILU, want_se, se_outs, defer_wgrad=True)
+        se_res = K.se_bwd(D, y2, st2, ACT_SILU, gate, hpre, pooled, w1, w2t, ACT_SILU, any(need_se), se_outs, defer_wgrad=True)
         dpooled, dw1, db1, dw2, db2 = se_res[:5]
         se_job = se_res[5]
         # ---- SiLU' and depthwise BN backward
         dz2, parts, n = K.act_bn_bwd(D, y2, gate, dpooled, st2, ACT_SILU, se_job=se_job)
         if dw1 is not None:
             dw1, dw2 = dw1.view(dw1.shape[0], -1, 1, 1), dw2.view(dw2.shape[0], -1, 1, 1)
-        coef2, dg_dw, db_dw = K.bn_bwd_finalize(parts, n, N * Ho * Wo, g_dw, st2, tr, need[5] or need[6],
-                                                _dest(ctx, 5, (Cmid,)), _dest(ctx, 6, (Cmid,)))
-        kk = geom.kernel
-        dw_dw = dx = dw_exp = dg_exp = db_exp = None
+        coef2 = bn_backward(dw, parts, n, N * Ho * Wo, st2, tr)
+        dx = None
         if cfg.expand:
-            dz1, parts, n = K.dwconv_bwd_data(dz2, y2, coef2, w_dw, y1, st1, ACT_SILU, y1.shape, geom.kernel,
+            dz1, parts, n = K.dwconv_bwd_data(dz2, y2, coef2, dw.w, y1, st1, ACT_SILU, y1.shape, geom.kernel,
                                               geom.stride, geom.pad_lead, geom.pad_lead)
-            coef1, dg_exp, db_exp = K.bn_bwd_finalize(parts, n, N * H * W, g_exp, st1, tr, need[2] or need[3],
-                                                      _dest(ctx, 2, (Cmid,)), _dest(ctx, 3, (Cmid,)))
+            coef1 = bn_backward(exp, parts, n, N * H * W, st1, tr)
             pro_dy1 = K.pro_affine2(y1, coef1)
             # blocks 1-3: data and weight gradient of the expand layer from ONE pass over (dz1, y1), the widest tensors of the
             # network (csrc/dfd_pwtnw.hip, DG) — bit-identical to the two kernels below
-            both = K.pwconv_bwd_fused(dz1, y1, coef1, x, wexp_kn, g if cfg.skip else None, _dest(ctx, 1, (Cmid, Cin))) \
-                if (need[0] and need[1] and K.pwconv_bwd_fused_ok(dz1, x)) else None
-            if need[4]:
-                dw_dw = K.dwconv_bwd_weight(dz2, y2, coef2, y1, st1, ACT_SILU, geom.kernel, geom.stride,
-                                            geom.pad_lead, geom.pad_lead, _dest(ctx, 4, (Cmid, 1, kk, kk)))
-            if need[1] and both is None:
-                dw_exp = K.pwconv_wgrad(dz1, pro_dy1, x, None, _dest(ctx, 1, (Cmid, Cin))).view(Cmid, Cin, 1, 1)
+            both = K.pwconv_bwd_fused(dz1, y1, coef1, x, wexp_kn, g if cfg.skip else None, _slot(exp.w, True, (Cmid, Cin))) \
+                if (need[0] and exp.need_w and K.pwconv_bwd_fused_ok(dz1, x)) else None
+            if dw.need_w:
+                dw.dw = K.dwconv_bwd_weight(dz2, y2, coef2, y1, st1, ACT_SILU, geom.kernel, geom.stride,
+                                            geom.pad_lead, geom.pad_lead, _slot(dw.w, True, tuple(dw.w.shape)))
+            if exp.need_w and both is None:
+                exp.dw = K.pwconv_wgrad(dz1, pro_dy1, x, None, _slot(exp.w, True, (Cmid, Cin))).view(Cmid, Cin, 1, 1)
             if both is not None:
-                dx, dw_exp = both[0], both[1].view(Cmid, Cin, 1, 1)
+                dx, exp.dw = both[0], both[1].view(Cmid, Cin, 1, 1)
             elif need[0]:
                 dx, _, _ = K.pwconv(dz1, pro_dy1, wexp_kn, g if cfg.skip else None, stats=False)
         else:
-            if need[4]:
-                dw_dw = K.dwconv_bwd_weight(dz2, y2, coef2, x, None, ACT_NONE, geom.kernel, geom.stride,
-                                            geom.pad_lead, geom.pad_lead, _dest(ctx, 4, (Cmid, 1, kk, kk)))
+            if dw.need_w:
+                dw.dw = K.dwconv_bwd_weight(dz2, y2, coef2, x, None, ACT_NONE, geom.kernel, geom.stride,
+                                            geom.pad_lead, geom.pad_lead, _slot(dw.w, True, tuple(dw.w.shape)))
             if need[0]:
-                dx, _, _ = K.dwconv_bwd_data(dz2, y2, coef2, w_dw, None, None, ACT_NONE, ctx.in_shape, geom.kernel,
+                dx, _, _ = K.dwconv_bwd_data(dz2, y2, coef2, dw.w, None, None, ACT_NONE, tuple(x.shape), geom.kernel,
                                              geom.stride, geom.pad_lead, geom.pad_lead)
                 if cfg.skip:
                     dx = K.add(dx, g)
-        return (dx, dw_exp, dg_exp, db_exp, dw_dw, dg_dw, db_dw, dw1, db1, dw2, db2, dw_proj, dg_proj, db_proj,
-                None, None)
+        return (dx, *exp.grads(bias=False), *dw.grads(bias=False), dw1, db1, dw2, db2, *proj.grads(bias=False), None, None)
 
 
 # =========================================================================== head
@@ -342,7 +418,7 @@ class HeadCtx:
     bn: BNRef
     dropout: float
     training: bool
-    derived: tuple | None = None          # (w_nk, w_kn) from kernels.DerivedWeights, or None
+    derived: dict | None = None           # see _prep
     counters: list | None = None          # see _bn_state
 
 
@@ -353,41 +429,41 @@ class HeadFunction(torch.autograd.Function):
     def forward(ctx, x, w_head, gamma, beta, w_fc, b_fc, drop_u, cfg: HeadCtx):
         N, H, W, Cin = x.shape
         need_bwd = any(ctx.needs_input_grad)
-        w_nk, w_kn = cfg.derived if cfg.derived is not None else K.prep_weights(w_head, x.dtype, True, need_bwd)
+        w_nk, w_kn = _prep(w_head, x.dtype, cfg.derived, need_bwd)
         y, parts, n = K.pwconv(x, None, w_nk, None, stats=cfg.training)
         st = _bn_state(parts, n, N * H * W, cfg.bn, gamma, beta, cfg.training, cfg.counters)
         pooled = K.pool_act(y, st, ACT_SILU)
         feat = K.dropout(pooled, drop_u, cfg.dropout) if drop_u is not None else pooled
         logits = K.linear_fwd(feat, w_fc, b_fc)
         ctx.cfg = cfg
-        ctx.pptr = _ptrs(x, w_head, gamma, beta, w_fc, b_fc)
-        ctx.has_bias = b_fc is not None
-        ctx.save_for_backward(x, y, st, feat, w_kn, w_fc, gamma, drop_u)
+        ctx.save_for_backward(x, y, st, feat, w_kn, w_head, gamma, beta, w_fc, b_fc, drop_u)
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
         cfg: HeadCtx = ctx.cfg
-        x, y, st, feat, w_kn, w_fc, gamma, drop_u = ctx.saved_tensors
+        x, y, st, feat, w_kn, *t, w_fc, b_fc, drop_u = ctx.saved_tensors
         need = ctx.needs_input_grad
-        N, H, W, Cin = x.shape
-        Chead = y.shape[3]
-        backbone = need[0] or need[1] or need[2] or need[3]
+        head = cut_layers(("head",), t, need[1:], 0, None, bias=False)["head"]
+        need_wfc, need_bfc = need[4], need[5] and b_fc is not None
+        Chead, Cin = y.shape[3], x.shape[3]
+        backbone = need[0] or head.need_any
         J = w_fc.shape[0]
-        dfeat, dw_fc, db_fc = K.linear_bwd(_c(dlogits.float()), feat, w_fc, backbone, need[4], ctx.has_bias and need[5],
-                                           _dest(ctx, 4, (J, Chead)), _dest(ctx, 5, (J,)) if ctx.has_bias else None)
-        dx = dw_head = dgamma = dbeta = None
+        # K.linear_bwd writes a bias gradient only next to the weight gradient: a classifier whose bias alone is trained asks for
+        # both (the weight gradient goes to a temporary and is dropped)
+        dfeat, dw_fc, db_fc = K.linear_bwd(_c(dlogits.float()), feat, w_fc, backbone, need_wfc or need_bfc, need_bfc,
+                                           _slot(w_fc, need_wfc, (J, Chead)), _slot(b_fc, need_bfc, (J,)))
+        dx = None
         if backbone:
             dpooled = K.dropout(dfeat, drop_u, cfg.dropout) if drop_u is not None else dfeat
             dz, parts, n = K.act_bn_bwd(None, y, None, dpooled, st, ACT_SILU)
-            coef, dgamma, dbeta = K.bn_bwd_finalize(parts, n, N * H * W, gamma, st, cfg.training, need[2] or need[3],
-                                                    _dest(ctx, 2, (Chead,)), _dest(ctx, 3, (Chead,)))
+            coef = bn_backward(head, parts, n, _rows(y), st, cfg.training)
             pro = K.pro_affine2(y, coef)
             if need[0]:
                 dx, _, _ = K.pwconv(dz, pro, w_kn, None, stats=False)
-            if need[1]:
-                dw_head = K.pwconv_wgrad(dz, pro, x, None, _dest(ctx, 1, (Chead, Cin))).view(Chead, Cin, 1, 1)
-        return dx, dw_head, dgamma, dbeta, dw_fc, db_fc, None, None
+            if head.need_w:
+                head.dw = K.pwconv_wgrad(dz, pro, x, None, _slot(head.w, True, (Chead, Cin))).view(Chead, Cin, 1, 1)
+        return dx, *head.grads(bias=False), dw_fc if need_wfc else None, db_fc, None, None
 
 # =========================================================================== hooked head (Grad-CAM)
 class HeadConvFunction(torch.autograd.Function):
@@ -463,5 +539,5 @@ class CrossEntropyFunction(torch.autograd.Function):
         return K.axpby(dlogits, None, 1.0, 0.0, a_dev=gloss.reshape(1).float()), None, None
 
 
-__all__ = ["BNRef", "CrossEntropyFunction", "HeadConvFunction", "HeadCtx", "HeadFunction", "HeadTailEvalFunction", "MBConvCtx", "MBConvFunction", "StemCtx",
-           "StemFunction"]
+__all__ = ["BNRef", "CrossEntropyFunction", "HeadConvFunction", "HeadCtx", "HeadFunction", "HeadTailEvalFunction", "Layer", "MBConvCtx",
+           "MBConvFunction", "StemCtx", "StemFunction", "bn_backward", "cut_layers"]

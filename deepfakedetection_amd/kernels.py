@@ -390,9 +390,9 @@ def bn_eval_coeffs(bn: BNParams) -> torch.Tensor:
     return state
 
 
-def bn_bwd_finalize_ex(partials: torch.Tensor, nparts: int, count: int, gamma: torch.Tensor, beta: torch.Tensor | None,
-                       ls: torch.Tensor | None, state: torch.Tensor, train: bool, want_bn: bool = True, want_ls: bool = False,
-                       want_bias: bool = False, outs=(None, None, None, None)):
+def bn_bwd_finalize(partials: torch.Tensor, nparts: int, count: int, gamma: torch.Tensor, beta: torch.Tensor | None,
+                    ls: torch.Tensor | None, state: torch.Tensor, train: bool, want_bn: bool = True, want_ls: bool = False,
+                    want_bias: bool = False, outs=(None, None, None, None)):
     """BatchNorm backward coefficients with LayerScale / convolution-bias gradients.
     Returns (coef, dgamma, dbeta, dls, dbias); outs: optional gradient-arena slots in that order."""
     C = gamma.numel()
@@ -405,19 +405,6 @@ def bn_bwd_finalize_ex(partials: torch.Tensor, nparts: int, count: int, gamma: t
     check(_L().dfd_bn_bwd_finalize_ex(_p(partials), nparts, C, float(count), _p(gamma), _p(beta), _p(ls), _p(state), int(train),
                                       _p(dgamma), _p(dbeta), _p(dls), _p(dbias), 0, _p(coef), _stream()), "dfd_bn_bwd_finalize_ex")
     return coef, dgamma, dbeta, dls, dbias
-
-
-def bn_bwd_finalize(partials: torch.Tensor, nparts: int, count: int, gamma: torch.Tensor, state: torch.Tensor,
-                    train: bool, want_param_grads: bool = True, out_dgamma: torch.Tensor | None = None,
-                    out_dbeta: torch.Tensor | None = None):
-    """out_*: optional destinations (gradient-arena slots) written instead of fresh tensors."""
-    C = gamma.numel()
-    coef = torch.empty((3, C), dtype=torch.float32, device=gamma.device)
-    dgamma = _dst(out_dgamma, (C,), gamma.device) if want_param_grads else None
-    dbeta = _dst(out_dbeta, (C,), gamma.device) if want_param_grads else None
-    check(_L().dfd_bn_bwd_finalize(_p(partials), nparts, C, float(count), _p(gamma), _p(state), int(train),
-                                   _p(dgamma), _p(dbeta), 0, _p(coef), _stream()), "dfd_bn_bwd_finalize")
-    return coef, dgamma, dbeta
 
 
 def bn_act_apply(y: torch.Tensor, state: torch.Tensor, act: int, residual: torch.Tensor | None = None,
@@ -1756,7 +1743,7 @@ _profile_sink: list | None = None
 _TIMED = ("bn_act_apply", "bn_bwd_reduce", "act_bn_bwd", "pool_act", "pool_bwd_reduce", "scale_rows", "dwconv_fwd",
           "dwconv_bwd_data", "dwconv_bwd_weight", "pwconv", "pwconv_wgrad", "pwconv_bwd_fused", "stem_conv_fwd", "stem_conv_wgrad",
           "se_fc_fwd", "se_fc_bwd", "linear_fwd", "linear_bwd", "ce_loss", "adamw_step", "prep_weights", "bn_finalize",
-          "bn_bwd_finalize", "bn_bwd_finalize_ex", "dropout", "bgemm", "attn_scores", "attn_apply", "attn_softmax_fwd", "attn_softmax_bwd", "im2col", "col2im",
+          "bn_bwd_finalize", "dropout", "bgemm", "attn_scores", "attn_apply", "attn_softmax_fwd", "attn_softmax_bwd", "im2col", "col2im",
           "wattn_fwd", "wattn_bwd", "mx_quant_rows", "mx_gemm",
           "bn_add_act", "bn_add_act_bwd", "affine2_apply", "up2_act_fwd", "up2_act_bwd", "layernorm_fwd", "layernorm_bwd",
           "channel_stats", "subsample_add")

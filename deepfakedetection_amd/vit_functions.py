@@ -3,7 +3,7 @@
 One torch.autograd.Function per network stage, built from plain forward/backward helper pairs (no autograd
 inside a stage, so a tensor with several consumers gets its gradient summed by the `residual` operand of a
 GEMM launch, never by an ATen add).  Every "conv (+bias) + BatchNorm [+ LayerScale]" layer travels through its stage
-as one `Layer` record (tensors, one need flag per tensor, the gradients its backward produced):
+as one `Layer` record (functions.py: tensors, one need flag per tensor, the gradients its backward produced):
 
   ConvStemFunction     conv3x3 s2 on the f32 image (+bias) + BN + GELU                    timm Stem4.conv1
   DenseConvBNFunction  dense 3x3 conv (+bias) + BN [+ GELU] as im2col + MFMA GEMM         Stem4.conv2, Downsample.conv
@@ -28,91 +28,7 @@ import torch
 
 from . import kernels as K
 from ._lib import ACT_GELU, ACT_NONE
-from .arena import grad_dest
-from .functions import BNRef, _bn_state, _c
-
-
-def _slot(t: torch.Tensor | None, need: bool, shape):
-    """Gradient-arena slot of parameter `t` if it wants a gradient and its slot is free."""
-    if not need or t is None:
-        return None
-    return grad_dest(t.data_ptr(), shape)
-
-
-def _rows(t: torch.Tensor) -> int:
-    return t.numel() // t.shape[-1]
-
-
-@dataclass
-class Layer:
-    """One "conv (+bias) + BatchNorm [+ LayerScale]" layer of a stage: its tensors, one need flag per tensor (all False in a
-    forward, where only the tensors matter) and the gradients its backward produced.  A plain record: built afresh from the
-    arguments in `forward` and from ctx.saved_tensors in `backward`, never kept on ctx."""
-
-    w: torch.Tensor | None
-    b: torch.Tensor | None
-    gamma: torch.Tensor
-    beta: torch.Tensor | None
-    bn: BNRef | None = None
-    ls: torch.Tensor | None = None
-    need_w: bool = False
-    need_b: bool = False
-    need_gamma: bool = False
-    need_beta: bool = False
-    need_ls: bool = False
-    dw: torch.Tensor | None = None
-    db: torch.Tensor | None = None
-    dgamma: torch.Tensor | None = None
-    dbeta: torch.Tensor | None = None
-    dls: torch.Tensor | None = None
-
-    @property
-    def need_bn(self) -> bool:
-        """gamma and beta share one launch flag: the kernel writes both."""
-        return self.need_gamma or self.need_beta
-
-    @property
-    def need_any(self) -> bool:
-        return self.need_w or self.need_b or self.need_bn
-
-    def grads(self):
-        """(dw, db, dgamma, dbeta) in input order, each masked by its own flag."""
-        return (self.dw if self.need_w else None, self.db if self.need_b else None,
-                self.dgamma if self.need_gamma else None, self.dbeta if self.need_beta else None)
-
-
-def cut_layers(names, t, need, offset: int, bns) -> dict[str, Layer]:
-    """{name: Layer} for the (weight, bias, bn.weight, bn.bias) quads that start at t[offset], one per name.
-    need: the slice of ctx.needs_input_grad that lines up with t (None in a forward); bns: name -> BNRef, or None."""
-    out = {}
-    for i, nm in enumerate(names):
-        o = offset + 4 * i
-        flags = need[o: o + 4] if need is not None else ()
-        out[nm] = Layer(*t[o: o + 4], bns[nm] if bns is not None else None, None, *flags)
-    return out
-
-
-def bn_backward(L: Layer, parts, n, rows: int, st, training: bool):
-    """The BatchNorm-backward coefficients of L from the partial sums; dgamma, dbeta, dls and the convolution-bias gradient land
-    on L — in their gradient-arena slots, each claimed only when this launch really writes it."""
-    C = L.gamma.numel()
-    nb, want_ls, want_b = L.need_bn, L.need_ls and L.ls is not None, L.need_b and L.b is not None
-    outs = (_slot(L.gamma, nb, (C,)), _slot(L.beta, nb, (C,)), _slot(L.ls, want_ls, (C,)), _slot(L.b, want_b, (C,)))
-    coef, L.dgamma, L.dbeta, L.dls, L.db = K.bn_bwd_finalize_ex(parts, n, rows, L.gamma, L.beta, L.ls, st, training, nb, want_ls,
-                                                                want_b, outs)
-    return coef
-
-
-def _prep(w: torch.Tensor, dt: torch.dtype, derived, need_bwd: bool = True):
-    """(w_nk, w_kn) of a 1x1 convolution weight [O, I, 1, 1] (or a 2-D GEMM weight) in the activation dtype.
-    derived: {weight.data_ptr(): (w_nk, w_kn)} refreshed for the whole network by one batched launch per forward
-    (kernels.DerivedWeights; w_nk a kernels.MxWeight with FasterViT's fp8 weights), or None: prepare this layer on the spot.
-    An entry of another dtype than `dt` (a table handed on into another autocast region) is not used."""
-    if derived is not None:
-        hit = derived.get(w.data_ptr())
-        if hit is not None and (isinstance(hit[0], K.MxWeight) or hit[0].dtype == dt):
-            return hit
-    return K.prep_weights(w, dt, True, need_bwd)
+from .functions import BNRef, Layer, _bn_state, _c, _prep, _rows, _slot, bn_backward, cut_layers
 
 
 # =========================================================================== helper pairs (no autograd)
@@ -483,12 +399,8 @@ class ConvMlpFunction(torch.autograd.Function):
         return out
 
     @staticmethod
+    @K.batched_sums                 # the three weight gradients' final sums in one pair of launches at the end
     def backward(ctx, g):
-        with K.sum_batch():        # the three weight gradients' final sums in one pair of launches at the end
-            return ConvMlpFunction._backward(ctx, g)
-
-    @staticmethod
-    def _backward(ctx, g):
         cfg: ConvMlpCtx = ctx.cfg
         x, y1, a1, y2, a2, y3, st1, st2, st3, w1_kn, w2_kn, *t = ctx.saved_tensors
         need = ctx.needs_input_grad

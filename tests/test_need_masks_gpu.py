@@ -1,12 +1,12 @@
-"""Gradients of the ViT autograd stages must not depend on which OTHER inputs are frozen.
+"""Gradients of the autograd stages must not depend on which OTHER inputs are frozen.
 
-Every stage of vit_functions.py / fastervit_functions.py that holds a "conv (+bias) + BatchNorm [+ LayerScale]" layer (and
-HATFunction) is built as its oracle test builds it (tests/test_efformer_gpu.py, tests/test_fastervit_gpu.py: same modules,
-same tensor sizes, smallest parametrisation), run once in f32 with every input trainable, and then again with each tensor
-input frozen alone, each trainable alone, x frozen, and (EfficientFormerV2) the reference fine-tune's pattern.  In every
-case a trainable input's gradient is bit for bit the baseline's, a frozen input's .grad is None, and no gradient holds a NaN
-from an unwritten buffer.  Two whole-model cases repeat this with a gradient arena, whose slots are pre-filled with NaN: a
-slot that was claimed but not written, or written by the wrong launch, shows at once.
+Every stage of functions.py / vit_functions.py / fastervit_functions.py that holds a "conv (+bias) + BatchNorm [+ LayerScale]"
+layer (and HATFunction) is built as its oracle test builds it (tests/test_efformer_gpu.py, tests/test_fastervit_gpu.py,
+tests/test_model_gpu.py: same modules, smallest parametrisation), run once in f32 with every input trainable, and then again
+with each tensor input frozen alone, each trainable alone, x frozen, and (EfficientFormerV2) the reference fine-tune's
+pattern.  In every case a trainable input's gradient is bit for bit the baseline's, a frozen input's .grad is None, and no
+gradient holds a NaN from an unwritten buffer.  Three whole-model cases repeat this with a gradient arena, whose slots are
+pre-filled with NaN: a slot that was claimed but not written, or written by the wrong launch, shows at once.
 """
 
 from __future__ import annotations
@@ -205,6 +205,77 @@ def test_hat(fv, level, train):
     check_masks(Stage(leaves, lambda: blk(x, ct, maps, None, tables)))
 
 
+# ------------------------------------------------------------------ EfficientNet-B0
+@pytest.fixture(scope="module")
+def en():
+    """flavour -> HipEfficientNet B0 as tests/test_model_gpu.py sets its models up: the oracle's initial weights and running
+    statistics warmed up by three oracle training steps.  Head dropout off, so that two passes of the whole model agree."""
+    from deepfakedetection_amd.efficientnet import HipEfficientNet
+    from oracle.effnet_ref import EfficientNetRef
+    from tests.test_model_gpu import warm_running_stats
+
+    made = {}
+
+    def get(flavour):
+        if flavour not in made:
+            torch.manual_seed(5)
+            ref = EfficientNetRef("b0", flavour, 2)
+            warm_running_stats(ref, 64)
+            hip = HipEfficientNet("b0", flavour, 2, drop_rate=0.0)
+            hip.load_state_dict(ref.state_dict())
+            made[flavour] = hip.cuda()
+        return made[flavour]
+
+    return get
+
+
+@TRAIN
+@pytest.mark.parametrize("flavour", ["timm", "lukemelas"])       # symmetric padding / static-same padding with its lead pad
+def test_efficientnet_stem(en, flavour, train):
+    from deepfakedetection_amd.functions import StemCtx, StemFunction
+    from deepfakedetection_amd.network import _bnref
+
+    net = en(flavour)
+    stem, stem_bn = net._parts()[:2]
+    img = nhwc(rand(2, 2, 3, 32, 32)).cuda()                      # the stem gives its image no gradient: not a leaf
+    cfg = StemCtx(net.plan.stem, _bnref(stem_bn), torch.float32, train, None)
+    leaves = {"weight": stem.weight, "bn.weight": stem_bn.weight, "bn.bias": stem_bn.bias}
+    check_masks(Stage(leaves, lambda: StemFunction.apply(img, stem.weight, stem_bn.weight, stem_bn.bias, cfg)))
+
+
+@TRAIN
+@pytest.mark.parametrize("flavour,index", [("timm", 0), ("timm", 1), ("timm", 2), ("timm", 3), ("lukemelas", 1)],
+                         ids=["no_expand", "expand_stride2", "skip_row_scale", "k5_stride2", "lukemelas_stride2"])
+def test_mbconv(en, flavour, index, train):
+    """Block 0: no expand convolution, no skip; 1: expand, stride 2; 2: expand and skip, with a drop-connect scale handed in;
+    3: 5 x 5, stride 2; block 1 of the lukemelas flavour for its asymmetric padding."""
+    blk = en(flavour).block_list()[index].train(train)
+    p = blk.plan
+    assert (p.expand, p.skip, p.dw.kernel, p.dw.stride) == [(False, False, 3, 1), (True, False, 3, 2), (True, True, 3, 1),
+                                                             (True, False, 5, 2)][index]
+    x = rand(3, 3, 16, 16, p.cin).cuda()
+    row_scale = torch.tensor([1.25, 0.0, 1.25]).cuda() if p.skip else None
+    check_masks(module_stage(blk, x, lambda: blk.run(x, row_scale)))
+
+
+@TRAIN
+@pytest.mark.parametrize("dropout", [True, False], ids=["dropout", "no_dropout"])
+def test_efficientnet_head(en, dropout, train):
+    """The classifier's weight and bias are frozen and trained one by one like every other input: a bias trained next to a
+    frozen weight gets its gradient."""
+    from deepfakedetection_amd.functions import HeadCtx, HeadFunction
+    from deepfakedetection_amd.network import _bnref
+
+    _, _, _, head, head_bn, fc = en("timm")._parts()
+    x = rand(4, 4, 7, 7, 320).cuda()
+    u = torch.rand(4, 1280, generator=torch.Generator().manual_seed(9)).cuda() if dropout else None
+    cfg = HeadCtx(_bnref(head_bn), 0.2, train, None, None)
+    leaves = {"x": x, "conv_head.weight": head.weight, "bn2.weight": head_bn.weight, "bn2.bias": head_bn.bias,
+              "classifier.weight": fc.weight, "classifier.bias": fc.bias}
+    fwd = lambda: HeadFunction.apply(x, head.weight, head_bn.weight, head_bn.bias, fc.weight, fc.bias, u, cfg)   # noqa: E731
+    check_masks(Stage(leaves, fwd))
+
+
 # ------------------------------------------------------------------ whole models, gradients in arena slots
 def _arena_grads(model, x, y, frozen: set) -> dict:
     from deepfakedetection_amd.optim import HipAdamW, HipCrossEntropyLoss
@@ -228,7 +299,7 @@ def _arena_grads(model, x, y, frozen: set) -> dict:
 
 
 def _check_model(model, layer: tuple):
-    """layer: the (weight, bias, gamma, beta) parameter names of one mid-network layer, each frozen alone."""
+    """layer: parameter names of one mid-network layer (its weight, bias, gamma, beta or the like), each frozen alone."""
     x = rand(1, 2, 3, 224, 224).cuda()
     y = torch.tensor([0, 1]).cuda()
     model.train()
@@ -241,6 +312,11 @@ def _check_model(model, layer: tuple):
     for p in model.parameters():
         p.requires_grad_(True)
     assert not bad, "\n".join(bad)
+
+
+def test_efficientnet_b0_with_an_arena(en):
+    b = "blocks.3.0"                                              # the first block of the fourth stage: expand, 3 x 3, stride 2
+    _check_model(en("timm"), (f"{b}.conv_pw.weight", f"{b}.bn1.weight", f"{b}.bn1.bias", f"{b}.se.conv_reduce.bias"))
 
 
 def test_efficientformer_s0_with_an_arena():

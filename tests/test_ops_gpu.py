@@ -422,13 +422,13 @@ def test_rowpass(case, rd):
     close(K.bn_act_apply(dev(y), dev(st), 0, dev(res), dev(rs)), want, tol(rd), "apply res rs")
     # bn_bwd_reduce + finalize
     parts, n = K.bn_bwd_reduce(dev(g), dev(y), dev(st), None)
-    coef, dgam, dbet = K.bn_bwd_finalize(parts, n, N * H * W, dev(gamma), dev(st), True)
+    coef, dgam, dbet, _, _ = K.bn_bwd_finalize(parts, n, N * H * W, dev(gamma), dev(beta), None, dev(st), True)
     wc, wdg, wdb = R.bn_bwd_coef(g.float(), y.float(), gamma, st)
     close(coef, wc, 2e-3, "bn bwd coef")
     close(dgam, wdg, 2e-3, "dgamma")
     close(dbet, wdb, 2e-3, "dbeta")
     parts, n = K.bn_bwd_reduce(dev(g), dev(y), dev(st), dev(rs))
-    coef2, _, _ = K.bn_bwd_finalize(parts, n, N * H * W, dev(gamma), dev(st), True)
+    coef2, *_ = K.bn_bwd_finalize(parts, n, N * H * W, dev(gamma), dev(beta), None, dev(st), True)
     wc2, _, _ = R.bn_bwd_coef(g.float() * rs[:, None, None, None], y.float(), gamma, st)
     close(coef2, wc2, 2e-3, "bn bwd coef rs")
     # bias gradient of a layer without statistics: column sums of g (times the row scale), into a given destination too

@@ -97,8 +97,8 @@ def test_bn_bwd_finalize_ex_matches_autograd(train):
         xhat = (y - mean) * rstd
         parts = torch.stack([g.sum(0), (g * xhat).sum(0)]).reshape(1, 2, C).contiguous()
         st = torch.stack([ls * gamma * rstd, ls * (beta - mean * gamma * rstd), mean, rstd]).contiguous()
-    coef, dg, db, dls, dbias = K.bn_bwd_finalize_ex(parts.cuda(), 1, M, gamma.detach().cuda(), beta.detach().cuda(),
-                                                    ls.detach().cuda(), st.cuda(), train, True, True, True)
+    coef, dg, db, dls, dbias = K.bn_bwd_finalize(parts.cuda(), 1, M, gamma.detach().cuda(), beta.detach().cuda(),
+                                                 ls.detach().cuda(), st.cuda(), train, True, True, True)
     close(dg, gamma.grad, 2e-4, "dgamma")
     close(db, beta.grad, 2e-4, "dbeta")
     close(dls, ls.grad, 2e-4, "dls")
