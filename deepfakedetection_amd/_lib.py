@@ -33,6 +33,8 @@ MIX_JOB_WORDS = 8
 MIX_KEEP, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2
 MIX_NHWC, MIX_NCHW = 0, 1
 AUG_MAX_OPS = 4
+BLUR_MAX_RADIUS = 32
+BLUR_MAX_PIXELS = 78 * 1024
 AUG_POLICY_JOB_WORDS = 16 + 2 + 9 * AUG_MAX_OPS     # struct dfd_augment_policy_job in int32 words (216 bytes)
 
 
@@ -122,6 +124,8 @@ SIGNATURES: dict[str, tuple] = {
     # ---- ABI 142
     "dfd_jpeg_u8": (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
     "dfd_jpeg_ws": (c_size_t, [c_int, c_int, c_int]),
+    # ---- ABI 144
+    "dfd_blur_u8": (c_int, [P, P, P, c_int, c_int, c_int, P]),
     # ---- ABI 111
     "dfd_bn_eval_coeffs_multi": (c_int, [P, c_int, P]),
     "dfd_sum_batch_begin": (c_int, []),

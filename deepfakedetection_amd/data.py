@@ -9,7 +9,7 @@ the source of randomness (so `apply_seed` governs augmentation):
   RandomResizedCrop(size, scale, ratio), RandomRotation(degrees), RandomHorizontalFlip(p),
   ColorJitter(brightness, contrast, saturation, hue), ToTensor, Normalize(mean, std),
   RandomErasing(p, scale, ratio, value), Compose, RandAugment(num_ops, magnitude), TrivialAugmentWide(),
-  RandomJpeg(p, quality).
+  RandomBlur(p, sigma), RandomJpeg(p, quality).
 
 Batches leave the loaders as float32 [N,3,H,W] + int64 [N] exactly like the reference's.
 """
@@ -26,7 +26,7 @@ from typing import Any
 
 import numpy as np
 import torch
-from PIL import Image, ImageEnhance, ImageOps
+from PIL import Image, ImageEnhance, ImageFilter, ImageOps
 
 from ._lib import AUG_MAX_OPS as AA_MAX_OPS, AUG_POLICY_JOB_WORDS as AA_JOB_WORDS     # struct dfd_augment_policy_job (include/dfd_hip.h)
 
@@ -294,6 +294,63 @@ class TrivialAugmentWide:
         for op, m in _aa_draw("trivial", 1, 0, *img.size):
             img = aa_apply(img, op, m)
         return img
+
+
+BLUR_MAX_SIGMA = 16.0                   # box radius 15: within DFD_BLUR_MAX_RADIUS (include/dfd_hip.h)
+
+
+def check_blur(p: float, lo: float, hi: float) -> tuple[float, float, float]:
+    if not 0.0 <= float(p) <= 1.0:
+        raise ValueError(f"RandomBlur: p must be within 0..1, got {p}")
+    if not 0.0 <= float(lo) <= float(hi) <= BLUR_MAX_SIGMA:
+        raise ValueError(f"RandomBlur: the sigma range must satisfy 0 <= min <= max <= {BLUR_MAX_SIGMA:g}, got {lo}..{hi}")
+    return float(p), float(lo), float(hi)
+
+
+def blur_plans(sigmas) -> np.ndarray:
+    """int64 [n, 3] = (r, ww, fw) of ImageFilter.GaussianBlur(radius=sigma) for every sigma: Pillow runs three extended box blurs
+    along x and three along y, each out[x] = (ww * sum_{|d| <= r} in[x + d] + fw * (in[x - r - 1] + in[x + r + 1]) + 2^23) >> 24
+    with replicated edges.  The box radius comes from sigma in float32, operation by operation as BoxBlur.c computes it; this is
+    the only place where floating point enters, the kernel (csrc/dfd_blur.hip) and tests/_blur_ref.py take the three integers."""
+    f = np.float32
+    s = np.asarray(sigmas, dtype=np.float32).reshape(-1)
+    s2 = s * s / f(3.0)
+    length = np.sqrt(f(12.0) * s2 + f(1.0))
+    l = np.floor((length - f(1.0)) / f(2.0))
+    a = (f(2.0) * l + f(1.0)) * (l * (l + f(1.0)) - f(3.0) * s2)
+    a = a / (f(6.0) * (s2 - (l + f(1.0)) * (l + f(1.0))))
+    fr = l + a
+    assert fr.dtype == np.float32
+    r = fr.astype(np.int64)
+    ww = (f(1 << 24) / (f(2.0) * fr + f(1.0))).astype(np.int64)
+    return np.stack([r, ww, ((1 << 24) - (2 * r + 1) * ww) // 2], axis=1)
+
+
+def blur_plan(sigma: float) -> tuple[int, int, int]:
+    """blur_plans for one sigma."""
+    r, ww, fw = blur_plans([sigma])[0].tolist()
+    return r, ww, fw
+
+
+def _blur_draw(p: float, lo: float, hi: float) -> float | None:
+    """The sigma RandomBlur blurs this picture at, None: it is left alone.  Sigma is drawn only for a selected picture."""
+    if _rand() < p:
+        return _uniform(lo, hi)
+    return None
+
+
+class RandomBlur:
+    """Gaussian-blur augmentation on PIL images: with probability `p` the picture is replaced by
+    ImageFilter.GaussianBlur(radius=sigma) of it, sigma drawn uniformly from lo..hi."""
+
+    def __init__(self, p: float = 0.5, sigma: tuple[float, float] = (0.0, 3.0)) -> None:
+        self.p, self.lo, self.hi = check_blur(p, *sigma)
+
+    def __call__(self, img: Image.Image) -> Image.Image:
+        sigma = _blur_draw(self.p, self.lo, self.hi)
+        if sigma is None:
+            return img
+        return img.convert("RGB").filter(ImageFilter.GaussianBlur(radius=sigma))
 
 
 def check_jpeg(p: float, lo: int, hi: int) -> tuple[float, int, int]:
@@ -588,13 +645,19 @@ class GpuInputTail:
     policy its draw follows the policy's, picture by picture.  Without one it is drawn for the whole batch after the flips and
     before the erasing boxes; the flip does not commute with the round trip, so the flip flags then go to dfd_jpeg_u8, which mirrors
     every picture — also those it only copies — before it compresses, and dfd_image_prep gets no flip.  With jpeg=None nothing
-    changes: same draws, same launches."""
+    changes: same draws, same launches.
+
+    blur=(p, sigma_min, sigma_max) adds RandomBlur behind the policy's slot and in front of RandomJpeg (dfd_blur_u8, byte-exact
+    with Pillow's GaussianBlur).  With a policy its draw follows the policy's and precedes RandomJpeg's, picture by picture.
+    Without one it is drawn for the whole batch after the flips and before the JPEG draws.  The blur is symmetric and replicates
+    edges, so it commutes with the flip: its jobs carry no flip flag and the flip stays where it is without blur, in dfd_image_prep
+    or in dfd_jpeg_u8.  With blur=None nothing changes: same draws, same launches."""
 
     def __init__(self, mean: Sequence[float], std: Sequence[float], flip_p: float = 0.0, erase_p: float = 0.0,
                  erase_scale: tuple[float, float] = (0.02, 0.33), erase_ratio: tuple[float, float] = (0.3, 3.3),
                  rotate_degrees: float = 0.0, jitter: Sequence[float] | None = None,
                  rand_augment: tuple[int, int] | None = None, trivial_augment: bool = False,
-                 jpeg: tuple[float, int, int] | None = None) -> None:
+                 jpeg: tuple[float, int, int] | None = None, blur: tuple[float, float, float] | None = None) -> None:
         self.mean, self.std = [float(v) for v in mean], [float(v) for v in std]
         self.flip_p, self.erase_p, self.erase_scale, self.erase_ratio = flip_p, erase_p, erase_scale, erase_ratio
         self.rotate_degrees = float(rotate_degrees)
@@ -604,6 +667,7 @@ class GpuInputTail:
         self.rand_augment = check_rand_augment(*rand_augment) if rand_augment is not None else None
         self.trivial_augment = bool(trivial_augment)
         self.jpeg = check_jpeg(*jpeg) if jpeg is not None else None
+        self.blur = check_blur(*blur) if blur is not None else None
 
     @property
     def augments(self) -> bool:
@@ -657,18 +721,35 @@ class GpuInputTail:
     def _sample_policy(self, n: int, h: int, w: int) -> tuple[torch.Tensor, torch.Tensor | None]:
         """sample_policy's jobs and, with jpeg on, the {quality, flip = 0} jobs of dfd_jpeg_u8, RandomJpeg's draw following the
         policy's for each picture."""
+        return self._sample_policy_all(n, h, w)[:2]
+
+    def _sample_policy_all(self, n: int, h: int, w: int) -> tuple[torch.Tensor, torch.Tensor | None, torch.Tensor | None]:
+        """_sample_policy's pair and, with blur on, the jobs of dfd_blur_u8, RandomBlur's draw standing between the policy's and
+        RandomJpeg's for each picture."""
         base = np.zeros((n, 16), dtype=np.int32)
         fl = base.view(np.float32)
-        flips, ops, qualities = [], [], []
+        flips, ops, qualities, sigmas = [], [], [], []
         num_ops, magnitude = self.rand_augment if self.rand_augment is not None else (1, 0)
         for i in range(n):
             self._draw_rotation(base, i, h, w)
             flips.append(1 if self.flip_p > 0 and _rand() < self.flip_p else 0)
             self._draw_jitter(base, fl, i)
             ops.append(_aa_draw(self.policy, num_ops, magnitude, w, h))
+            if self.blur is not None:
+                sigmas.append(_blur_draw(*self.blur))
             if self.jpeg is not None:
                 qualities.append(_jpeg_draw(*self.jpeg))
-        return pack_policy_jobs(base, flips, ops, w, h), (self._jpeg_jobs(qualities, None) if self.jpeg is not None else None)
+        return (pack_policy_jobs(base, flips, ops, w, h), self._jpeg_jobs(qualities, None) if self.jpeg is not None else None,
+                self._blur_jobs(sigmas) if self.blur is not None else None)
+
+    @staticmethod
+    def _blur_jobs(sigmas: Sequence[float | None]) -> torch.Tensor:
+        """Host int32 [N, 4] = {r, ww, fw, 0} of dfd_blur_u8; a picture that is not selected keeps ww = 0 and is copied."""
+        jobs = np.zeros((len(sigmas), 4), dtype=np.int32)
+        chosen = [i for i, sigma in enumerate(sigmas) if sigma is not None]
+        if chosen:
+            jobs[chosen, :3] = blur_plans([sigmas[i] for i in chosen])          # one pass over the batch: the draws stay per picture
+        return torch.from_numpy(jobs)
 
     @staticmethod
     def _jpeg_jobs(qualities: Sequence[int], flip: torch.Tensor | None) -> torch.Tensor:
@@ -706,17 +787,24 @@ class GpuInputTail:
 
     def _draw(self, n: int, h: int, w: int):
         """(rotation / jitter jobs | None, policy jobs | None, flip | None, erase | None, jpeg jobs | None) for a batch."""
+        return self._draw_all(n, h, w)[:5]
+
+    def _draw_all(self, n: int, h: int, w: int):
+        """_draw's five and the blur jobs | None."""
         if self.policy is not None:
-            policy, jpeg = self._sample_policy(n, h, w)
-            return None, policy, None, self._sample_erase(n, h, w), jpeg
+            policy, jpeg, blur = self._sample_policy_all(n, h, w)
+            return None, policy, None, self._sample_erase(n, h, w), jpeg, blur
         aug = self.sample_augment(n, h, w) if self.augments else None
-        if self.jpeg is None:
-            return (aug, None, *self.sample(n, h, w), None)
+        if self.jpeg is None and self.blur is None:
+            return (aug, None, *self.sample(n, h, w), None, None)
         flip = None
         if self.flip_p > 0:
             flip = torch.tensor([1 if _rand() < self.flip_p else 0 for _ in range(n)], dtype=torch.uint8)
+        blur = self._blur_jobs([_blur_draw(*self.blur) for _ in range(n)]) if self.blur is not None else None
+        if self.jpeg is None:
+            return aug, None, flip, self._sample_erase(n, h, w), None, blur    # the blur commutes with the flip: dfd_image_prep flips
         jpeg = self._jpeg_jobs([_jpeg_draw(*self.jpeg) for _ in range(n)], flip)          # the flip goes in front of the round trip
-        return aug, None, None, self._sample_erase(n, h, w), jpeg
+        return aug, None, None, self._sample_erase(n, h, w), jpeg, blur
 
     def __call__(self, batch_u8: torch.Tensor, device) -> torch.Tensor:
         from . import kernels as K
@@ -725,18 +813,20 @@ class GpuInputTail:
             flat, jobs, meta = batch_u8
             oh, ow, shrink = (int(v) for v in meta)
             n = jobs.numel() // _JOB_DTYPE.itemsize
-            aug, policy, flip, erase, jpeg = self._draw(n, oh, ow)
+            aug, policy, flip, erase, jpeg, blur = self._draw_all(n, oh, ow)
             dev = K.resize_crop_u8(flat.to(device, non_blocking=True), jobs.to(device, non_blocking=True), n, oh, ow, shrink)
         else:
             if batch_u8.dim() != 4 or batch_u8.shape[3] != 3 or batch_u8.dtype != torch.uint8:
                 raise ValueError("GpuInputTail expects a uint8 [N, H, W, 3] batch (ToUint8HWC at the end of the CPU pipeline)")
             n, h, w, _ = batch_u8.shape
-            aug, policy, flip, erase, jpeg = self._draw(n, h, w)
+            aug, policy, flip, erase, jpeg, blur = self._draw_all(n, h, w)
             dev = batch_u8.to(device, non_blocking=True).contiguous()
         if aug is not None:
             dev = K.augment_u8(dev, aug.to(device, non_blocking=True))
         if policy is not None:
             dev = K.augment_policy_u8(dev, policy)
+        if blur is not None:
+            dev = K.blur_u8(dev, blur)
         if jpeg is not None:
             dev = K.jpeg_u8(dev, jpeg)
         return K.image_prep(dev, self.mean, self.std,

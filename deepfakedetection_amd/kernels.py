@@ -591,6 +591,24 @@ def jpeg_u8(src_u8: torch.Tensor, jobs_i32: torch.Tensor, ws: torch.Tensor | Non
     return out
 
 
+def blur_u8(src_u8: torch.Tensor, jobs_i32: torch.Tensor) -> torch.Tensor:
+    """uint8 [N, H, W, 3] on the device + one {r, ww, fw, 0} job per picture as a HOST int32 [N, 4] tensor (data.blur_plan;
+    GpuInputTail._blur_jobs) -> each picture after Pillow's GaussianBlur, byte-exact, in one launch (csrc/dfd_blur.hip, ABI 144).
+    A job with ww == 0, or with r outside 0.._lib.BLUR_MAX_RADIUS, copies its picture through.  H * W may not exceed
+    _lib.BLUR_MAX_PIXELS.  The upload does not block when the tensor is pinned."""
+    if src_u8.dtype != torch.uint8 or src_u8.dim() != 4 or src_u8.shape[3] != 3 or not src_u8.is_contiguous():
+        raise ValueError("expected a contiguous uint8 [N, H, W, 3] tensor")
+    N, H, W, _ = src_u8.shape
+    if H * W > _lib.BLUR_MAX_PIXELS:
+        raise ValueError(f"blur_u8: pictures may have at most {_lib.BLUR_MAX_PIXELS} pixels, got {H}x{W}")
+    if jobs_i32.is_cuda or jobs_i32.dtype != torch.int32 or tuple(jobs_i32.shape) != (N, 4) or not jobs_i32.is_contiguous():
+        raise ValueError(f"blur_u8: expected a host int32 [{N}, 4] job tensor of (r, ww, fw, 0)")
+    out = torch.empty_like(src_u8)
+    jobs_dev = jobs_i32.to(src_u8.device, non_blocking=True)
+    check(_L().dfd_blur_u8(_p(src_u8), _p(jobs_dev), _p(out), N, H, W, _stream()), "dfd_blur_u8", f"{tuple(src_u8.shape)}")
+    return out
+
+
 def image_prep(src_u8: torch.Tensor, mean, std, flip: torch.Tensor | None, erase: torch.Tensor | None) -> torch.Tensor:
     """uint8 [N, H, W, 3] on the device -> f32, returned as an [N, 3, H, W] channels_last view of the
     NHWC result (zero-copy: exactly what HipEfficientNet.forward turns back into NHWC)."""

@@ -169,7 +169,8 @@ _EXTRA_TRAIN_ENV = (("ft_batch_size", "FT_BATCH_SIZE"), ("pretrained", "PRETRAIN
                     ("mix_switch_prob", "MIX_SWITCH_PROB"), ("mix_mode", "MIX_MODE"),
                     ("rand_augment_ops", "RAND_AUGMENT_OPS"), ("rand_augment_magnitude", "RAND_AUGMENT_MAGNITUDE"),
                     ("trivial_augment", "TRIVIAL_AUGMENT"), ("clip_grad", "CLIP_GRAD"), ("clip_mode", "CLIP_MODE"),
-                    ("jpeg_p", "JPEG_P"), ("jpeg_quality_min", "JPEG_QUALITY_MIN"), ("jpeg_quality_max", "JPEG_QUALITY_MAX"))
+                    ("jpeg_p", "JPEG_P"), ("jpeg_quality_min", "JPEG_QUALITY_MIN"), ("jpeg_quality_max", "JPEG_QUALITY_MAX"),
+                    ("blur_p", "BLUR_P"), ("blur_sigma_min", "BLUR_SIGMA_MIN"), ("blur_sigma_max", "BLUR_SIGMA_MAX"))
 
 
 def _first_set(*values: Any) -> Any:
@@ -300,12 +301,14 @@ def build_inference_loader(*, dataset, batch_size: int, num_workers: int) -> Dat
                       persistent_workers=num_workers > 0, **extra)
 
 
-def class_probabilities(model: nn.Module, images: torch.Tensor, device: torch.device, amp: bool = False):
+def class_probabilities(model: nn.Module, images: torch.Tensor, device: torch.device, amp: bool = False, tail=None):
     """logits -> (softmax probabilities, arg-max) for one batch (orchestrator.py:589-592).  amp: run the forward in a
-    bf16 autocast region (opt-in `inference.amp: bf16`; the reference's inference is f32, which stays the default)."""
+    bf16 autocast region (opt-in `inference.amp: bf16`; the reference's inference is f32, which stays the default).
+    tail: the D.GpuInputTail a data.collate_raw batch goes through (default: _GPU_EVAL_TAIL; the robustness pass hands in
+    one that perturbs the cropped bytes first)."""
     with torch.inference_mode(), torch.autocast(device_type=device.type, dtype=torch.bfloat16, enabled=amp and device.type == "cuda"):
         if isinstance(images, (tuple, list)):          # data.collate_raw batch: resize / crop / normalise on the device
-            images = _GPU_EVAL_TAIL(images, device)
+            images = (tail if tail is not None else _GPU_EVAL_TAIL)(images, device)
         logits = model(images.to(device, non_blocking=True))
         if logits.is_cuda:
             from .. import kernels  # HIP softmax/argmax epilogue
@@ -315,6 +318,30 @@ def class_probabilities(model: nn.Module, images: torch.Tensor, device: torch.de
             probs = torch.softmax(logits, dim=1)
             preds = torch.argmax(probs, dim=1)
     return probs, preds
+
+
+def robustness_levels(infer_cfg: dict[str, Any]) -> list[tuple[str, float | int]]:
+    """Extra key `inference.robustness: {blur_sigma: [1, 2, 3], jpeg_quality: [90, 70, 50]}`: the perturbation levels the test
+    split is evaluated at once more after the metrics pass, as ("blur_sigma", sigma) / ("jpeg_quality", quality) in the order
+    written, blur first.  Either list may be absent; no key, no levels.  ValueError for a sigma outside 0..16 or a quality
+    outside 1..100."""
+    raw = infer_cfg.get("robustness")
+    if not isinstance(raw, dict):
+        return []
+    levels: list[tuple[str, float | int]] = []
+    for sigma in raw.get("blur_sigma") or []:
+        levels.append(("blur_sigma", D.check_blur(1.0, float(sigma), float(sigma))[1]))
+    for quality in raw.get("jpeg_quality") or []:
+        levels.append(("jpeg_quality", D.check_jpeg(1.0, quality, quality)[1]))
+    return levels
+
+
+def robustness_tail(kind: str, level: float | int) -> D.GpuInputTail:
+    """The eval tail that applies one perturbation level to every picture of the cropped uint8 batch: RandomBlur or RandomJpeg at
+    probability 1 over a range of one value, so the same kernels as in training and nothing random in the result."""
+    if kind == "blur_sigma":
+        return D.GpuInputTail(IMAGENET_MEAN, IMAGENET_STD, blur=(1.0, level, level))
+    return D.GpuInputTail(IMAGENET_MEAN, IMAGENET_STD, jpeg=(1.0, level, level))
 
 
 def cam_limit(infer_cfg: dict[str, Any]) -> int | None:
@@ -458,6 +485,32 @@ def _resolve_weights(infer_cfg: dict[str, Any], model_name: str, out: Console) -
     return path
 
 
+def _split_metrics(name: str, split: str, probs_t: torch.Tensor, preds_t: torch.Tensor, targets_t: torch.Tensor, num_classes: int,
+                   threshold: float) -> tuple[dict[str, Any], torch.Tensor, np.ndarray]:
+    """(one metrics.jsonl record, the predictions it judges, their confusion matrix) of one pass over a split; a binary problem
+    predicts by `threshold` on the second class's probability."""
+    if num_classes == 2:
+        preds_t = (probs_t[:, 1] >= threshold).long()
+    accuracy = (preds_t == targets_t).float().mean().item()
+    metrics: dict[str, Any] = {"model": name, "split": split, "accuracy": accuracy, "timestamp": datetime.now().isoformat()}
+    truth_np, pred_np = targets_t.numpy(), preds_t.numpy()
+    if torch.unique(targets_t).numel() > 1:
+        try:
+            from sklearn.metrics import roc_auc_score
+
+            if num_classes == 2:
+                metrics["roc_auc"] = float(roc_auc_score(truth_np, probs_t[:, 1].numpy()))
+            else:
+                metrics["roc_auc"] = float(roc_auc_score(truth_np, probs_t.numpy(), multi_class="ovr"))
+        except (ImportError, ValueError):
+            pass
+    if num_classes == 2:
+        metrics["threshold"] = float(threshold)
+    cm = confusion_counts(truth_np, pred_np)
+    metrics["confusion_matrix"] = cm.tolist()
+    return metrics, preds_t, cm
+
+
 def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: dict[str, Any], run_paths: RunPaths) -> None:
     tty = getattr(sys.stdout, "isatty", None)
     out = Console(file=sys.stdout, force_terminal=bool(tty()) if callable(tty) else False)
@@ -484,6 +537,7 @@ def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: 
         model.fp8_weights = True       # extra key (FasterViT, with `amp: bf16`): Linear weights as MX fp8 on the scaled fp8 MFMA
     eval_toggles = resolve_transform_mapping(model_cfg, phase="eval")
     transform = build_eval_transforms(image_size, toggles=eval_toggles)
+    device_pipeline = False
     if str(infer_cfg.get("gpu_resize", "")).lower() in ("1", "true", "yes", "on") and device.type == "cuda":
         # extra key: the workers only decode; Resize + CenterCrop + ToTensor + Normalize run on the device (bit-exact with the
         # PIL pipeline above, tests/test_ops_gpu.py::test_resize_crop_matches_pillow_bit_for_bit).  The device pipeline IS the default
@@ -495,6 +549,7 @@ def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: 
             out.print(f"[bold yellow]inference.gpu_resize ignored[/]: eval toggles {switched_off} are off; the PIL pipeline honours them")
         else:
             transform = D.Compose([D.Lambda(_to_rgb), D.PlanGeometry("center", image_size, image_size)])
+            device_pipeline = True
     root = Path(data_cfg.get("root")).expanduser()
     if not root.is_absolute():
         root = (Path.cwd() / root).resolve()
@@ -539,32 +594,40 @@ def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: 
             progress.update(task, advance=1, speed=f"{seen / max(perf_counter() - start, 1e-6):.1f} img/s")
 
     probs_t, preds_t, targets_t = torch.cat(all_probs), torch.cat(all_preds), torch.cat(all_targets)
-    if num_classes == 2:
-        preds_t = (probs_t[:, 1] >= threshold).long()
-    accuracy = (preds_t == targets_t).float().mean().item()
-    metrics: dict[str, Any] = {"model": name, "split": split, "accuracy": accuracy, "timestamp": datetime.now().isoformat()}
-    truth_np, pred_np = targets_t.numpy(), preds_t.numpy()
+    metrics, preds_t, cm = _split_metrics(name, split, probs_t, preds_t, targets_t, num_classes, threshold)
+    accuracy = metrics["accuracy"]
+    truth_np = targets_t.numpy()
     multi_label = torch.unique(targets_t).numel() > 1
-    if multi_label:
-        try:
-            from sklearn.metrics import roc_auc_score
-
-            if num_classes == 2:
-                metrics["roc_auc"] = float(roc_auc_score(truth_np, probs_t[:, 1].numpy()))
-            else:
-                metrics["roc_auc"] = float(roc_auc_score(truth_np, probs_t.numpy(), multi_class="ovr"))
-        except (ImportError, ValueError):
-            pass
-    if num_classes == 2:
-        metrics["threshold"] = float(threshold)
-    cm = confusion_counts(truth_np, pred_np)
-    metrics["confusion_matrix"] = cm.tolist()
     _save_plots(cm, list(dataset.classes), truth_np, probs_t[:, 1].numpy() if num_classes == 2 and multi_label else None,
                 run_paths.plots)
     with (run_paths.logs / "metrics.jsonl").open("a", encoding="utf-8") as handle:
         handle.write(json.dumps(metrics) + "\n")
     extras = " ".join(f"{k}={v:.4f}" for k, v in metrics.items() if isinstance(v, float) and k != "accuracy")
     out.print(f"[bold]Accuracy[/]: {accuracy:.4f} {extras}")
+    levels = robustness_levels(infer_cfg)
+    if levels and not device_pipeline:
+        # the perturbation is applied to the cropped uint8 batch on the device, which only the device pipeline has
+        out.print("[bold yellow]inference.robustness skipped[/]: needs inference.gpu_resize on a CUDA device")
+    elif levels:
+        from .._lib import BLUR_MAX_PIXELS
+
+        if image_size * image_size > BLUR_MAX_PIXELS and any(kind == "blur_sigma" for kind, _ in levels):
+            out.print(f"[bold yellow]inference.robustness blur_sigma skipped[/]: dfd_blur_u8 takes at most {BLUR_MAX_PIXELS} pixels")
+            levels = [(kind, level) for kind, level in levels if kind != "blur_sigma"]
+        for kind, level in levels:
+            tail = robustness_tail(kind, level)
+            level_probs, level_preds = [], []
+            for images, _ in build_inference_loader(dataset=dataset, batch_size=batch_size, num_workers=num_workers):
+                probs, preds = class_probabilities(model, images, device, amp, tail=tail)
+                level_probs.append(probs.cpu())
+                level_preds.append(preds.cpu())
+            perturbed, _, _ = _split_metrics(name, split, torch.cat(level_probs), torch.cat(level_preds), targets_t, num_classes,
+                                             threshold)                     # judged at the clean pass's threshold
+            perturbed["perturbation"] = {kind: level}
+            with (run_paths.logs / "metrics.jsonl").open("a", encoding="utf-8") as handle:
+                handle.write(json.dumps(perturbed) + "\n")
+            extras = " ".join(f"{k}={v:.4f}" for k, v in perturbed.items() if isinstance(v, float) and k != "accuracy")
+            out.print(f"[bold]Robustness[/] {kind}={level:g}: accuracy {perturbed['accuracy']:.4f} {extras}")
     limit = cam_limit(infer_cfg)
     if limit is not None:
         if device.type != "cuda":

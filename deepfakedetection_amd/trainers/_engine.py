@@ -47,7 +47,7 @@ from ..orchestration.train_env import (
     apply_seed, create_console, env_float, env_int, env_path, env_str, maybe_load_checkpoint, prepare_training_environment,
     save_best_checkpoint, save_latest_checkpoint,
 )
-from ._inputs import device_batches, get_loaders, jpeg_settings, make_loader, policy_settings
+from ._inputs import blur_settings, device_batches, get_loaders, jpeg_settings, make_loader, policy_settings
 
 DATA_ROOT = Path.home() / "code" / "DeepfakeDetection" / "data" / "Dataset"
 LOG_EVERY = 10
@@ -463,6 +463,7 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
         console.print(f"Expected: {data_root}/{train_split}/<class> and {data_root}/{val_split}/<class>")
         raise SystemExit(1)
     jpeg_settings()         # likewise a bad training.jpeg_p / jpeg_quality_min / jpeg_quality_max
+    blur_settings()         # and a bad training.blur_p / blur_sigma_min / blur_sigma_max
     policy_settings()       # a bad training.rand_augment_* / trivial_augment is a ValueError here, not a class-count message below
     clip_cfg = clip_settings()      # and so is a bad training.clip_grad / clip_mode
     try:

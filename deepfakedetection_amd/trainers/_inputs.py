@@ -53,13 +53,24 @@ def jpeg_settings() -> tuple[float, int, int] | None:
     return D.check_jpeg(p, env_int("JPEG_QUALITY_MIN", 60), env_int("JPEG_QUALITY_MAX", 100))
 
 
+def blur_settings() -> tuple[float, float, float] | None:
+    """(p, sigma_min, sigma_max) of the Gaussian-blur augmentation from $BLUR_P (YAML training.blur_p; absent or 0: off),
+    $BLUR_SIGMA_MIN (default 0.0) and $BLUR_SIGMA_MAX (default 3.0).  ValueError for p outside 0..1 or a sigma range outside
+    0 <= min <= max <= 16."""
+    p = env_float("BLUR_P", 0.0)
+    if p == 0:
+        return None
+    return D.check_blur(p, env_float("BLUR_SIGMA_MIN", 0.0), env_float("BLUR_SIGMA_MAX", 3.0))
+
+
 _POLICY_FROM_ENV = object()
 
 
 def build_transforms(img_size: int, gpu_tail: bool = False, *, rotation_default: bool | None = None,
                      erasing_default: bool | None = None, jitter=(0.2, 0.2, 0.2, 0.05), rotation_after_flip: bool = False,
                      gpu_resize: bool = False, policy: PolicySettings | None = _POLICY_FROM_ENV,
-                     jpeg: tuple[float, int, int] | None = _POLICY_FROM_ENV):
+                     jpeg: tuple[float, int, int] | None = _POLICY_FROM_ENV,
+                     blur: tuple[float, float, float] | None = _POLICY_FROM_ENV):
     """(train, val) pipelines from the toggle defaults of the reference + $TRANSFORMS.
     gpu_tail=True: the pipelines end in uint8 HWC tensors and (train, val, train_tail, val_tail) is
     returned, the tails being `D.GpuInputTail`s that do flip / to-float / normalise / erasing on the GPU.
@@ -79,11 +90,18 @@ def build_transforms(img_size: int, gpu_tail: bool = False, *, rotation_default:
     jpeg (default: jpeg_settings(), i.e. $JPEG_P / $JPEG_QUALITY_MIN / $JPEG_QUALITY_MAX; None: off): (p, quality_min, quality_max) of
     the JPEG-compression augmentation, the last operation on bytes of the training pipeline, never in the validation one:
     D.RandomJpeg directly in front of ToTensor without gpu_tail; with gpu_tail always on the device (D.GpuInputTail(jpeg=),
-    csrc/dfd_jpeg.hip, byte-exact with Pillow) and never in the workers."""
+    csrc/dfd_jpeg.hip, byte-exact with Pillow) and never in the workers.
+    blur (default: blur_settings(), i.e. $BLUR_P / $BLUR_SIGMA_MIN / $BLUR_SIGMA_MAX; None: off): (p, sigma_min, sigma_max) of the
+    Gaussian-blur augmentation, directly behind the policy's slot and directly in front of RandomJpeg in the training pipeline,
+    never in the validation one.  It counts like rotation, jitter and a policy: without gpu_tail D.RandomBlur runs in the workers;
+    with gpu_tail it runs on the device (D.GpuInputTail(blur=), csrc/dfd_blur.hip, byte-exact with Pillow) whenever one picture
+    fits the augment kernel's LDS, and else in the workers in front of ToUint8HWC."""
     if policy is _POLICY_FROM_ENV:
         policy = policy_settings()
     if jpeg is _POLICY_FROM_ENV:
         jpeg = jpeg_settings()
+    if blur is _POLICY_FROM_ENV:
+        blur = blur_settings()
     small = img_size <= 64
     toggles = load_transform_toggles(
         {
@@ -128,7 +146,7 @@ def build_transforms(img_size: int, gpu_tail: bool = False, *, rotation_default:
     want_rot = on("train_random_rotation", False) and (rotation_after_flip or not small)
     want_jit = on("train_color_jitter", False)
     aug_fits = img_size * img_size * 3 <= D.AUGMENT_MAX_BYTES
-    train_on_gpu = gpu_tail and gpu_resize and (aug_fits or not (want_rot or want_jit or policy is not None))
+    train_on_gpu = gpu_tail and gpu_resize and (aug_fits or not (want_rot or want_jit or policy is not None or blur is not None))
     if train_on_gpu:
         # the geometric head of the pipeline as a PLAN (same decisions, same RNG calls), pixels untouched
         train = [D.Lambda(_rgb)] if on("ensure_rgb", True) else []
@@ -145,7 +163,7 @@ def build_transforms(img_size: int, gpu_tail: bool = False, *, rotation_default:
                                     erase_p=0.5 if on("train_random_erasing", False) else 0.0,
                                     rotate_degrees=10.0 if want_rot else 0.0, jitter=jitter if want_jit else None,
                                     rand_augment=policy.rand_augment if policy is not None else None,
-                                    trivial_augment=policy is not None and policy.trivial_augment, jpeg=jpeg)
+                                    trivial_augment=policy is not None and policy.trivial_augment, jpeg=jpeg, blur=blur)
     elif gpu_tail:
         # flip commutes with the per-pixel colour jitter, so it can move behind it onto the device — unless a policy follows
         worker_flip = policy is not None and on("train_random_horizontal_flip", True)
@@ -157,11 +175,14 @@ def build_transforms(img_size: int, gpu_tail: bool = False, *, rotation_default:
             train.append(D.ColorJitter(*jitter))
         if policy is not None:
             train.append(policy.transform())
+        if blur is not None and not aug_fits:
+            train.append(D.RandomBlur(blur[0], (blur[1], blur[2])))
         train.append(D.ToUint8HWC())
         train_tail = D.GpuInputTail(mean if on("train_normalize", True) else [0.0] * 3,
                                     std if on("train_normalize", True) else [1.0] * 3,
                                     flip_p=0.5 if on("train_random_horizontal_flip", True) and not worker_flip else 0.0,
-                                    erase_p=0.5 if on("train_random_erasing", False) else 0.0, jpeg=jpeg)
+                                    erase_p=0.5 if on("train_random_erasing", False) else 0.0, jpeg=jpeg,
+                                    blur=blur if aug_fits else None)
     else:
         if not rotation_after_flip and on("train_random_horizontal_flip", True):
             train.append(D.RandomHorizontalFlip())
@@ -169,6 +190,8 @@ def build_transforms(img_size: int, gpu_tail: bool = False, *, rotation_default:
             train.append(D.ColorJitter(*jitter))
         if policy is not None:
             train.append(policy.transform())
+        if blur is not None:
+            train.append(D.RandomBlur(blur[0], (blur[1], blur[2])))
         if jpeg is not None:
             train.append(D.RandomJpeg(jpeg[0], (jpeg[1], jpeg[2])))
         if on("train_to_tensor", True):

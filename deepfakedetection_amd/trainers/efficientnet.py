@@ -17,7 +17,7 @@ from ._engine import (  # noqa: F401  (re-exported)
     ACC, ACC_COUNTS, DATA_ROOT, LOG_EVERY, EvalResult, TrainerSpec, clip_settings, ema_settings, eval_forward, evaluate, make_mixer, make_stepper,
     mix_settings, run, train_one_epoch,
 )
-from ._inputs import PolicySettings, build_transforms, device_batches, get_loaders, jpeg_settings, make_loader, policy_settings  # noqa: F401
+from ._inputs import PolicySettings, blur_settings, build_transforms, device_batches, get_loaders, jpeg_settings, make_loader, policy_settings  # noqa: F401
 
 DEFAULT_MODEL = "efficientnet_b3"
 DEFAULT_EPOCHS, DEFAULT_BATCH_SIZE, DEFAULT_IMG_SIZE, DEFAULT_NUM_WORKERS = 25, 64, 224, 8

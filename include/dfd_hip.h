@@ -88,7 +88,8 @@ typedef void* dfd_stream;          /* a hipStream_t */
  * 140 = dfd_grad_sumsq, dfd_grad_clip_finish, dfd_adamw_step_clip (gradient clipping by global norm or by value in the AdamW step);
  * 141 = the one-kernel depthwise backward export of 120 (3x3 stride 1, data and weight gradient together) removed;
  * 142 = dfd_jpeg_u8, dfd_jpeg_ws (JPEG-compression augmentation: the pixels of a baseline JPEG round trip, byte-exact with Pillow);
- * 143 = dfd_tune keeps keys 0, 4 and 8-11; keys 1-3, 5-7, 12 and 13 (A/B-only sizes and the timing-only ablation mask) are DFD_EINVAL. */
+ * 143 = dfd_tune keeps keys 0, 4 and 8-11; keys 1-3, 5-7, 12 and 13 (A/B-only sizes and the timing-only ablation mask) are DFD_EINVAL;
+ * 144 = dfd_blur_u8 (Gaussian-blur augmentation: Pillow's three box passes along x and three along y, byte-exact). */
 int dfd_version(void);
 
 /* Planner knobs: the tier switches and grid sizes by which tests and per-layer scripts reach a kernel tier.  Process-wide plain ints:
@@ -495,6 +496,17 @@ int dfd_augment_policy_u8(const unsigned char* src, const dfd_augment_policy_job
  * W >= 5 (libjpeg upsamples a chroma plane of width 1 or 2 differently): DFD_EINVAL otherwise, and for a NULL pointer.  Two launches. */
 int dfd_jpeg_u8(const unsigned char* src, const int* jobs_dev, void* ws, unsigned char* out, int N, int H, int W, dfd_stream stream);
 size_t dfd_jpeg_ws(int N, int H, int W);
+/* Gaussian-blur augmentation (data.RandomBlur is its PIL form): picture n of the uint8 [N][H][W][3] batch `src` becomes in `out` what
+ * Image.filter(ImageFilter.GaussianBlur(radius=sigma)) makes of it, byte for byte: three extended box blurs along x, then three along
+ * y, each pass out[x] = (ww * sum_{|d| <= r} in[x + d] + fw * (in[x - r - 1] + in[x + r + 1]) + 2^23) >> 24 on replicated edges,
+ * rounded to a byte, the three channels apart (csrc/dfd_blur.hip; tests/_blur_ref.py restates it in numpy).  jobs_dev: DEVICE int32
+ * [N][4] = {r, ww, fw, 0} as data.blur_plan(sigma) gives them.  A job with ww == 0 copies its picture through, and so does one with r
+ * outside 0..DFD_BLUR_MAX_RADIUS (sigma 16 has r = 15): defined behaviour, the jobs cannot be checked on the host.  The blur commutes
+ * with a mirror in x, so the jobs carry no flip.  src != out; H * W <= DFD_BLUR_MAX_PIXELS (two byte planes of one channel stay in one
+ * CU's LDS through all six passes): DFD_EINVAL otherwise, and for a NULL pointer or N, H or W below 1.  One launch. */
+#define DFD_BLUR_MAX_RADIUS 32
+#define DFD_BLUR_MAX_PIXELS (78 * 1024)
+int dfd_blur_u8(const unsigned char* src, const int* jobs_dev, unsigned char* out, int N, int H, int W, dfd_stream stream);
 
 /* Input tail on the device (trainers/efficientnet.py:111-234): a uint8 NHWC
  * batch [N][H][W][3] -> RandomHorizontalFlip -> ToTensor (/255) -> Normalize((x-mean)/std) ->
