@@ -834,10 +834,12 @@ k_ce_rows(const float* __restrict__ logits, const int64_t* __restrict__ targets,
     const float lse = __logf(se);
     const int tgt = (int)targets[n];
     // sum_j logp_j = sl - J*lse ; logp_t = lr[t] - mx - lse
+    // eps == 0: a -inf logit off the target (probability 0, no weight in the loss) makes smooth +inf, and 0 * inf is NaN where
+    // torch's loss is finite.  The product is not formed then; the zero of smooth's sign is what it is for every finite smooth.
     if (t == 0) {
         const float logp_t = lr[tgt] - mx - lse;
         const float smooth = -(sl - (float)J * lse) / (float)J;
-        row_loss[n] = (1.f - eps) * (-logp_t) + eps * smooth;
+        row_loss[n] = (1.f - eps) * (-logp_t) + (eps == 0.f ? copysignf(0.f, smooth) : eps * smooth);
     }
     if (dlogits) {
         const float inv = 1.f / se, sc = gscale / (float)N;
@@ -917,7 +919,10 @@ k_softmax_argmax(const float* __restrict__ logits, int J, float* __restrict__ pr
     for (int j = t; j < J; j += DFD_THREADS) se += __expf(lr[j] - mx);
     se = block_reduce(se, sm, false);
     const float inv = 1.f / se;
-    float bp = -1.f; int bi = 0x7fffffff;
+    // A thread starts from (-1, index 0): any probability, which is >= 0, beats it, so a thread without a column never wins.  A
+    // NaN or an infinity in the row makes every probability NaN, none of which compares greater: the arg max is then 0, the
+    // index torch.argmax(torch.softmax(row)) returns, and stays an index into the row.
+    float bp = -1.f; int bi = 0;
     for (int j = t; j < J; j += DFD_THREADS) {
         const float p = __expf(lr[j] - mx) * inv;
         if (probs) probs[(long)n * J + j] = p;

@@ -89,7 +89,9 @@ typedef void* dfd_stream;          /* a hipStream_t */
  * 141 = the one-kernel depthwise backward export of 120 (3x3 stride 1, data and weight gradient together) removed;
  * 142 = dfd_jpeg_u8, dfd_jpeg_ws (JPEG-compression augmentation: the pixels of a baseline JPEG round trip, byte-exact with Pillow);
  * 143 = dfd_tune keeps keys 0, 4 and 8-11; keys 1-3, 5-7, 12 and 13 (A/B-only sizes and the timing-only ablation mask) are DFD_EINVAL;
- * 144 = dfd_blur_u8 (Gaussian-blur augmentation: Pillow's three box passes along x and three along y, byte-exact). */
+ * 144 = dfd_blur_u8 (Gaussian-blur augmentation: Pillow's three box passes along x and three along y, byte-exact);
+ * 145 = dfd_softmax_argmax returns index 0 for a row that holds a NaN or an infinity (it returned 0x7fffffff), dfd_ce_loss with
+ * label_smoothing 0 keeps a finite loss beside a -inf logit off the target (it returned NaN); finite inputs give the same bits. */
 int dfd_version(void);
 
 /* Planner knobs: the tier switches and grid sizes by which tests and per-layer scripts reach a kernel tier.  Process-wide plain ints:
@@ -398,7 +400,8 @@ int dfd_linear_bwd(const float* dout, const float* x, const float* w, float* dx,
                    float* dw, float* db, int N, int K, int J, int accumulate,
                    dfd_stream stream);
 /* nn.CrossEntropyLoss(label_smoothing) mean-reduced; dlogits (optional) is
- * d(loss*grad_scale)/dlogits.                                                     */
+ * d(loss*grad_scale)/dlogits.  With label_smoothing 0 a -inf logit off the target
+ * leaves the loss finite and has gradient 0, as in torch.  Targets are not range-checked. */
 int dfd_ce_loss(const float* logits, const int64_t* targets, int N, int J,
                 float label_smoothing, float grad_scale, float* row_loss, float* loss,
                 float* dlogits, dfd_stream stream);
@@ -408,6 +411,8 @@ int dfd_ce_loss(const float* logits, const int64_t* targets, int N, int J,
 int dfd_ce_loss_soft(const float* logits, const float* targets, int N, int J,
                      float label_smoothing, float grad_scale, float* row_loss, float* loss,
                      float* dlogits, dfd_stream stream);
+/* probs (optional) = softmax(logits) per row, preds = its arg max, the lowest index on ties.  A row that holds a NaN or an
+ * infinity has NaN probabilities and preds 0 (torch.argmax(torch.softmax(row))): preds is always an index into the row. */
 int dfd_softmax_argmax(const float* logits, int N, int J, float* probs, int64_t* preds,
                        dfd_stream stream);
 /* Resize + CenterCrop / RandomResizedCrop of decoded uint8 RGB images on the device, bit-exact with Pillow's bilinear

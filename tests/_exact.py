@@ -915,17 +915,23 @@ def attn_apply(case):
     return NS(shape=case, f=f32(f), x=f32(x), g=f32(g), out=out, out_t=out_t)
 
 
-LINEAR_CASE = (6, 1280, 10)                             # N, K, J of the classifier head
+# N, K, J of the classifier head.  (6, 1280, 10): fewer rows than one 8-row trip of the weight gradient, K a multiple of 64.
+# (72, 176, 2), the EfficientFormerV2-S0 head: K % 64 = 48, nine 8-row trips, a second trip of the bias-gradient loop.
+# (13, 224, 3): one 8-row trip and a remainder of 5, K % 64 = 32, a wave that holds 3 of its 4 outputs.
+LINEAR_CASES = [(6, 1280, 10), (72, 176, 2), (13, 224, 3)]
 
 
-@functools.lru_cache(maxsize=1)
-def linear():
-    N, Kd, J = LINEAR_CASE
+@functools.lru_cache(maxsize=len(LINEAR_CASES))
+def linear(case=LINEAR_CASES[0]):
+    N, Kd, J = case
     x, w, b, dout = pick((N, Kd), 6400, S3), pick((J, Kd), 6401, S3), pick((J,), 6402, S3), pick((N, J), 6403, S3)
-    out = matmul_case("linear_fwd", x, w.t(), (F32,), (F32,)) + b
-    dx = matmul_case("linear dx", dout, w, (F32,), (F32,))
-    dwt = matmul_case("linear dw", dout.t(), x, (F32,), (F32,))
-    return NS(x=f32(x), w=f32(w), b=f32(b), dout=f32(dout), out=out, dx=dx, dw=dwt, db=dout.sum(0))
+    out = matmul_case(f"linear_fwd {case}", x, w.t(), (F32,), (F32,)) + b
+    dx = matmul_case(f"linear dx {case}", dout, w, (F32,), (F32,))
+    dwt = matmul_case(f"linear dw {case}", dout.t(), x, (F32,), (F32,))
+    db = dout.sum(0)
+    check_exact(f"linear bias {case}", operands=[("b", b, (F32,))], reductions=[("db", dout.abs().sum(0), 1.0)],
+                results=[("out", out, (F32,)), ("db", db, (F32,))])
+    return NS(x=f32(x), w=f32(w), b=f32(b), dout=f32(dout), out=out, dx=dx, dw=dwt, db=db)
 
 
 GEMM_BIAS_ACT_CASE = (256 * 80 + 17, 192, 520)          # M, K, N: served by dfd_gemm_bias_act (tests/test_vit_ops_gpu.py)

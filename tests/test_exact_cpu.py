@@ -211,10 +211,6 @@ def test_vit_matrix_products():
         back = lambda t, T: t.permute(0, 2, 1, 3).reshape(B, T, 1, H * D)
         same(R.rnd(back(0.5 * (R.rnd(c.f, BF16) @ heads(c.x, Tc)), To), BF16), c.out, f"attn_apply {case}")
         same(R.rnd(back(0.5 * (R.rnd(c.f, BF16).transpose(-1, -2) @ heads(c.g, To)), Tc), BF16), c.out_t, f"attn_apply^T {case}")
-    l = E.linear()
-    same(F.linear(l.x, l.w, l.b), l.out, "linear_fwd")
-    same(l.dout @ l.w, l.dx, "linear dx")
-    same(l.dout.t() @ l.x, l.dw, "linear dw")
     g = E.gemm_bias_act()
     y = R.rnd(g.a @ g.w.t(), BF16)
     same(y, g.y, "gemm_bias_act product")
@@ -230,6 +226,16 @@ def test_vit_matrix_products():
     t = torch.zeros(v.T, v.H, requires_grad=True)
     (16 * torch.sigmoid(t[v.ridx.long()].view(v.nl, v.nl, v.H).permute(2, 0, 1))).backward(v.dbias[:, v.ng:, v.ng:])
     same(t.grad, v.dtable, "relpos_bias_bwd at table = 0")
+
+
+@pytest.mark.parametrize("case", E.LINEAR_CASES)
+def test_linear_head(case):
+    """test_linear_is_exact of tests/test_exact_gpu.py: the builder has checked that every sum stays exact in f32; plain f32 torch agrees."""
+    l = E.linear(case)
+    same(F.linear(l.x, l.w, l.b), l.out, f"linear_fwd {case}")
+    same(l.dout @ l.w, l.dx, f"linear dx {case}")
+    same(l.dout.t() @ l.x, l.dw, f"linear dw {case}")
+    same(l.dout.sum(0), l.db, f"linear db {case}")
 
 
 def _mlp32(c):

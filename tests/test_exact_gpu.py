@@ -410,15 +410,16 @@ def test_attn_apply_is_exact(case):
     same(K.attn_apply(f, dev(c.g, BF16), (B, Tc, 1, H * D), H, alpha=0.5, transpose=True), c.out_t, f"attn_apply {case} transposed")
 
 
-def test_linear_is_exact():
+@pytest.mark.parametrize("case", E.LINEAR_CASES)
+def test_linear_is_exact(case):
     K = _k()
-    c = E.linear()
+    c = E.linear(case)
     x, w, b, dout = dev(c.x), dev(c.w), dev(c.b), dev(c.dout)
-    same(K.linear_fwd(x, w, b), c.out, "linear_fwd")
+    same(K.linear_fwd(x, w, b), c.out, f"linear_fwd {case}")
     dx, dw, db = K.linear_bwd(dout, x, w, True, True, True)
-    same(dx, c.dx, "linear_bwd dx")
-    same(dw, c.dw, "linear_bwd dw")
-    same(db, c.db, "linear_bwd db")
+    same(dx, c.dx, f"linear_bwd dx {case}")
+    same(dw, c.dw, f"linear_bwd dw {case}")
+    same(db, c.db, f"linear_bwd db {case}")
 
 
 def test_gemm_bias_act_is_exact():
