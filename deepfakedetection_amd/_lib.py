@@ -36,6 +36,15 @@ AUG_MAX_OPS = 4
 BLUR_MAX_RADIUS = 32
 BLUR_MAX_PIXELS = 78 * 1024
 AUG_POLICY_JOB_WORDS = 16 + 2 + 9 * AUG_MAX_OPS     # struct dfd_augment_policy_job in int32 words (216 bytes)
+# csrc/dfd_metrics.hip (the DFD_ROC_* / DFD_CONFUSION_* constants of include/dfd_hip.h)
+ROC_TILE = 2048                     # scores per workgroup of dfd_roc_curve's tile passes
+ROC_SCAN_WIDTH = 1024               # tile totals its scan takes per trip
+ROC_MAX_N = 1 << 28
+ROC_MAX_CUTS = 4096
+ROC_STATS_LEN = 5
+(ROC_P, ROC_N, ROC_G, ROC_NONFINITE, ROC_TWO_U) = range(5)
+CONFUSION_LDS_MAX_J = 128           # largest J whose J x J int32 histogram stays in LDS
+CONFUSION_MAX_J = 1024
 
 
 class DwShape(Structure):
@@ -126,6 +135,11 @@ SIGNATURES: dict[str, tuple] = {
     "dfd_jpeg_ws": (c_size_t, [c_int, c_int, c_int]),
     # ---- ABI 144
     "dfd_blur_u8": (c_int, [P, P, P, c_int, c_int, c_int, P]),
+    # ---- ABI 146
+    "dfd_roc_ws": (c_size_t, [c_int]),
+    "dfd_roc_curve": (c_int, [P, P, c_int, c_int64, P, c_size_t, P, P, P, P, P]),
+    "dfd_roc_sweep": (c_int, [P, P, P, P, c_int, P, c_int, P, P, P]),
+    "dfd_confusion": (c_int, [P, P, c_int, c_int, P, P, P]),
     # ---- ABI 111
     "dfd_bn_eval_coeffs_multi": (c_int, [P, c_int, P]),
     "dfd_sum_batch_begin": (c_int, []),

@@ -340,14 +340,14 @@ def _nbytes(t: torch.Tensor | None) -> int:
     return 0 if t is None else t.numel() * t.element_size()
 
 
-def _dst(out: torch.Tensor | None, shape, device) -> torch.Tensor:
-    """A caller-provided destination (gradient-arena slot) or a fresh f32 tensor."""
+def _dst(out: torch.Tensor | None, shape, device, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """A caller-provided destination (gradient-arena slot) or a fresh tensor (f32 unless `dtype` says otherwise)."""
     if out is None:
         # a fresh tensor is handed to autograd, which adds it to (or clones it into) .grad as soon as the Function returns: the open
         # batch's sums may then not wait for a carrier launch (sum_batch)
         _sum_batch.temp_dest = True
-        return torch.empty(shape, dtype=torch.float32, device=device)
-    if tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or not out.is_contiguous():
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or not out.is_contiguous():
         raise ValueError(f"bad gradient destination {tuple(out.shape)} for {tuple(shape)}")
     return out
 
@@ -1175,6 +1175,78 @@ def softmax_argmax(logits: torch.Tensor, want_probs: bool = True):
     preds = torch.empty(N, dtype=torch.int64, device=logits.device)
     check(_L().dfd_softmax_argmax(_p(logits), N, J, _p(probs), _p(preds), _stream()), "dfd_softmax_argmax")
     return probs, preds
+
+
+# ------------------------------------------------------------------ evaluation metrics (ABI 146, csrc/dfd_metrics.hip)
+ROC_TILE, ROC_SCAN_WIDTH = _lib.ROC_TILE, _lib.ROC_SCAN_WIDTH
+ROC_MAX_N, ROC_MAX_CUTS, ROC_STATS_LEN = _lib.ROC_MAX_N, _lib.ROC_MAX_CUTS, _lib.ROC_STATS_LEN
+CONFUSION_LDS_MAX_J, CONFUSION_MAX_J = _lib.CONFUSION_LDS_MAX_J, _lib.CONFUSION_MAX_J
+
+
+def roc_ws(n: int) -> int:
+    """Bytes of workspace roc_curve needs for n scores."""
+    if not 0 <= n <= ROC_MAX_N:
+        raise ValueError(f"roc_curve takes 0..{ROC_MAX_N} scores, got {n}")
+    return _L().dfd_roc_ws(n)
+
+
+def roc_curve(scores: torch.Tensor, labels: torch.Tensor, positive: int = 1, ws: torch.Tensor | None = None, out=None):
+    """f32 [n] scores sorted ascending and their int64 labels in the same order -> (thr f32 [n], cum_pos int64 [n], cum_neg
+    int64 [n], stats int64 [ROC_STATS_LEN] = P, N, G, nonfinite, two_u): the ROC curve by tie group, compacted to the first G
+    entries (the rest is not written), and twice the Mann-Whitney U (include/dfd_hip.h).  Four launches, no host sync: G is read
+    by whoever reads `stats`.  `ws`: at least roc_ws(n) bytes of uint8 scratch; `out`: the four destinations."""
+    if scores.dim() != 1 or scores.dtype != torch.float32 or labels.shape != scores.shape or labels.dtype != torch.int64:
+        raise ValueError("roc_curve: expected f32 [n] scores and int64 [n] labels")
+    n, device = scores.numel(), scores.device
+    need = roc_ws(n)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
+    elif ws.dtype != torch.uint8 or ws.numel() < need or ws.device != device:
+        raise ValueError(f"roc_curve: ws must be a uint8 tensor of at least {need} bytes on {device}")
+    o_thr, o_pos, o_neg, o_stats = out if out is not None else (None, None, None, None)
+    thr = _dst(o_thr, (n,), device)
+    cum_pos = _dst(o_pos, (n,), device, torch.int64)
+    cum_neg = _dst(o_neg, (n,), device, torch.int64)
+    stats = _dst(o_stats, (ROC_STATS_LEN,), device, torch.int64)
+    check(_L().dfd_roc_curve(_p(scores), _p(labels), n, int(positive), _p(ws), ws.numel(), _p(thr), _p(cum_pos), _p(cum_neg),
+                             _p(stats), _stream()), "dfd_roc_curve", f"n={n}")
+    return thr, cum_pos, cum_neg, stats
+
+
+def roc_sweep(thr: torch.Tensor, cum_pos: torch.Tensor, cum_neg: torch.Tensor, stats: torch.Tensor, cuts: torch.Tensor, out=None):
+    """roc_curve's outputs + T <= ROC_MAX_CUTS ascending f64 cut points on the device -> (tp, fp) int64 [T]: the positives /
+    negatives with score >= cut, compared in f64.  One launch; G, P and N are read from `stats` on the device."""
+    if cuts.dim() != 1 or cuts.dtype != torch.float64 or not 1 <= cuts.numel() <= ROC_MAX_CUTS:
+        raise ValueError(f"roc_sweep: expected 1..{ROC_MAX_CUTS} f64 cut points")
+    if thr.dtype != torch.float32 or cum_pos.dtype != torch.int64 or cum_neg.dtype != torch.int64 or stats.dtype != torch.int64 \
+            or cum_pos.numel() != thr.numel() or cum_neg.numel() != thr.numel() or stats.numel() != ROC_STATS_LEN:
+        raise ValueError("roc_sweep: expected roc_curve's (thr, cum_pos, cum_neg, stats)")
+    T, device = cuts.numel(), cuts.device
+    o_tp, o_fp = out if out is not None else (None, None)
+    tp = _dst(o_tp, (T,), device, torch.int64)
+    fp = _dst(o_fp, (T,), device, torch.int64)
+    check(_L().dfd_roc_sweep(_p(thr), _p(cum_pos), _p(cum_neg), _p(stats), thr.numel(), _p(cuts), T, _p(tp), _p(fp), _stream()),
+          "dfd_roc_sweep", f"T={T}")
+    return tp, fp
+
+
+def confusion_counts(truth: torch.Tensor, pred: torch.Tensor, num_classes: int, out=None):
+    """int64 [n] truth and predictions -> (counts int64 [J, J] with row = truth and column = prediction, oob int64 [1] = the
+    pairs with a label outside [0, J), which the matrix leaves out).  J <= CONFUSION_LDS_MAX_J counts in LDS, above that (up to
+    CONFUSION_MAX_J) with global integer adds."""
+    J = int(num_classes)
+    if not 1 <= J <= CONFUSION_MAX_J:
+        raise ValueError(f"confusion_counts: num_classes must be 1..{CONFUSION_MAX_J}, got {J}")
+    if truth.dim() != 1 or truth.dtype != torch.int64 or pred.shape != truth.shape or pred.dtype != torch.int64:
+        raise ValueError("confusion_counts: expected int64 [n] truth and predictions")
+    n, device = truth.numel(), truth.device
+    if n >= 1 << 31:
+        raise ValueError("confusion_counts: at most 2^31 - 1 samples")
+    o_counts, o_oob = out if out is not None else (None, None)
+    counts = _dst(o_counts, (J, J), device, torch.int64)
+    oob = _dst(o_oob, (1,), device, torch.int64)
+    check(_L().dfd_confusion(_p(truth), _p(pred), n, J, _p(counts), _p(oob), _stream()), "dfd_confusion", f"n={n} J={J}")
+    return counts, oob
 
 
 # ------------------------------------------------------------------ Grad-CAM (ABI 136)

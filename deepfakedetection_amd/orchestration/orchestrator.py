@@ -170,7 +170,8 @@ _EXTRA_TRAIN_ENV = (("ft_batch_size", "FT_BATCH_SIZE"), ("pretrained", "PRETRAIN
                     ("rand_augment_ops", "RAND_AUGMENT_OPS"), ("rand_augment_magnitude", "RAND_AUGMENT_MAGNITUDE"),
                     ("trivial_augment", "TRIVIAL_AUGMENT"), ("clip_grad", "CLIP_GRAD"), ("clip_mode", "CLIP_MODE"),
                     ("jpeg_p", "JPEG_P"), ("jpeg_quality_min", "JPEG_QUALITY_MIN"), ("jpeg_quality_max", "JPEG_QUALITY_MAX"),
-                    ("blur_p", "BLUR_P"), ("blur_sigma_min", "BLUR_SIGMA_MIN"), ("blur_sigma_max", "BLUR_SIGMA_MAX"))
+                    ("blur_p", "BLUR_P"), ("blur_sigma_min", "BLUR_SIGMA_MIN"), ("blur_sigma_max", "BLUR_SIGMA_MAX"),
+                    ("val_auc", "VAL_AUC"), ("select_metric", "SELECT_METRIC"))
 
 
 def _first_set(*values: Any) -> Any:
@@ -418,8 +419,9 @@ def confusion_counts(truth: np.ndarray, pred: np.ndarray) -> np.ndarray:
     return cm
 
 
-def _save_plots(cm: np.ndarray, labels: list[str], truth: np.ndarray, scores: np.ndarray | None, plots: Path) -> None:
-    """confusion_matrix.png / roc_curve.png; skipped quietly when matplotlib/sklearn are absent."""
+def _save_plots(cm: np.ndarray, labels: list[str], truth: np.ndarray, scores: np.ndarray | None, plots: Path, roc=None) -> None:
+    """confusion_matrix.png / roc_curve.png; skipped quietly when matplotlib/sklearn are absent.  roc: a metrics.RocResult
+    (inference.device_metrics) whose integer curve is drawn instead of sklearn's."""
     try:
         import matplotlib
 
@@ -440,15 +442,21 @@ def _save_plots(cm: np.ndarray, labels: list[str], truth: np.ndarray, scores: np
     fig.tight_layout()
     fig.savefig(plots / "confusion_matrix.png")
     plt.close(fig)
-    if scores is not None:
+    points = None
+    if roc is not None:
+        if roc.n_pos and roc.n_neg and not roc.nonfinite:
+            fps, tps, _ = roc.curve()
+            points = np.concatenate([[0.0], fps / roc.n_neg]), np.concatenate([[0.0], tps / roc.n_pos])
+    elif scores is not None:
         try:
             from sklearn.metrics import roc_curve
 
-            fpr, tpr, _ = roc_curve(truth, scores)
+            points = roc_curve(truth, scores)[:2]
         except Exception:  # noqa: BLE001
             return
+    if points is not None:
         fig, ax = plt.subplots(figsize=(6, 5))
-        ax.plot(fpr, tpr)
+        ax.plot(*points)
         ax.set_title("ROC Curve")
         ax.set_xlabel("False Positive Rate")
         ax.set_ylabel("True Positive Rate")
@@ -511,6 +519,55 @@ def _split_metrics(name: str, split: str, probs_t: torch.Tensor, preds_t: torch.
     return metrics, preds_t, cm
 
 
+SWEEP_STEPS = 501           # best_balanced_accuracy_threshold's grid
+
+
+def _device_threshold(book) -> float | None:
+    """best_balanced_accuracy_threshold of a validation pass kept in a metrics.ScoreBook, from the device sweep; None when
+    the pass saw one class only (or scores that are not finite): the caller keeps its default."""
+    from ..metrics import binary_roc
+
+    res = binary_roc(book.probs[:, 1], book.targets, cuts=np.linspace(0.0, 1.0, SWEEP_STEPS, dtype=np.float64), strict=False)
+    if not res.n_pos or not res.n_neg or res.nonfinite:
+        return None
+    return res.best_balanced_accuracy_threshold()
+
+
+def _split_metrics_device(name: str, split: str, book, num_classes: int, threshold: float):
+    """_split_metrics of a pass kept in a metrics.ScoreBook (inference.device_metrics): the same record with the same keys, the
+    AUC, the equal error rate and the confusion matrix from the device kernels (exact, no sklearn), plus `eer` and
+    `balanced_accuracy` (mean recall over the classes that occur, at the record's predictions).  Returns (record, host
+    probabilities, host predictions, host targets, confusion matrix, the binary RocResult or None): one transfer of the book."""
+    from .. import metrics as M
+
+    probs_d, preds_d, targets_d = book.probs, book.preds, book.targets
+    roc = None
+    if num_classes == 2:
+        preds_d = (probs_d[:, 1] >= threshold).long()
+        roc = M.binary_roc(probs_d[:, 1], targets_d, strict=False)
+        auc, eer = roc.auc, roc.eer
+    else:
+        per_class = [M.binary_roc(probs_d[:, j], targets_d, positive=j, strict=False) for j in range(num_classes)]
+        present = all(r.n_pos and r.n_neg for r in per_class)
+        auc = float(sum(r.auc for r in per_class) / num_classes) if present else None
+        eer = float(sum(r.eer for r in per_class) / num_classes) if present else None
+    full = M.confusion(targets_d, preds_d, num_classes).cpu().numpy()
+    probs_t, preds_t, targets_t = probs_d.cpu(), preds_d.cpu(), targets_d.cpu()
+    accuracy = (preds_t == targets_t).float().mean().item()
+    record: dict[str, Any] = {"model": name, "split": split, "accuracy": accuracy, "timestamp": datetime.now().isoformat()}
+    if auc is not None:
+        record["roc_auc"] = auc
+    if num_classes == 2:
+        record["threshold"] = float(threshold)
+    occurs = (full.sum(0) + full.sum(1)) > 0                    # the labels in truth or prediction, as confusion_counts keeps them
+    cm = full[occurs][:, occurs]
+    record["confusion_matrix"] = cm.tolist()
+    rows = full.sum(1)
+    record["eer"] = eer
+    record["balanced_accuracy"] = float(np.mean(np.diag(full)[rows > 0] / rows[rows > 0])) if rows.any() else None
+    return record, probs_t, preds_t, targets_t, cm, roc
+
+
 def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: dict[str, Any], run_paths: RunPaths) -> None:
     tty = getattr(sys.stdout, "isatty", None)
     out = Console(file=sys.stdout, force_terminal=bool(tty()) if callable(tty) else False)
@@ -553,13 +610,27 @@ def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: 
     root = Path(data_cfg.get("root")).expanduser()
     if not root.is_absolute():
         root = (Path.cwd() / root).resolve()
+    # extra key: probabilities, predictions and targets stay on the device (metrics.ScoreBook) and AUC, EER, the threshold sweep
+    # and the confusion matrix come from the exact counting kernels; off (the default): the host path below, unchanged
+    device_metrics = as_bool(infer_cfg.get("device_metrics", False))
+    if device_metrics and device.type != "cuda":
+        out.print("[bold yellow]inference.device_metrics ignored[/]: needs a CUDA device; the host metrics run")
+        device_metrics = False
+    if device_metrics:
+        from ..metrics import ScoreBook
 
     threshold = 0.5
     if num_classes == 2:
         val_dir = root / data_cfg.get("val_split", "val")
         if val_dir.exists():
             val_set = D.ImageFolder(val_dir, transform=transform)
-            if len(val_set) > 0:
+            if len(val_set) > 0 and device_metrics:
+                book = ScoreBook(len(val_set), num_classes, device)
+                for images, targets in build_inference_loader(dataset=val_set, batch_size=batch_size, num_workers=num_workers):
+                    probs, _ = class_probabilities(model, images, device, amp)
+                    book.append(probs, None, targets.to(device, non_blocking=True))
+                threshold = _first_set(_device_threshold(book), threshold)
+            elif len(val_set) > 0:
                 scores, truth = [], []
                 for images, targets in build_inference_loader(dataset=val_set, batch_size=batch_size, num_workers=num_workers):
                     probs, _ = class_probabilities(model, images, device, amp)
@@ -582,24 +653,32 @@ def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: 
     progress = Progress(TextColumn("[bold blue]{task.description}"), BarColumn(bar_width=None), MofNCompleteColumn(),
                         TimeElapsedColumn(), TimeRemainingColumn(), TextColumn("{task.fields[speed]}"), console=out)
     all_probs, all_preds, all_targets = [], [], []
+    book = ScoreBook(len(dataset), num_classes, device) if device_metrics else None
     seen, start = 0, perf_counter()
     with progress:
         task = progress.add_task("inference", total=len(loader), speed="")
         for images, targets in loader:
             probs, preds = class_probabilities(model, images, device, amp)
-            all_probs.append(probs.cpu())
-            all_preds.append(preds.cpu())
-            all_targets.append(targets.cpu())
+            if book is not None:
+                book.append(probs, preds, targets.to(device, non_blocking=True))       # no host round trip per batch
+            else:
+                all_probs.append(probs.cpu())
+                all_preds.append(preds.cpu())
+                all_targets.append(targets.cpu())
             seen += targets.size(0)
             progress.update(task, advance=1, speed=f"{seen / max(perf_counter() - start, 1e-6):.1f} img/s")
 
-    probs_t, preds_t, targets_t = torch.cat(all_probs), torch.cat(all_preds), torch.cat(all_targets)
-    metrics, preds_t, cm = _split_metrics(name, split, probs_t, preds_t, targets_t, num_classes, threshold)
+    roc = None
+    if book is not None:
+        metrics, probs_t, preds_t, targets_t, cm, roc = _split_metrics_device(name, split, book, num_classes, threshold)
+    else:
+        probs_t, preds_t, targets_t = torch.cat(all_probs), torch.cat(all_preds), torch.cat(all_targets)
+        metrics, preds_t, cm = _split_metrics(name, split, probs_t, preds_t, targets_t, num_classes, threshold)
     accuracy = metrics["accuracy"]
     truth_np = targets_t.numpy()
     multi_label = torch.unique(targets_t).numel() > 1
     _save_plots(cm, list(dataset.classes), truth_np, probs_t[:, 1].numpy() if num_classes == 2 and multi_label else None,
-                run_paths.plots)
+                run_paths.plots, roc=roc)
     with (run_paths.logs / "metrics.jsonl").open("a", encoding="utf-8") as handle:
         handle.write(json.dumps(metrics) + "\n")
     extras = " ".join(f"{k}={v:.4f}" for k, v in metrics.items() if isinstance(v, float) and k != "accuracy")
@@ -617,12 +696,20 @@ def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: 
         for kind, level in levels:
             tail = robustness_tail(kind, level)
             level_probs, level_preds = [], []
-            for images, _ in build_inference_loader(dataset=dataset, batch_size=batch_size, num_workers=num_workers):
+            if book is not None:
+                book.reset()
+            for images, targets in build_inference_loader(dataset=dataset, batch_size=batch_size, num_workers=num_workers):
                 probs, preds = class_probabilities(model, images, device, amp, tail=tail)
-                level_probs.append(probs.cpu())
-                level_preds.append(preds.cpu())
-            perturbed, _, _ = _split_metrics(name, split, torch.cat(level_probs), torch.cat(level_preds), targets_t, num_classes,
-                                             threshold)                     # judged at the clean pass's threshold
+                if book is not None:
+                    book.append(probs, preds, targets.to(device, non_blocking=True))
+                else:
+                    level_probs.append(probs.cpu())
+                    level_preds.append(preds.cpu())
+            if book is not None:
+                perturbed = _split_metrics_device(name, split, book, num_classes, threshold)[0]
+            else:
+                perturbed, _, _ = _split_metrics(name, split, torch.cat(level_probs), torch.cat(level_preds), targets_t, num_classes,
+                                                 threshold)                     # judged at the clean pass's threshold
             perturbed["perturbation"] = {kind: level}
             with (run_paths.logs / "metrics.jsonl").open("a", encoding="utf-8") as handle:
                 handle.write(json.dumps(perturbed) + "\n")

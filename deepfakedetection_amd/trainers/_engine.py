@@ -44,7 +44,7 @@ from torch.utils.data import DataLoader
 from ..dp import GradAllReducer, all_reduce_counts, broadcast_module_state, init_distributed
 from ..orchestration.model_registry import get_model_spec
 from ..orchestration.train_env import (
-    apply_seed, create_console, env_float, env_int, env_path, env_str, maybe_load_checkpoint, prepare_training_environment,
+    apply_seed, as_bool, create_console, env_float, env_int, env_path, env_str, maybe_load_checkpoint, prepare_training_environment,
     save_best_checkpoint, save_latest_checkpoint,
 )
 from ._inputs import blur_settings, device_batches, get_loaders, jpeg_settings, make_loader, policy_settings
@@ -95,6 +95,8 @@ class EvalResult:
     total: int
     correct: int
     loss: float | None = None                       # mean CE loss when evaluate() got a criterion
+    auc: float | None = None                        # ROC-AUC over all ranks' validation scores (val_auc; macro one-vs-rest above two classes)
+    eer: float | None = None                        # equal error rate (val_auc, two classes)
 
 
 @dataclass(frozen=True)
@@ -102,6 +104,37 @@ class EpochResult:
     stats: dict                                     # throughput figures for logs/throughput.jsonl
     loss: float | None = None                       # mean training loss over all ranks (with_loss)
     clip: dict | None = None                        # the epoch's gradient-clipping record (clip_settings() on)
+
+
+@dataclass(frozen=True)
+class MetricSettings:
+    val_auc: bool           # evaluate() also reports the exact ROC-AUC (metrics.binary_roc on the device)
+    select: str             # "acc" or "auc": what the best epoch, early stopping and the best-weights file follow
+
+
+def metric_settings() -> MetricSettings:
+    """$VAL_AUC (YAML training.val_auc, default off) and $SELECT_METRIC (training.select_metric: acc | auc, default acc —
+    today's behaviour); selecting by AUC switches val_auc on."""
+    select = env_str("SELECT_METRIC", "acc").strip().lower() or "acc"
+    if select not in ("acc", "auc"):
+        raise ValueError(f"SELECT_METRIC must be acc or auc, got {select!r}")
+    return MetricSettings(val_auc=as_bool(env_str("VAL_AUC", "0")) or select == "auc", select=select)
+
+
+def selection_value(res: "EvalResult", metric: str) -> float | None:
+    """The figure of an evaluation that the best epoch follows; None (no AUC: a class is absent, or a diverged epoch's scores
+    are not finite) never counts as an improvement."""
+    if metric == "auc":
+        return None if res.auc is None or math.isnan(res.auc) else res.auc
+    return res.acc
+
+
+def improves(value: float | None, best: float) -> bool:
+    return value is not None and value > best + 1e-4
+
+
+def auc_suffix(res: "EvalResult") -> str:
+    return "" if res.auc is None else f" | auc={res.auc:.4f}"
 
 
 def eval_forward(model: nn.Module, device: str):
@@ -296,11 +329,14 @@ def _make_criterion_and_optimizer(use_cuda: bool):
     return nn.CrossEntropyLoss(label_smoothing=0.1), optim.AdamW
 
 
-def evaluate(model: nn.Module, dl: DataLoader, device: str, tail=None, criterion: nn.Module | None = None) -> EvalResult:
+def evaluate(model: nn.Module, dl: DataLoader, device: str, tail=None, criterion: nn.Module | None = None,
+             val_auc: bool = False) -> EvalResult:
     """Top-1 accuracy and, with a `criterion`, the mean loss; f32, no autocast (efficientnet.py:237-262,
     efficientformer_v2.py:206-219, fastervit.py:224-240).  The counters stay on the device and are read once at the end
-    (and summed over ranks in one collective)."""
+    (and summed over ranks in one collective).  val_auc: the softmax scores stay on the device as well, are gathered over the
+    ranks (disjoint validation shards) and give the exact ROC-AUC and equal error rate; non-finite scores give nan, not an error."""
     model.eval()
+    kept_probs, kept_targets = [], []
     correct = torch.zeros((), dtype=torch.float64, device=device)
     loss_sum = torch.zeros((), dtype=torch.float64, device=device) if criterion is not None else None
     total = 0
@@ -313,10 +349,23 @@ def evaluate(model: nn.Module, dl: DataLoader, device: str, tail=None, criterion
                 loss_sum += criterion(logits, targets).double() * targets.size(0)
             correct += (logits.argmax(1) == targets).sum()
             total += targets.numel()
+            if val_auc:
+                kept_probs.append(torch.softmax(logits.float(), dim=1))        # a new tensor: a graphed forward reuses `logits`
+                kept_targets.append(targets.to(torch.int64))
     sums = [float(correct), float(total)] + ([float(loss_sum)] if criterion is not None else [])
     n_correct, n_total, *s_loss = all_reduce_counts(*sums, device=device)
+    auc = eer = None
+    if val_auc and kept_probs:
+        from ..metrics import binary_roc, gather_scores, ovr_auc
+
+        probs, truth = gather_scores(torch.cat(kept_probs), torch.cat(kept_targets))
+        if probs.shape[1] == 2:
+            roc = binary_roc(probs[:, 1], truth, strict=False)
+            auc, eer = roc.auc, roc.eer
+        else:
+            auc = ovr_auc(probs, truth, probs.shape[1], strict=False)
     return EvalResult(acc=n_correct / max(1, n_total), total=int(n_total), correct=int(n_correct),
-                      loss=s_loss[0] / max(1, n_total) if s_loss else None)
+                      loss=s_loss[0] / max(1, n_total) if s_loss else None, auc=auc, eer=eer)
 
 
 def train_one_epoch(model: nn.Module, dl: DataLoader, opt: optim.Optimizer, scaler, criterion: nn.Module, device: str, *,
@@ -466,6 +515,11 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
     blur_settings()         # and a bad training.blur_p / blur_sigma_min / blur_sigma_max
     policy_settings()       # a bad training.rand_augment_* / trivial_augment is a ValueError here, not a class-count message below
     clip_cfg = clip_settings()      # and so is a bad training.clip_grad / clip_mode
+    metric_cfg = metric_settings()  # and a bad training.select_metric
+    if metric_cfg.val_auc and not use_cuda:
+        console.print("[bold yellow]training.val_auc / select_metric: auc ignored[/]: the AUC kernels need a CUDA device; accuracy is followed")
+        metric_cfg = MetricSettings(val_auc=False, select="acc")
+    val_auc, metric = metric_cfg.val_auc, metric_cfg.select
     try:
         # $GPU_INPUT_TAIL (YAML training.gpu_input_tail): loaders ship uint8 batches, the device does
         # flip / to-float / normalise / erasing
@@ -526,9 +580,10 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
             log_throughput(env, chief, world, phase="warmup", epoch=0, model=model_name, batch_size=batch_size, **done.stats)
             if reducer is not None:
                 reducer.detach()
-            res = evaluate(model, val_dl, device, val_tail, eval_criterion)
-            best_val_acc, best_epoch, warmup_done = res.acc, 0, True
-            console.print("[bold cyan]warmup[/] | " + spec.warmup_line.format(res=res) + clip_suffix(done.clip))
+            res = evaluate(model, val_dl, device, val_tail, eval_criterion, val_auc=val_auc)
+            value = selection_value(res, metric)
+            best_val_acc, best_epoch, warmup_done = best_val_acc if value is None else value, 0, True
+            console.print("[bold cyan]warmup[/] | " + spec.warmup_line.format(res=res) + clip_suffix(done.clip) + auc_suffix(res))
             if getattr(warm_opt, "arena", None) is not None:
                 warm_opt.zero_grad()
                 warm_opt.arena.release()
@@ -559,6 +614,11 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
             best_epoch = int(resume_state.get("best_epoch", best_epoch))
             warmup_done = bool(resume_state.get("warmup_done", warmup_done))
             epochs_no_improve = max(0, start_epoch - best_epoch)
+            saved_metric = str(resume_state.get("select_metric", "acc"))
+            if saved_metric != metric:
+                console.print(f"[bold yellow]Resume[/]: the checkpoint's best value follows {saved_metric}, this run follows {metric}; "
+                              "the best value starts over")
+                best_val_acc, epochs_no_improve = -1.0, 0
             console.print(f"[bold green]Resumed[/] from epoch {start_epoch} using {env.resume_checkpoint}")
 
         for epoch in range(start_epoch + 1, epochs + 1):
@@ -571,17 +631,18 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
             log_throughput(env, chief, world, phase="fine-tune", epoch=epoch, model=model_name,
                            batch_size=ft_dl.batch_size, accum_steps=accum, **done.stats)
             scheduler.step()
-            res = evaluate(model, val_dl, device, val_tail, eval_criterion)
+            res = evaluate(model, val_dl, device, val_tail, eval_criterion, val_auc=val_auc)
             console.print(f"[bold cyan]epoch {epoch}[/] | "
                           + spec.epoch_line.format(res=res, train_loss=done.loss, lr=scheduler.get_last_lr()[0])
-                          + clip_suffix(done.clip))
-            acc = res.acc
+                          + clip_suffix(done.clip) + auc_suffix(res))
+            acc = selection_value(res, metric)
             if ema is not None:
-                res_ema = evaluate(ema.module, val_dl, device, val_tail, eval_criterion)
-                console.print(f"[bold cyan]epoch {epoch} EMA[/] | " + spec.ema_line.format(res=res_ema) + f" | updates={ema.updates}")
+                res_ema = evaluate(ema.module, val_dl, device, val_tail, eval_criterion, val_auc=val_auc)
+                console.print(f"[bold cyan]epoch {epoch} EMA[/] | " + spec.ema_line.format(res=res_ema) + f" | updates={ema.updates}"
+                              + auc_suffix(res_ema))
                 if ema_cfg.select:
-                    acc = res_ema.acc
-            improved = acc > best_val_acc + 1e-4
+                    acc = selection_value(res_ema, metric)
+            improved = improves(acc, best_val_acc)
             if improved:
                 best_val_acc, best_epoch, epochs_no_improve = acc, epoch, 0
             else:
@@ -589,14 +650,15 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
             if chief:
                 state = save_latest_checkpoint(env, model=model, optimizer=opt, scheduler=scheduler, epoch=epoch,
                                                best_val_acc=best_val_acc, best_epoch=best_epoch,
-                                               extra={"warmup_done": warmup_done, **ema_checkpoint_extra(ema)})
+                                               extra={"warmup_done": warmup_done, **ema_checkpoint_extra(ema),
+                                                      **({"select_metric": metric} if metric != "acc" else {})})
                 if improved:
                     save_best_checkpoint(env, state, weights_key="model_ema" if ema is not None and ema_cfg.select else "model")
-                    console.print(f"[bold green]new best[/] val_acc={best_val_acc:.4f} (epoch {best_epoch}) → saved "
+                    console.print(f"[bold green]new best[/] val_{metric}={best_val_acc:.4f} (epoch {best_epoch}) → saved "
                                   f"{env.best_weights_path.name}")
             if spec.early_stop and not improved and epochs_no_improve >= patience:
                 console.print(f"[bold yellow]Early stopping[/]: no improvement for {patience} epoch(s). "
-                              f"Best at epoch {best_epoch} with val_acc={best_val_acc:.4f}.")
+                              f"Best at epoch {best_epoch} with val_{metric}={best_val_acc:.4f}.")
                 break
 
     console.print(f"[bold green]Best weights saved →[/] {env.best_weights_path.resolve()}")

@@ -91,7 +91,8 @@ typedef void* dfd_stream;          /* a hipStream_t */
  * 143 = dfd_tune keeps keys 0, 4 and 8-11; keys 1-3, 5-7, 12 and 13 (A/B-only sizes and the timing-only ablation mask) are DFD_EINVAL;
  * 144 = dfd_blur_u8 (Gaussian-blur augmentation: Pillow's three box passes along x and three along y, byte-exact);
  * 145 = dfd_softmax_argmax returns index 0 for a row that holds a NaN or an infinity (it returned 0x7fffffff), dfd_ce_loss with
- * label_smoothing 0 keeps a finite loss beside a -inf logit off the target (it returned NaN); finite inputs give the same bits. */
+ * label_smoothing 0 keeps a finite loss beside a -inf logit off the target (it returned NaN); finite inputs give the same bits;
+ * 146 = dfd_roc_curve / dfd_roc_ws, dfd_roc_sweep, dfd_confusion (exact ROC curve, rank statistic, threshold sweep and confusion matrix). */
 int dfd_version(void);
 
 /* Planner knobs: the tier switches and grid sizes by which tests and per-layer scripts reach a kernel tier.  Process-wide plain ints:
@@ -512,6 +513,47 @@ size_t dfd_jpeg_ws(int N, int H, int W);
 #define DFD_BLUR_MAX_RADIUS 32
 #define DFD_BLUR_MAX_PIXELS (78 * 1024)
 int dfd_blur_u8(const unsigned char* src, const int* jobs_dev, unsigned char* out, int N, int H, int W, dfd_stream stream);
+
+/* Evaluation metrics on the device, exact (csrc/dfd_metrics.hip; tests/_metrics_ref.py restates them in numpy and Python integers).
+ * All three are integer counting: the results do not depend on the order in which workgroups run, no workgroup waits for another
+ * (dependent work is a later launch on the same stream), and the only atomics are integer adds.
+ *
+ * dfd_roc_curve: `score` = n f32 scores sorted ASCENDING (NaN last, as torch.sort leaves them) and `label` their int64 labels in the
+ * same order; a sample is a positive when its label == `positive`, a negative otherwise.  A tie group is a maximal run with
+ * score[i] == score[i + 1] under float comparison (-0.0 and +0.0 are one group, every NaN is a group of its own); the order inside a
+ * group does not matter.  Outputs, with G the number of groups:
+ *   thr[g]                   the score of group g (of its last member: the sign of a zero group is that member's), g < G
+ *   cum_pos[g], cum_neg[g]   positives / negatives in groups 0..g inclusive; entries g >= G of the three arrays are NOT written
+ *   stats[DFD_ROC_STATS_LEN] = {P, N, G, nonfinite (scores that are NaN or +-inf), two_u}
+ *   two_u = sum_g p_g * (cum_neg[g - 1] + cum_neg[g]), p_g the positives of group g: twice the Mann-Whitney U with ties counted
+ *   half, so AUC = two_u / (2 P N) exactly (the caller divides once).
+ * ws: dfd_roc_ws(n) bytes of scratch (int32 tile totals), no initial contents required.  n == 0 is valid and leaves zeros in stats;
+ * n > DFD_ROC_MAX_N (two_u stays below 2^56), a negative n or a NULL pointer: DFD_EINVAL (dfd_roc_ws: 0); a small ws: DFD_EWORKSPACE.
+ * Four launches: per-tile sums (DFD_ROC_TILE scores per workgroup), one workgroup of DFD_ROC_SCAN_WIDTH threads that scans the tile
+ * totals (looping when there are more tiles than threads), the tile pass that writes the compacted arrays, the pass over the groups.
+ *
+ * dfd_roc_sweep: for each of T <= DFD_ROC_MAX_CUTS ascending f64 cut points, tp[k] = #{positive, score >= cuts[k]} and fp[k] likewise
+ * for the negatives, the comparison in f64 (the promotion numpy applies to float32 scores against a float64 cut: rounding the cut to
+ * f32 moves it across scores).  One thread per cut, a binary search in thr[0..G); G, P and N are read from `stats` on the device (G
+ * clamped to `cap`, the arrays' length), so no host synchronisation separates it from dfd_roc_curve.  Scores must be free of NaN.
+ *
+ * dfd_confusion: counts[J][J] (int64, row = truth, column = prediction) over n int64 label pairs; a pair with either label outside
+ * [0, J) is left out of the matrix and counted in *oob.  Both outputs are zeroed first.  J <= DFD_CONFUSION_LDS_MAX_J: an int32
+ * histogram per workgroup in LDS (J * J * 4 bytes, at most 64 KiB), flushed with 64-bit integer adds; above, up to
+ * DFD_CONFUSION_MAX_J: one 64-bit integer add per sample.  J outside 1..DFD_CONFUSION_MAX_J, n < 0 or a NULL pointer: DFD_EINVAL. */
+#define DFD_ROC_TILE 2048
+#define DFD_ROC_SCAN_WIDTH 1024
+#define DFD_ROC_MAX_N (1 << 28)
+#define DFD_ROC_MAX_CUTS 4096
+#define DFD_ROC_STATS_LEN 5
+#define DFD_CONFUSION_LDS_MAX_J 128
+#define DFD_CONFUSION_MAX_J 1024
+size_t dfd_roc_ws(int n);
+int dfd_roc_curve(const float* score, const int64_t* label, int n, int64_t positive, void* ws, size_t ws_bytes, float* thr,
+                  int64_t* cum_pos, int64_t* cum_neg, int64_t* stats, dfd_stream stream);
+int dfd_roc_sweep(const float* thr, const int64_t* cum_pos, const int64_t* cum_neg, const int64_t* stats, int cap, const double* cuts,
+                  int T, int64_t* tp, int64_t* fp, dfd_stream stream);
+int dfd_confusion(const int64_t* truth, const int64_t* pred, int n, int J, int64_t* counts, int64_t* oob, dfd_stream stream);
 
 /* Input tail on the device (trainers/efficientnet.py:111-234): a uint8 NHWC
  * batch [N][H][W][3] -> RandomHorizontalFlip -> ToTensor (/255) -> Normalize((x-mean)/std) ->
