@@ -18,8 +18,9 @@ import torch
 from torch import nn
 
 from ._lib import ACT_RELU
-from .fastervit_functions import (AttnSpec, ConvBlockCtx, ConvBlockFunction, FVDownsampleFunction, HATCtx, HATFunction,
-                                  TokenInitFunction, derived_weights)
+from .fastervit_functions import (AttnSub, ConvBlockCtx, ConvBlockFunction, FVDownsampleFunction, HATCtx, HATFunction, MlpSub, Stream,
+                                  Table, TokenInitFunction, derived_weights, hat_inputs, lin_layer)
+from .functions import Layer
 from .network import HipNetwork, _bnref, compute_dtype
 from .vit_functions import ConvStemCtx, ConvStemFunction, DenseConvBNFunction, DenseConvCtx, TailCtx, TailFunction
 
@@ -80,13 +81,10 @@ class WindowAttention(nn.Module):
         self.proj = nn.Linear(dim, dim)
         self.pos_emb_funct = PosEmbMLPSwinv2D(resolution, heads, seq_length)
 
-    def spec(self) -> AttnSpec:
-        n_local = self.resolution ** 2
-        return AttnSpec(self.heads, n_local, self.seq_length - n_local, self.pos_emb_funct._coords2d, self.pos_emb_funct._idx32)
-
-    def tensors(self, norm: nn.LayerNorm):
-        """The attention sub-block's own tensors; the relative-position bias (pos_emb_funct) comes from coord_tables."""
-        return (norm.weight, norm.bias, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias)
+    def record(self, norm: nn.LayerNorm, bias, gamma) -> AttnSub:
+        """The attention sub-block behind `norm`; bias: its relative-position bias (pos_emb_funct) from coord_tables."""
+        return AttnSub(Layer(None, None, norm.weight, norm.bias), lin_layer(self.qkv.weight, self.qkv.bias),
+                       lin_layer(self.proj.weight, self.proj.bias, gamma), Table(bias))
 
 
 class Mlp(nn.Module):
@@ -95,8 +93,9 @@ class Mlp(nn.Module):
         self.fc1 = nn.Linear(dim, hidden)
         self.fc2 = nn.Linear(hidden, dim)
 
-    def tensors(self, norm: nn.LayerNorm):
-        return norm.weight, norm.bias, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias
+    def record(self, norm: nn.LayerNorm, gamma) -> MlpSub:
+        return MlpSub(Layer(None, None, norm.weight, norm.bias), lin_layer(self.fc1.weight, self.fc1.bias),
+                      lin_layer(self.fc2.weight, self.fc2.bias, gamma))
 
 
 class HipHAT(nn.Module):
@@ -128,8 +127,8 @@ class HipHAT(nn.Module):
         from .fastervit_functions import CoordJob
 
         def cpb(att: WindowAttention) -> CoordJob:
-            sp = att.spec()
-            return CoordJob("cpb", sp.coords2d, sp.idx, sp.n_local, sp.n_global)
+            n_local = att.resolution ** 2           # tokens of the window grid (49, or 16 for the carrier grid); the rest: carrier tokens
+            return CoordJob("cpb", att.pos_emb_funct._coords2d, att.pos_emb_funct._idx32, n_local, att.seq_length - n_local)
 
         jobs = [CoordJob("pos", self.pos_embed._coords), cpb(self.attn)]
         params = [*self.pos_embed.tensors(), *self.attn.pos_emb_funct.tensors()]
@@ -152,16 +151,11 @@ class HipHAT(nn.Module):
             rs_win = rng.drop_path_scale(x.shape[0], keep, stream_id=4 * self.index)
             if carrier:
                 rs_ct = rng.drop_path_scale(ct.shape[0], keep, stream_id=4 * self.index + 1)
-        flat = [tables[0], *self.attn.tensors(self.norm1), tables[1], *self.mlp.tensors(self.norm2)]
-        if carrier:
-            flat += [tables[2], *self.hat_attn.tensors(self.hat_norm1), tables[3], *self.hat_mlp.tensors(self.hat_norm2)]
-        flat += [self.gamma3, self.gamma4]
-        if carrier:
-            flat += [self.gamma1, self.gamma2]
-        flat += [rs_win, rs_ct]
-        cfg = HATCtx(self.attn.heads, carrier, self.attn.spec(), self.hat_attn.spec() if carrier else None, self.pos_embed._coords,
-                     self.hat_pos_embed._coords if carrier else None, *(maps if carrier else (None, None, None)), self.training)
-        return HATFunction.apply(x, ct, cfg, *flat)
+        win = Stream(Table(tables[0]), self.attn.record(self.norm1, tables[1], self.gamma3), self.mlp.record(self.norm2, self.gamma4))
+        car = Stream(Table(tables[2]), self.hat_attn.record(self.hat_norm1, tables[3], self.gamma1),
+                     self.hat_mlp.record(self.hat_norm2, self.gamma2)) if carrier else None
+        cfg = HATCtx(self.attn.heads, carrier, *(maps if carrier else (None, None, None)))
+        return HATFunction.apply(x, ct, cfg, *hat_inputs(win, car, rs_win, rs_ct))
 
 
 class HipConvBlock(nn.Module):

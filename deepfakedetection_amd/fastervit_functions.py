@@ -11,7 +11,12 @@ Dense 3x3 convolutions run as im2col + the MFMA GEMM kernels; Linear layers run 
 bias (and LayerScale, residual, DropPath scale) applied by the BatchNorm-apply pass under an identity statistic
 (mean 0, variance 1, eps 0), so `Linear + bias` needs no kernel of its own and its bias gradient is the BN-beta
 gradient.  Window bookkeeping (partition, carrier-token concatenation and split) is `dfd_copy_rows` with index
-maps built once per batch size.  Reference call sites: trainers/fastervit.py:271 (train), :235 (evaluate),
+maps built once per batch size.
+
+Every stage follows the plumbing of functions.py: its tensor inputs are cut into records, `Layer` for a convolution or Linear
+layer (cut_layers; lin_layer) or a LayerNorm, and for the HAT block also the records below (`Table`, `AttnSub`, `MlpSub`, `Stream`, cut by
+cut_hat in the order hat_slots states once); tensors reach the backward through ctx.save_for_backward only, the records are
+rebuilt there and never kept on ctx; gradients come back through Layer.grads() / hat_grads().  Reference call sites: trainers/fastervit.py:271 (train), :235 (evaluate),
 orchestration/orchestrator.py:529,590; arithmetic per fastervit 1.0.0 faster_vit.py (restated in
 oracle/fastervit_ref.py).
 """
@@ -21,6 +26,7 @@ from __future__ import annotations
 import contextlib
 import threading
 from dataclasses import dataclass
+from itertools import islice
 
 import torch
 
@@ -133,15 +139,7 @@ class CoordTablesFunction(torch.autograd.Function):
                 dtab = torch.empty((T, D), dtype=torch.float32, device=dev)
                 rp.append((raw[i], job.idx, g, dtab, job.n_local, job.n_global))
                 g = dtab
-            dw0 = (_slot(w0, True, tuple(w0.shape)) if nw0 else None)
-            db0 = (_slot(b0, True, tuple(b0.shape)) if nb0 else None)
-            dw2 = (_slot(w2, True, tuple(w2.shape)) if nw2 else None)
-            if nw0 and dw0 is None:
-                dw0 = torch.empty_like(w0)
-            if nb0 and db0 is None:
-                db0 = torch.empty_like(b0)
-            if nw2 and dw2 is None:
-                dw2 = torch.empty_like(w2)
+            dw0, db0, dw2 = _place(None, w0, nw0), _place(None, b0, nb0), _place(None, w2, nw2)
             grads[3 * i], grads[3 * i + 1], grads[3 * i + 2] = dw0, db0, dw2
             cj.append((job.coords, w0, b0, w2, g, dw0, db0, dw2))
         K.coord_tables_bwd(rp, cj)
@@ -168,15 +166,6 @@ def derived_weights(table: dict | None):
         yield
     finally:
         _derived_tls.table = prev
-
-
-@dataclass
-class AttnSpec:
-    heads: int
-    n_local: int            # tokens of the window grid (49, or 16 for the carrier grid)
-    n_global: int           # carrier tokens in front (4 in level 2's window attention, else 0)
-    coords2d: torch.Tensor  # [(2w-1)^2, 2] f32 log-spaced relative coordinates
-    idx: torch.Tensor       # int32 [n_local^2] relative position index
 
 
 def window_attention_fwd(qkv, bias, H: int):
@@ -227,234 +216,267 @@ def window_attention_bwd(qkv, dO, saved, bias, H: int, need_bias: bool):
     return dqkv, dfull
 
 
-def attn_sub_fwd(x, P, spec: AttnSpec, ls, row_scale):
-    """x + [rs *] [ls *] proj(softmax(q k^T * scale + bias) v) with q, k, v = qkv(LN(x)).
-    P: dict of tensors (ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b, bias); bias = the [H, T, T] relative-position bias of
-    CoordTablesFunction."""
-    H = spec.heads
-    dt = x.dtype
-    derived = getattr(_derived_tls, "table", None)
-    xn, lnst = K.layernorm_fwd(x, P["ln_w"], P["ln_b"], 1e-5)
-    wq_nk, wq_kn = _prep(P["qkv_w"], dt, derived)
-    qkv, yq, stq = lin_fwd(xn, wq_nk, lin_layer(P["qkv_w"], P["qkv_b"]))
-    bias_full = P["bias"]
-    O, Pm = window_attention_fwd(qkv, bias_full, H)
-    wp_nk, wp_kn = _prep(P["proj_w"], dt, derived)
-    out, yp, stp = lin_fwd(O, wp_nk, lin_layer(P["proj_w"], P["proj_b"], ls), ACT_NONE, x, row_scale)
-    return out, (x, xn, lnst, qkv, yq, stq, Pm, O, yp, stp, wq_kn, wp_kn, bias_full)
+# =========================================================================== records of the HAT block
+# Like functions.Layer: tensors, one need flag per tensor (need_<field>) and the gradient the backward produced (d<field>); built
+# afresh from the arguments in `forward` and from ctx.saved_tensors in `backward`.  A LayerNorm is a Layer of gamma and beta alone.
+@dataclass
+class Table:
+    """An output of CoordTablesFunction: a position table [T, C] or a relative-position attention bias [H, T, T]."""
+
+    tab: torch.Tensor | None = None
+    need_tab: bool = False
+    dtab: torch.Tensor | None = None
 
 
-def attn_sub_bwd(g, saved, P, spec: AttnSpec, ls, row_scale, need: dict, need_dx: bool):
-    """-> (dx, grads dict).  need: name -> bool for the entries of P and 'ls'."""
-    x, xn, lnst, qkv, yq, stq, Pm, O, yp, stp, wq_kn, wp_kn, bias_full = saved
-    T = x.shape[1]
-    H = spec.heads
-    grads = {}
-    upstream = need_dx or any(need[k] for k in ("ln_w", "ln_b", "qkv_w", "qkv_b", "bias"))
-    proj = lin_layer(P["proj_w"], P["proj_b"], ls, need["proj_w"], need["proj_b"], need["ls"])
-    dO = lin_bwd(g, O, yp, stp, wp_kn, proj, ACT_NONE, upstream, None, row_scale)
-    grads["proj_w"], grads["proj_b"], grads["ls"] = proj.dw, proj.dbeta, proj.dls
-    if not upstream:
-        return None, grads
-    need_cpb = need["bias"]
-    dqkv, dfull = window_attention_bwd(qkv, dO, Pm, bias_full, H, need_cpb)
-    if need_cpb:
-        grads["bias"] = dfull.view(H, T, T)
-    need_xn = need_dx or need["ln_w"] or need["ln_b"]
-    qkv_l = lin_layer(P["qkv_w"], P["qkv_b"], None, need["qkv_w"], need["qkv_b"])
-    dxn = lin_bwd(dqkv, xn, yq, stq, wq_kn, qkv_l, ACT_NONE, need_xn)
-    grads["qkv_w"], grads["qkv_b"] = qkv_l.dw, qkv_l.dbeta
-    dx = None
-    if need_xn:
-        dx, grads["ln_w"], grads["ln_b"] = _ln_bwd(dxn, x, P["ln_w"], P["ln_b"], lnst, need["ln_w"], need["ln_b"],
-                                                   g if need_dx else None)
-        if not need_dx:
-            dx = None
-    return dx, grads
+@dataclass
+class AttnSub:
+    ln: Layer
+    qkv: Layer
+    proj: Layer             # proj.ls: the sub-block's LayerScale (gamma3, or gamma1 on the carrier tokens), None without one
+    bias: Table
 
 
-def _ln_bwd(dxn, x, ln_w, ln_b, lnst, need_w: bool, need_b: bool, residual=None):
-    """LayerNorm backward with the skip connection's gradient added in the same kernel; (dgamma, dbeta) are summed straight
-    into the parameters' gradient-arena slots when both are wanted and the slots are adjacent (weight, bias: they are)."""
-    C = ln_w.numel()
-    sw = _slot(ln_w, need_w, (C,)) if need_w else None
-    sb = _slot(ln_b, need_b, (C,)) if need_b else None
-    if sw is not None and sb is not None and sb.data_ptr() == sw.data_ptr() + 4 * C:
-        both = torch.as_strided(sw, (2, C), (C, 1))
-        dx, dg, db = K.layernorm_bwd(dxn, x, ln_w, lnst, residual, both)
-        return dx, dg, db
-    dx, dg, db = K.layernorm_bwd(dxn, x, ln_w, lnst, residual)
-
-    def place(val, slot, need):
-        if not need:
-            return None
-        if slot is None:
-            return val
-        return K.axpby(val.reshape(-1), None, 1.0, 0.0, out=slot.view(-1)).view(slot.shape)
-
-    return dx, place(dg, sw, need_w), place(db, sb, need_b)
+@dataclass
+class MlpSub:
+    ln: Layer
+    fc1: Layer
+    fc2: Layer              # fc2.ls: gamma4 / gamma2
 
 
-def _to_slot(val: torch.Tensor, param: torch.Tensor, need: bool):
-    """Move a freshly computed f32 gradient into the parameter's arena slot when it has one."""
+@dataclass
+class Stream:
+    """What one token stream of the block goes through: position table, attention sub-block, MLP sub-block.  A block has the
+    window stream and, with carrier tokens, the carrier stream in front of it."""
+
+    pos: Table
+    attn: AttnSub
+    mlp: MlpSub
+
+
+def _stream_slots(s: Stream):
+    """(record, field) of the stream's tensor inputs in input order, and of its two LayerScales, which come behind both streams."""
+    a, m = s.attn, s.mlp
+    return ([(s.pos, "tab"), (a.ln, "gamma"), (a.ln, "beta"), (a.qkv, "w"), (a.qkv, "beta"), (a.proj, "w"), (a.proj, "beta"), (a.bias, "tab"),
+             (m.ln, "gamma"), (m.ln, "beta"), (m.fc1, "w"), (m.fc1, "beta"), (m.fc2, "w"), (m.fc2, "beta")],
+            [(a.proj, "ls"), (m.fc2, "ls")])
+
+
+def hat_slots(win: Stream, car: Stream | None) -> list:
+    """(record, field) of every tensor input of HATFunction behind (x, ct, cfg) and in front of the two DropPath row scales: the
+    window stream, the carrier stream, gamma3, gamma4, gamma1, gamma2.  The one statement of that order: hat_inputs, cut_hat and
+    hat_grads all walk it."""
+    streams = [_stream_slots(s) for s in (win, car) if s is not None]
+    return [slot for main, _ in streams for slot in main] + [slot for _, scales in streams for slot in scales]
+
+
+def hat_inputs(win: Stream, car: Stream | None, rs_win=None, rs_ct=None) -> list:
+    """HATFunction's tensor inputs behind (x, ct, cfg): the tensors of the records, then the two DropPath row scales."""
+    return [getattr(r, f) for r, f in hat_slots(win, car)] + [rs_win, rs_ct]
+
+
+def cut_hat(t, need, carrier: bool):
+    """(window stream, carrier stream or None, (rs_win, rs_ct)) from HATFunction's tensor inputs `t` behind (x, ct, cfg).
+    need: the slice of ctx.needs_input_grad that lines up with t (None in a forward: every flag False)."""
+    def blank():
+        ln1, qkv, proj, ln2, fc1, fc2 = (Layer(None, None, None, None) for _ in range(6))
+        return Stream(Table(), AttnSub(ln1, qkv, proj, Table()), MlpSub(ln2, fc1, fc2))
+
+    win, car = blank(), blank() if carrier else None
+    slots = hat_slots(win, car)
+    for i, (r, f) in enumerate(slots):
+        setattr(r, f, t[i])
+        if need is not None and need[i] and t[i] is not None:
+            setattr(r, "need_" + f, True)
+    for L in [L for s in (win, car) if s is not None for L in (s.attn.qkv, s.attn.proj, s.mlp.fc1, s.mlp.fc2)]:
+        L.gamma, L.bn = ident(L.w.device, L.w.shape[0])           # see lin_layer
+    return win, car, tuple(t[len(slots):])
+
+
+def hat_grads(win: Stream, car: Stream | None) -> list:
+    """One gradient per tensor input of hat_inputs, in its order: those on the records, each masked by its own flag, and none for
+    the row scales."""
+    return [getattr(r, "d" + f) if getattr(r, "need_" + f) else None for r, f in hat_slots(win, car)] + [None, None]
+
+
+def _place(val, param, need: bool, slot=None):
+    """Where a wanted f32 gradient of `param` lives: its gradient-arena slot if the parameter has a free one (slot: that slot, where
+    the caller has claimed it already), else a tensor of its own.  val: the freshly computed gradient, moved into the slot by one
+    launch or handed back as it is; None: the buffer itself, for the caller's kernel to write."""
     if not need:
         return None
-    slot = _slot(param, True, tuple(param.shape))
+    if slot is None:
+        slot = _slot(param, True, tuple(param.shape))
+    if val is None:
+        return slot if slot is not None else torch.empty_like(param)
     if slot is None:
         return val.view(param.shape)
     return K.axpby(val.reshape(-1), None, 1.0, 0.0, out=slot.view(-1)).view(param.shape)
 
 
-def mlp_sub_fwd(x, P, ls, row_scale):
-    """x + [rs *] [ls *] fc2(GELU(fc1(LN(x)))).  P: ln_w, ln_b, fc1_w, fc1_b, fc2_w, fc2_b."""
+def _ln_bwd(dxn, x, ln: Layer, lnst, residual=None):
+    """LayerNorm backward with the skip connection's gradient added in the same kernel -> dx; (dgamma, dbeta) land on ln, summed
+    straight into the parameters' gradient-arena slots when both are wanted and the slots are adjacent (weight, bias: they are)."""
+    C = ln.gamma.numel()
+    sw = _slot(ln.gamma, ln.need_gamma, (C,))
+    sb = _slot(ln.beta, ln.need_beta, (C,))
+    if sw is not None and sb is not None and sb.data_ptr() == sw.data_ptr() + 4 * C:
+        dx, ln.dgamma, ln.dbeta = K.layernorm_bwd(dxn, x, ln.gamma, lnst, residual, torch.as_strided(sw, (2, C), (C, 1)))
+        return dx
+    dx, dg, db = K.layernorm_bwd(dxn, x, ln.gamma, lnst, residual)
+    ln.dgamma, ln.dbeta = _place(dg, ln.gamma, ln.need_gamma, sw), _place(db, ln.beta, ln.need_beta, sb)
+    return dx
+
+
+N_ATTN_SAVED, N_MLP_SAVED = 12, 10          # tensors attn_sub_fwd / mlp_sub_fwd keep for their backward
+
+
+def attn_sub_fwd(x, A: AttnSub, heads: int, row_scale):
+    """x + [rs *] [ls *] proj(softmax(q k^T * scale + bias) v) with q, k, v = qkv(LN(x)) -> (out, saved)."""
     dt = x.dtype
     derived = getattr(_derived_tls, "table", None)
-    xn, lnst = K.layernorm_fwd(x, P["ln_w"], P["ln_b"], 1e-5)
-    w1_nk, w1_kn = _prep(P["fc1_w"], dt, derived)
-    hid = P["fc1_w"].shape[0]
-    ones, ref = ident(x.device, hid)
-    st1 = _bn_state(None, 0, _rows(xn), ref, ones, P["fc1_b"], False)
-    w2_nk, w2_kn = _prep(P["fc2_w"], dt, derived)
-    C = P["fc2_w"].shape[0]
-    ones2, ref2 = ident(x.device, C)
-    st2 = _bn_state(None, 0, _rows(xn), ref2, ones2, P["fc2_b"], False, None, None, ls)
+    xn, lnst = K.layernorm_fwd(x, A.ln.gamma, A.ln.beta, 1e-5)
+    wq_nk, wq_kn = _prep(A.qkv.w, dt, derived)
+    qkv, yq, stq = lin_fwd(xn, wq_nk, A.qkv)
+    O, Pm = window_attention_fwd(qkv, A.bias.tab, heads)
+    wp_nk, wp_kn = _prep(A.proj.w, dt, derived)
+    out, yp, stp = lin_fwd(O, wp_nk, A.proj, ACT_NONE, x, row_scale)
+    return out, (x, xn, lnst, qkv, yq, stq, Pm, O, yp, stp, wq_kn, wp_kn)
+
+
+def attn_sub_bwd(g, saved, A: AttnSub, heads: int, row_scale, need_dx: bool):
+    """-> dx (None unless need_dx); the parameter and bias gradients land on A's records."""
+    x, xn, lnst, qkv, yq, stq, Pm, O, yp, stp, wq_kn, wp_kn = saved
+    T = x.shape[1]
+    need_xn = need_dx or A.ln.need_bn
+    upstream = need_xn or A.qkv.need_w or A.qkv.need_beta or A.bias.need_tab
+    dO = lin_bwd(g, O, yp, stp, wp_kn, A.proj, ACT_NONE, upstream, None, row_scale)
+    if not upstream:
+        return None
+    dqkv, dfull = window_attention_bwd(qkv, dO, Pm, A.bias.tab, heads, A.bias.need_tab)
+    if A.bias.need_tab:
+        A.bias.dtab = dfull.view(heads, T, T)
+    dxn = lin_bwd(dqkv, xn, yq, stq, wq_kn, A.qkv, ACT_NONE, need_xn)
+    if not need_xn:
+        return None
+    dx = _ln_bwd(dxn, x, A.ln, lnst, g if need_dx else None)
+    return dx if need_dx else None
+
+
+def _lin_apply(x, w_nk, st, act, residual=None, row_scale=None, want_raw=True):
+    """act(x w^T + bias) [* ls] [* rs] [+ residual] under the coefficient block `st` -> (out, raw product or None): one kernel where
+    the shape is dfd_gemm's, else the product and one apply pass."""
+    fused = K.gemm_bias_act(x, w_nk, st, act, residual, row_scale, want_raw=want_raw)
+    if fused is not None:
+        return fused
+    y, _, _ = K.pwconv(x, None, w_nk, None, stats=False)
+    return K.bn_act_apply(y, st, act, residual, row_scale), y
+
+
+def mlp_sub_fwd(x, M: MlpSub, row_scale):
+    """x + [rs *] [ls *] fc2(GELU(fc1(LN(x)))) -> (out, saved).
+    Not two lin_fwd calls: both layers' derived weights and coefficient blocks are made before the first product, and a block
+    used on its own launches each of them, so going through lin_fwd (state, then product, per layer) would reorder launches."""
+    dt = x.dtype
+    derived = getattr(_derived_tls, "table", None)
+    fc1, fc2 = M.fc1, M.fc2
+    xn, lnst = K.layernorm_fwd(x, M.ln.gamma, M.ln.beta, 1e-5)
+    w1_nk, w1_kn = _prep(fc1.w, dt, derived)
+    st1 = _bn_state(None, 0, _rows(xn), fc1.bn, fc1.gamma, fc1.beta, False)
+    w2_nk, w2_kn = _prep(fc2.w, dt, derived)
+    st2 = _bn_state(None, 0, _rows(xn), fc2.bn, fc2.gamma, fc2.beta, False, None, None, fc2.ls)
     # fc1 + bias + GELU and fc2 + bias (+ LayerScale, DropPath row scale, skip connection) are one kernel each where the shape
     # is dfd_gemm's (the activated hidden tensor `a` and the pre-activation `h` both leave fc1's epilogue: `h` for GELU');
     # otherwise the activated tensor is materialised by one pass — as a GEMM prologue the GELU was evaluated once per
     # 128-column output tile by fc2's forward and again by its weight gradient
-    f1 = K.gemm_bias_act(xn, w1_nk, st1, ACT_GELU, None, None, want_raw=True)
-    if f1 is not None:
-        a, h = f1
-    else:
-        h, _, _ = K.pwconv(xn, None, w1_nk, None, stats=False)
-        a = K.bn_act_apply(h, st1, ACT_GELU)
-    f2 = K.gemm_bias_act(a, w2_nk, st2, ACT_NONE, x, row_scale, want_raw=ls is not None)
-    if f2 is not None:
-        out, y2 = f2                                        # y2 None without LayerScale: the backward never reads it (and `out`
-                                                            # must not stand in: a Function must not save its own output)
-    else:
-        y2, _, _ = K.pwconv(a, None, w2_nk, None, stats=False)
-        out = K.bn_act_apply(y2, st2, ACT_NONE, x, row_scale)
+    a, h = _lin_apply(xn, w1_nk, st1, ACT_GELU)
+    # y2 is None from the one-kernel form without LayerScale: the backward never reads it (and `out` must not stand in: a
+    # Function must not save its own output)
+    out, y2 = _lin_apply(a, w2_nk, st2, ACT_NONE, x, row_scale, want_raw=fc2.ls is not None)
     return out, (x, xn, lnst, h, a, st1, y2, st2, w1_kn, w2_kn)
 
 
-def mlp_sub_bwd(g, saved, P, ls, row_scale, need: dict, need_dx: bool):
+def mlp_sub_bwd(g, saved, M: MlpSub, row_scale, need_dx: bool):
+    """-> dx (None unless need_dx); the parameter gradients land on M's records.  Its own launch sequence, not lin_bwd's: with
+    LayerScale fc2's mapped gradient dz2 is materialised once (affine2_apply) instead of being a GEMM prologue, and fc1's
+    bn_backward runs only when its bias gradient is wanted (dz1 needs no coefficients under the identity statistic)."""
     x, xn, lnst, h, a, st1, y2, st2, w1_kn, w2_kn = saved
-    grads = {}
-    C, hid = P["fc2_w"].shape[0], P["fc1_w"].shape[0]
-    dev = x.device
+    ln, fc1, fc2 = M.ln, M.fc1, M.fc2
+    C, hid = fc2.w.shape[0], fc1.w.shape[0]
     gb = K.scale_rows(g, row_scale) if row_scale is not None else g
     # fc2 has no BatchNorm: the backward map of its identity statistic is dz = ls * g.  Without layer scale that is g itself and
     # the bias gradient is the column sums of g (one reduction launch, its final summation in the block's batch); with it the
     # BatchNorm-shaped pair runs and the scaled gradient is materialised once (as a GEMM prologue it was evaluated once per
     # 128-column tile of the data gradient — 8 times per element at hidden 1024 — and read y2 only to multiply it by zero)
-    if ls is None:
-        grads["fc2_b"] = K.bias_grad(gb, None, _slot(P["fc2_b"], True, (C,))) if need["fc2_b"] else None
-        grads["ls"] = None
+    if fc2.ls is None:
+        if fc2.need_beta:
+            fc2.dbeta = K.bias_grad(gb, None, _slot(fc2.beta, True, (C,)))
         dz2 = gb
     else:
         parts, n = K.bn_bwd_reduce(gb, y2, st2, None)
-        ones2, _ = ident(dev, C)
-        outs = (None, _slot(P["fc2_b"], need["fc2_b"], (C,)), _slot(ls, need["ls"], (C,)), None)
-        coef2, _, db2, dls, _ = K.bn_bwd_finalize(parts, n, _rows(y2), ones2, P["fc2_b"], ls, st2, False, need["fc2_b"] or True,
-                                                  need["ls"], False, outs)
-        grads["fc2_b"], grads["ls"] = (db2 if need["fc2_b"] else None), dls
-        dz2 = K.affine2_apply(gb, y2, coef2)
-    upstream = need_dx or any(need[k] for k in ("ln_w", "ln_b", "fc1_w", "fc1_b"))
-    if need["fc2_w"]:
-        grads["fc2_w"] = K.pwconv_wgrad(dz2, None, a, None, _slot(P["fc2_w"], True, (C, hid))).view(P["fc2_w"].shape)
-    if not upstream:
-        return None, grads
+        dz2 = K.affine2_apply(gb, y2, bn_backward(fc2, parts, n, _rows(y2), st2, False))
+    need_xn = need_dx or ln.need_bn
+    if fc2.need_w:
+        fc2.dw = K.pwconv_wgrad(dz2, None, a, None, _slot(fc2.w, True, (C, hid))).view(fc2.w.shape)
+    if not (need_xn or fc1.need_w or fc1.need_beta):
+        return None
     D, _, _ = K.pwconv(dz2, None, w2_kn, None, stats=False)
     dz1, parts, n = K.act_bn_bwd(D, h, None, None, st1, ACT_GELU)
-    if need["fc1_b"]:
-        fc1 = lin_layer(P["fc1_w"], P["fc1_b"], need_b=True)
+    if fc1.need_beta:
         bn_backward(fc1, parts, n, _rows(h), st1, False)
-        grads["fc1_b"] = fc1.dbeta
-    if need["fc1_w"]:
-        grads["fc1_w"] = K.pwconv_wgrad(dz1, None, xn, None, _slot(P["fc1_w"], True, (hid, C))).view(P["fc1_w"].shape)
-    dx = None
-    if need_dx or need["ln_w"] or need["ln_b"]:
-        dxn, _, _ = K.pwconv(dz1, None, w1_kn, None, stats=False)
-        dx, grads["ln_w"], grads["ln_b"] = _ln_bwd(dxn, x, P["ln_w"], P["ln_b"], lnst, need["ln_w"], need["ln_b"],
-                                                   g if need_dx else None)
-        if not need_dx:
-            dx = None
-    return dx, grads
+    if fc1.need_w:
+        fc1.dw = K.pwconv_wgrad(dz1, None, xn, None, _slot(fc1.w, True, (hid, C))).view(fc1.w.shape)
+    if not need_xn:
+        return None
+    dxn, _, _ = K.pwconv(dz1, None, w1_kn, None, stats=False)
+    dx = _ln_bwd(dxn, x, ln, lnst, g if need_dx else None)
+    return dx if need_dx else None
 
 
 # =========================================================================== HAT block
-_ATTN_KEYS = ("ln_w", "ln_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "bias")
-_MLP_KEYS = ("ln_w", "ln_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")
-_POS_KEYS = ("table",)
-
-
 @dataclass
 class HATCtx:
     heads: int
     carrier: bool                       # level 2: carrier-token stream + concatenation
-    win_spec: AttnSpec
-    ct_spec: AttnSpec | None
-    coords_win: torch.Tensor            # [49, 2] PosEmbMLPSwinv1D coordinates of the window grid
-    coords_ct: torch.Tensor | None      # [16, 2]
     cat_src_ct: torch.Tensor | None     # int32 [nW*4]: carrier row of every (window, slot)
     cat_dst_ct: torch.Tensor | None     # int32 [nW*4]: its row in the concatenated tensor
     cat_dst_x: torch.Tensor | None      # int32 [nW*49]: row of every window token in the concatenated tensor
-    training: bool
-
-
-def _layout(carrier: bool, has_ls: bool) -> list[str]:
-    """Order of the tensor inputs after (x, ct)."""
-    names = [f"pos.{k}" for k in _POS_KEYS] + [f"attn.{k}" for k in _ATTN_KEYS] + [f"mlp.{k}" for k in _MLP_KEYS]
-    if carrier:
-        names += [f"hpos.{k}" for k in _POS_KEYS] + [f"hattn.{k}" for k in _ATTN_KEYS] + [f"hmlp.{k}" for k in _MLP_KEYS]
-    names += ["gamma3", "gamma4"] + (["gamma1", "gamma2"] if carrier else [])
-    names += ["rs_win", "rs_ct"]
-    return names
 
 
 class HATFunction(torch.autograd.Function):
     """One hierarchical-attention block.  x: [nW, 49, 1, C] window tokens; ct: [B, 16, 1, C] carrier tokens in row-major
-    image order (None without carrier tokens).  Returns (x_out, ct_out)."""
+    image order (None without carrier tokens); then hat_inputs(...), rs_win, rs_ct.  Returns (x_out, ct_out)."""
 
     @staticmethod
     def forward(ctx, x, ct, cfg: HATCtx, *t):
-        names = _layout(cfg.carrier, True)
-        T = dict(zip(names, t))
+        win, car, (rs_win, rs_ct) = cut_hat(t, None, cfg.carrier)
         nW, Tw, _, C = x.shape
-
-        def sub(prefix, keys):
-            return {k: T[f"{prefix}.{k}"] for k in keys}
-
-        x1 = K.add_rowtable(x, T["pos.table"])
-        saved_ct = None
+        x1 = K.add_rowtable(x, win.pos.tab)
+        per, kept = 0, ()
         if cfg.carrier:
             B, Tc = ct.shape[0], ct.shape[1]
-            c1 = K.add_rowtable(ct, T["hpos.table"])
-            c2, hattn_saved = attn_sub_fwd(c1, sub("hattn", _ATTN_KEYS), cfg.ct_spec, T["gamma1"], T["rs_ct"])
-            c3, hmlp_saved = mlp_sub_fwd(c2, sub("hmlp", _MLP_KEYS), T["gamma2"], T["rs_ct"])
+            c1 = K.add_rowtable(ct, car.pos.tab)
+            c2, hattn_saved = attn_sub_fwd(c1, car.attn, cfg.heads, rs_ct)
+            c3, hmlp_saved = mlp_sub_fwd(c2, car.mlp, rs_ct)
             per = Tc * B // nW                                      # carrier tokens per window (4)
             xc = torch.empty((nW, Tw + per, 1, C), dtype=x.dtype, device=x.device)
             K.copy_rows(c3.view(-1, C), cfg.cat_src_ct, xc.view(-1, C), cfg.cat_dst_ct, nW * per)
             K.copy_rows(x1.view(-1, C), None, xc.view(-1, C), cfg.cat_dst_x, nW * Tw)
-            saved_ct = (hattn_saved, hmlp_saved, per)
+            kept = (*hattn_saved, *hmlp_saved)
         else:
             xc = x1
-        xa, attn_saved = attn_sub_fwd(xc, sub("attn", _ATTN_KEYS), cfg.win_spec, T["gamma3"], T["rs_win"])
-        xm, mlp_saved = mlp_sub_fwd(xa, sub("mlp", _MLP_KEYS), T["gamma4"], T["rs_win"])
+        xa, attn_saved = attn_sub_fwd(xc, win.attn, cfg.heads, rs_win)
+        xm, mlp_saved = mlp_sub_fwd(xa, win.mlp, rs_win)
         if cfg.carrier:
-            per = saved_ct[2]
             x_out = torch.empty_like(x)
             ct_out = torch.empty_like(ct)
             K.copy_rows(xm.view(-1, C), cfg.cat_dst_x, x_out.view(-1, C), None, nW * Tw)
             K.copy_rows(xm.view(-1, C), cfg.cat_dst_ct, ct_out.view(-1, C), cfg.cat_src_ct, nW * per)
         else:
             x_out, ct_out = xm, None
-        ctx.cfg = cfg
-        ctx.names = names
-        ctx.T = T
-        ctx.saved = (saved_ct, attn_saved, mlp_saved)
+        ctx.cfg, ctx.per = cfg, per
         ctx.shapes = (tuple(x.shape), tuple(ct.shape) if ct is not None else None, x.dtype)
+        # the inputs, then what the two or four sub-blocks kept; never an output (without carrier tokens x_out is mlp_sub_fwd's)
+        ctx.save_for_backward(*t, *kept, *attn_saved, *mlp_saved)
         if ct_out is None:
             ctx.mark_non_differentiable()
             return x_out, None
@@ -464,27 +486,21 @@ class HATFunction(torch.autograd.Function):
     @K.batched_sums
     def backward(ctx, gx, gct):
         cfg: HATCtx = ctx.cfg
-        names, T = ctx.names, ctx.T
-        saved_ct, attn_saved, mlp_saved = ctx.saved
+        per = ctx.per
         x_shape, ct_shape, dt = ctx.shapes
-        need = dict(zip(["x", "ct", "cfg"] + names, ctx.needs_input_grad))
+        need_x, need_ct, _, *need = ctx.needs_input_grad
+        saved = ctx.saved_tensors
+        win, car, (rs_win, rs_ct) = cut_hat(saved[:len(need)], need, cfg.carrier)
+        kept = iter(saved[len(need):])
+        if cfg.carrier:
+            hattn_saved, hmlp_saved = tuple(islice(kept, N_ATTN_SAVED)), tuple(islice(kept, N_MLP_SAVED))
+        attn_saved, mlp_saved = tuple(islice(kept, N_ATTN_SAVED)), tuple(islice(kept, N_MLP_SAVED))
         nW, Tw, _, C = x_shape
         dev = gx.device
-        grads: dict = {}
-
-        def sub(prefix, keys):
-            return {k: T[f"{prefix}.{k}"] for k in keys}
-
-        def sub_need(prefix, keys, gamma):
-            d = {k: need[f"{prefix}.{k}"] for k in keys}
-            d["ls"] = need[gamma]
-            return d
-
-        carrier_up = cfg.carrier and (need["ct"] or any(need[n] for n in names if n.startswith(("hpos", "hattn", "hmlp", "gamma1", "gamma2"))))
-        need_x1 = need["x"] or any(need[f"pos.{k}"] for k in _POS_KEYS)
+        carrier_up = cfg.carrier and (need_ct or any(getattr(r, "need_" + f) for part in _stream_slots(car) for r, f in part))
+        need_x1 = need_x or win.pos.need_tab
         gx = _c(gx)
         if cfg.carrier:
-            per = saved_ct[2]
             gm = torch.empty((nW, Tw + per, 1, C), dtype=dt, device=dev)
             K.copy_rows(gx.view(-1, C), None, gm.view(-1, C), cfg.cat_dst_x, nW * Tw)
             if gct is not None:
@@ -494,18 +510,10 @@ class HATFunction(torch.autograd.Function):
                 K.copy_rows(zero, None, gm.view(-1, C), cfg.cat_dst_ct, nW * per)
         else:
             gm = gx
-        need_xa = True
-        dxa, g_mlp = mlp_sub_bwd(gm, mlp_saved, sub("mlp", _MLP_KEYS), T["gamma4"], T["rs_win"], sub_need("mlp", _MLP_KEYS, "gamma4"), need_xa)
-        for k, v in g_mlp.items():
-            grads["gamma4" if k == "ls" else f"mlp.{k}"] = v
-        need_xc = need_x1 or carrier_up
-        dxc, g_attn = attn_sub_bwd(dxa, attn_saved, sub("attn", _ATTN_KEYS), cfg.win_spec, T["gamma3"], T["rs_win"],
-                                   sub_need("attn", _ATTN_KEYS, "gamma3"), need_xc)
-        for k, v in g_attn.items():
-            grads["gamma3" if k == "ls" else f"attn.{k}"] = v
+        dxa = mlp_sub_bwd(gm, mlp_saved, win.mlp, rs_win, True)
+        dxc = attn_sub_bwd(dxa, attn_saved, win.attn, cfg.heads, rs_win, need_x1 or carrier_up)
         dx = dct = None
         if cfg.carrier:
-            hattn_saved, hmlp_saved, per = saved_ct
             dx1 = None
             if need_x1:
                 dx1 = torch.empty(x_shape, dtype=dt, device=dev)
@@ -513,26 +521,20 @@ class HATFunction(torch.autograd.Function):
             if carrier_up:
                 dc3 = torch.empty(ct_shape, dtype=dt, device=dev)
                 K.copy_rows(dxc.view(-1, C), cfg.cat_dst_ct, dc3.view(-1, C), cfg.cat_src_ct, nW * per)
-                dc2, g_hm = mlp_sub_bwd(dc3, hmlp_saved, sub("hmlp", _MLP_KEYS), T["gamma2"], T["rs_ct"], sub_need("hmlp", _MLP_KEYS, "gamma2"), True)
-                for k, v in g_hm.items():
-                    grads["gamma2" if k == "ls" else f"hmlp.{k}"] = v
-                need_c1 = need["ct"] or any(need[f"hpos.{k}"] for k in _POS_KEYS)
-                dc1, g_ha = attn_sub_bwd(dc2, hattn_saved, sub("hattn", _ATTN_KEYS), cfg.ct_spec, T["gamma1"], T["rs_ct"],
-                                         sub_need("hattn", _ATTN_KEYS, "gamma1"), need_c1)
-                for k, v in g_ha.items():
-                    grads["gamma1" if k == "ls" else f"hattn.{k}"] = v
-                if need_c1:
-                    if need["hpos.table"]:
-                        grads["hpos.table"] = K.rowtable_grad(dc1, ct_shape[1])
-                    dct = dc1 if need["ct"] else None
+                dc2 = mlp_sub_bwd(dc3, hmlp_saved, car.mlp, rs_ct, True)
+                dc1 = attn_sub_bwd(dc2, hattn_saved, car.attn, cfg.heads, rs_ct, need_ct or car.pos.need_tab)
+                if car.pos.need_tab:
+                    car.pos.dtab = K.rowtable_grad(dc1, ct_shape[1])
+                dct = dc1 if need_ct else None
         else:
             dx1 = dxc
-        if need_x1 and dx1 is not None:
-            if need["pos.table"]:
-                grads["pos.table"] = K.rowtable_grad(dx1, Tw)
-            dx = dx1 if need["x"] else None
-        flat = [grads.get(nm) if need[nm] else None for nm in names]
-        return (dx, dct, None, *flat)
+        if need_x1:
+            if win.pos.need_tab:
+                win.pos.dtab = K.rowtable_grad(dx1, Tw)
+            dx = dx1 if need_x else None
+        return (dx, dct, None, *hat_grads(win, car))
+
+
 
 
 # =========================================================================== ConvBlock (levels 0, 1)
@@ -637,7 +639,7 @@ class FVDownsampleFunction(torch.autograd.Function):
             dcol, _, _ = K.pwconv(g, None, w_kn, None, stats=False)
             dxn = K.col2im(dcol, (N, H, W, C), 3, 2, 1)
             dx, dgm, dbt = K.layernorm_bwd(dxn, x, ln_w, lnst)
-            dlw, dlb = _to_slot(dgm, ln_w, need[1]), _to_slot(dbt, ln_b, need[2])
+            dlw, dlb = _place(dgm, ln_w, need[1]), _place(dbt, ln_b, need[2])
             if not need[0]:
                 dx = None
         return dx, dlw, dlb, dw
@@ -666,7 +668,7 @@ class TokenInitFunction(torch.autograd.Function):
         N, H, W, C = x.shape
         ho = (H - kernel) // stride + 1
         g4 = _c(g).view(N, ho, -1, C)
-        db = _to_slot(K.rowtable_grad(g4, 1).view(-1), b, need[2])
+        db = _place(K.rowtable_grad(g4, 1).view(-1), b, need[2])
         dx = dw = None
         if need[0] or need[1]:
             dy = K.avgpool_bwd(g4, yshape, kernel, stride)
@@ -677,4 +679,4 @@ class TokenInitFunction(torch.autograd.Function):
         return dx, dw, db, None, None
 
 
-__all__ = ["AttnSpec", "ConvBlockCtx", "ConvBlockFunction", "FVDownsampleFunction", "HATCtx", "HATFunction", "TokenInitFunction"]
+__all__ = ["ConvBlockCtx", "ConvBlockFunction", "FVDownsampleFunction", "HATCtx", "HATFunction", "TokenInitFunction"]

@@ -205,6 +205,34 @@ def test_hat(fv, level, train):
     check_masks(Stage(leaves, lambda: blk(x, ct, maps, None, tables)))
 
 
+@TRAIN
+@pytest.mark.parametrize("sr_ratio", [2, 1], ids=["carrier_tokens", "plain"])
+def test_hat_with_layer_scale(sr_ratio, train):
+    """test_hat on a block with LayerScale (FasterViT-0 has none): gamma1..4 are leaves, so proj's and fc2's LayerScale gradients
+    and the BatchNorm-shaped backward of fc2 go through every mask.  A stand-alone block at the smallest width its kernels take
+    (dim 64, head dim 32); 3 images of 12 (carrier tokens: 14 x 14 maps) or 3 windows."""
+    from deepfakedetection_amd.fastervit import HipHAT, _window_maps
+    from deepfakedetection_amd.fastervit_functions import coord_tables
+
+    torch.manual_seed(0)
+    blk = HipHAT(dim=64, heads=2, sr_ratio=sr_ratio, drop_path=0.0, layer_scale=1e-5, index=0)
+    randomise_fv(blk, 1)                                          # gammas: 0.2 .. 0.5
+    blk = blk.cuda().train(train)
+    carrier = sr_ratio > 1
+    B = 3
+    x = rand(5, B * (4 if carrier else 1), 49, 1, 64).cuda()
+    ct = rand(6, B, 16, 1, 64).cuda() if carrier else None
+    maps = _window_maps(B, 14, torch.device("cuda"))[1:] if carrier else None
+    with torch.no_grad():
+        tables = [t.clone() for t in coord_tables(*blk.coord_jobs())]
+    leaves = {"x": x, **{f"table{i}": t for i, t in enumerate(tables)},
+              **{n: p for n, p in blk.named_parameters() if "pos_emb" not in n}}
+    assert {"gamma3", "gamma4"} | ({"gamma1", "gamma2"} if carrier else set()) <= set(leaves)
+    if ct is not None:
+        leaves["ct"] = ct
+    check_masks(Stage(leaves, lambda: blk(x, ct, maps, None, tables)))
+
+
 # ------------------------------------------------------------------ EfficientNet-B0
 @pytest.fixture(scope="module")
 def en():
@@ -336,4 +364,8 @@ def test_fastervit_0_with_an_arena():
     model = HipFasterViT("0", 2, 224, drop_path_rate=0.0)
     randomise_fv(model, 1)
     b = "levels.1.blocks.0"                                       # the first ConvBlock of level 1
-    _check_model(model.cuda(), (f"{b}.conv1.weight", f"{b}.conv1.bias", f"{b}.norm1.weight", f"{b}.norm1.bias"))
+    h = "levels.2.blocks.1"                                       # a HAT block with carrier tokens: one LayerNorm parameter frozen takes
+    #                                                               _ln_bwd off its adjacent-slot path, either side of the test
+    _check_model(model.cuda(), (f"{b}.conv1.weight", f"{b}.conv1.bias", f"{b}.norm1.weight", f"{b}.norm1.bias",
+                                f"{h}.norm1.weight", f"{h}.norm1.bias", f"{h}.attn.qkv.bias", f"{h}.mlp.fc1.bias",
+                                f"{h}.mlp.fc2.weight", f"{h}.hat_norm2.bias"))
