@@ -140,6 +140,8 @@ SIGNATURES: dict[str, tuple] = {
     "dfd_roc_curve": (c_int, [P, P, c_int, c_int64, P, c_size_t, P, P, P, P, P]),
     "dfd_roc_sweep": (c_int, [P, P, P, P, c_int, P, c_int, P, P, P]),
     "dfd_confusion": (c_int, [P, P, c_int, c_int, P, P, P]),
+    # ---- ABI 147
+    "dfd_ce_loss_w": (c_int, [P, P, c_int, c_int, c_int, c_float, c_float, P, c_float, P, P, P, P, P]),
     # ---- ABI 111
     "dfd_bn_eval_coeffs_multi": (c_int, [P, c_int, P]),
     "dfd_sum_batch_begin": (c_int, []),

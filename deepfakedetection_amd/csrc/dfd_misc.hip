@@ -906,6 +906,121 @@ extern "C" int dfd_ce_loss_soft(const float* logits, const float* targets, int N
     return DFD_CHECK_LAUNCH();
 }
 
+// Class-weighted and focal cross entropy (ABI 147), index or probability targets behind one entry point:
+//   row_n = -sum_j w_j q_nj (1 - p_nj)^gamma logp_nj,   loss = sum_n row_n / D,   D = sum_n w[t_n] (index targets) or N.
+// (1 - p)^fg and fg * (1 - p)^(fg - 1); fg > 0 and omp > 0.  fg = 1 and 2 are products, any other fg goes through exp2 / log2.
+__device__ __forceinline__ void focal_powers(float omp, float fg, float& m, float& dm) {
+    const float pw1 = fg == 1.f ? 1.f : fg == 2.f ? omp : exp2f((fg - 1.f) * log2f(omp));
+    m = pw1 * omp;
+    dm = fg * pw1;
+}
+// One class of one row: its term of the row loss (before the sign) and g = d(term sum)/d(logp) chain factor of the header.
+//   d = logit - row maximum, e = exp(d), se = sum of e, cnt = how many d are 0, rest = the sum of the other e, lse = log(se).
+// The class at the maximum has 1 - p = (cnt - 1 + rest) / se, which keeps its relative accuracy where 1 - e / se cancels.
+// q == 0 gives (0, 0) whatever the logit is: a -inf logit beside it never meets a product.
+__device__ __forceinline__ void ce_w_class(float d, float q, float w, float fg, float se, float cnt, float rest, float lse,
+                                           float& p, float& term, float& g) {
+    const float e = d == 0.f ? 1.f : expf(d);
+    p = e / se;
+    term = 0.f; g = 0.f;
+    if (q == 0.f) return;
+    const float logp = d - lse, wq = w * q;
+    if (fg == 0.f) { term = wq * logp; g = -wq; return; }
+    const float omp = d == 0.f ? (cnt - 1.f + rest) / se : 1.f - p;
+    if (!(omp > 0.f)) {                                 // p = 1: both limits are 0 (a NaN row stays NaN)
+        if (omp != omp) term = g = omp;
+        return;
+    }
+    float m, dm;
+    focal_powers(omp, fg, m, dm);
+    term = wq * m * logp;
+    g = wq * (dm * p * logp - m);
+}
+__device__ __forceinline__ float ce_w_q(bool soft, const float* __restrict__ tr, int tgt, int j, float keep, float floor_q) {
+    return soft ? tr[j] * keep + floor_q : floor_q + (j == tgt ? keep : 0.f);
+}
+// denom[0] = sum_n w[t_n] in a fixed order (one workgroup); a target outside [0, J) adds nothing
+__global__ void __launch_bounds__(DFD_THREADS)
+k_ce_w_denom(const int64_t* __restrict__ targets, const float* __restrict__ w, int N, int J, float* __restrict__ denom) {
+    __shared__ float sm[4];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < N; i += DFD_THREADS) {
+        const int64_t t = targets[i];
+        s += (t >= 0 && t < J) ? w[t] : 0.f;
+    }
+    s = block_reduce(s, sm, false);
+    if (threadIdx.x == 0) denom[0] = s;
+}
+__global__ void __launch_bounds__(DFD_THREADS)
+k_ce_rows_w(const float* __restrict__ logits, const void* __restrict__ targets, int soft, int N, int J, float eps, float fg,
+            const float* __restrict__ cw, float gscale, const float* __restrict__ denom, float* __restrict__ row_loss,
+            float* __restrict__ dlogits) {
+    __shared__ float sm[4];
+    const int n = blockIdx.x, t = threadIdx.x;
+    const float* lr = logits + (long)n * J;
+    const float* tr = soft ? (const float*)targets + (long)n * J : nullptr;
+    const int tgt = soft ? -1 : (int)((const int64_t*)targets)[n];
+    float mx = -INFINITY;
+    for (int j = t; j < J; j += DFD_THREADS) mx = fmaxf(mx, lr[j]);
+    mx = block_reduce(mx, sm, true);
+    float cnt = 0.f, rest = 0.f;
+    for (int j = t; j < J; j += DFD_THREADS) {
+        const float d = lr[j] - mx;
+        if (d == 0.f) cnt += 1.f; else rest += expf(d);
+    }
+    cnt = block_reduce(cnt, sm, false);
+    rest = block_reduce(rest, sm, false);
+    const float se = cnt + rest;
+    const float lse = cnt == 1.f ? log1pf(rest) : logf(se);
+    const float keep = 1.f - eps, floor_q = eps / (float)J;
+    float sl = 0.f, sg = 0.f;
+    for (int j = t; j < J; j += DFD_THREADS) {
+        float p, term, g;
+        ce_w_class(lr[j] - mx, ce_w_q(soft, tr, tgt, j, keep, floor_q), cw ? cw[j] : 1.f, fg, se, cnt, rest, lse, p, term, g);
+        sl += term; sg += g;
+    }
+    sl = block_reduce(sl, sm, false);
+    if (t == 0) row_loss[n] = -sl;
+    if (dlogits) {
+        sg = block_reduce(sg, sm, false);
+        const float sc = gscale / (denom ? denom[0] : (float)N);
+        for (int j = t; j < J; j += DFD_THREADS) {
+            float p, term, g;
+            ce_w_class(lr[j] - mx, ce_w_q(soft, tr, tgt, j, keep, floor_q), cw ? cw[j] : 1.f, fg, se, cnt, rest, lse, p, term, g);
+            dlogits[(long)n * J + j] = (g - p * sg) * sc;
+        }
+    }
+}
+__global__ void k_mean_rows_w(const float* __restrict__ row_loss, int N, const float* __restrict__ denom, float* __restrict__ loss) {
+    __shared__ float sm[4];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < N; i += DFD_THREADS) s += row_loss[i];
+    s = block_reduce(s, sm, false);
+    // D = 0 (every target names a class of weight 0): NaN as in torch, whose weighted mean of the target terms is 0 / 0 then,
+    // also where label smoothing leaves the rows a positive sum
+    if (threadIdx.x == 0) {
+        const float D = denom ? denom[0] : (float)N;
+        *loss = D == 0.f ? NAN : s / D;
+    }
+}
+extern "C" int dfd_ce_loss_w(const float* logits, const void* targets, int soft, int N, int J, float label_smoothing,
+                             float focal_gamma, const float* class_weight, float grad_scale, float* denom, float* row_loss,
+                             float* loss, float* dlogits, dfd_stream stream) {
+    if (!logits || !targets || !denom || !row_loss || !loss || N < 1 || J < 1) return DFD_EINVAL;
+    if (!(focal_gamma >= 0.f) || !__builtin_isfinite(focal_gamma) || !(label_smoothing >= 0.f && label_smoothing < 1.f)) return DFD_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    // index targets under class weights: D = sum_n w[t_n], summed once; every other case divides by N
+    const float* d = nullptr;
+    if (!soft && class_weight) {
+        hipLaunchKernelGGL(k_ce_w_denom, dim3(1), dim3(DFD_THREADS), 0, st, (const int64_t*)targets, class_weight, N, J, denom);
+        d = denom;
+    }
+    hipLaunchKernelGGL(k_ce_rows_w, dim3(N), dim3(DFD_THREADS), 0, st, logits, targets, soft ? 1 : 0, N, J, label_smoothing,
+                       focal_gamma, class_weight, grad_scale, d, row_loss, dlogits);
+    hipLaunchKernelGGL(k_mean_rows_w, dim3(1), dim3(DFD_THREADS), 0, st, row_loss, N, d, loss);
+    return DFD_CHECK_LAUNCH();
+}
+
 __global__ void __launch_bounds__(DFD_THREADS)
 k_softmax_argmax(const float* __restrict__ logits, int J, float* __restrict__ probs, int64_t* __restrict__ preds) {
     __shared__ float sm[4];

@@ -342,6 +342,43 @@ class ShardedSampler:
         return iter(order[self.rank:total:self.world])
 
 
+class BalancedShardedSampler:
+    """Class-balanced training sampler: every epoch draws len(targets) indices WITH replacement, a sample of class c with
+    probability 1 / (classes present * count of c), so that every class present is seen equally often on average
+    (torch's WeightedRandomSampler with inverse-frequency weights).  The draw is torch.multinomial under
+    torch.Generator().manual_seed(seed + epoch): every rank makes the same one, pads it to a multiple of `world` like
+    ShardedSampler(pad=True) and takes its rank-strided shard.  A class without samples gets no probability."""
+
+    def __init__(self, targets, rank: int = 0, world: int = 1, seed: int = 0) -> None:
+        t = torch.as_tensor(targets, dtype=torch.int64).reshape(-1)
+        if t.numel() < 1:
+            raise ValueError("BalancedShardedSampler needs at least one target")
+        if int(t.min()) < 0:
+            raise ValueError("BalancedShardedSampler: class indices must be >= 0")
+        counts = torch.bincount(t).double()
+        present = int((counts > 0).sum())
+        self.weights = (1.0 / (present * counts))[t]                # f64 [len(targets)], sums to one
+        self.length, self.rank, self.world, self.seed = t.numel(), rank, world, seed
+        self.per_rank = math.ceil(self.length / world)
+        self.epoch = 0
+
+    def set_epoch(self, epoch: int) -> None:
+        self.epoch = epoch
+
+    def __len__(self) -> int:
+        return self.per_rank
+
+    def draw(self) -> list[int]:
+        """This epoch's common draw, padded to per_rank * world indices (what the ranks' shards interleave back to)."""
+        g = torch.Generator().manual_seed(self.seed + self.epoch)
+        order = torch.multinomial(self.weights, self.length, replacement=True, generator=g).tolist()
+        total = self.per_rank * self.world
+        return order + order[: total - len(order)]
+
+    def __iter__(self) -> Iterator[int]:
+        return iter(self.draw()[self.rank::self.world])
+
+
 def all_reduce_counts(*values: float, device: torch.device | str = "cpu") -> list[float]:
     """Sum scalars (correct / total / loss sums of `evaluate`) over ranks."""
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
@@ -351,5 +388,5 @@ def all_reduce_counts(*values: float, device: torch.device | str = "cpu") -> lis
     return t.tolist()
 
 
-__all__ = ["GradAllReducer", "ShardedSampler", "all_reduce_counts", "broadcast_module_state", "env_rank", "init_distributed",
+__all__ = ["BalancedShardedSampler", "GradAllReducer", "ShardedSampler", "all_reduce_counts", "broadcast_module_state", "env_rank", "init_distributed",
            "rccl_log_request", "rccl_log_summary"]

@@ -539,5 +539,25 @@ class CrossEntropyFunction(torch.autograd.Function):
         return K.axpby(dlogits, None, 1.0, 0.0, a_dev=gloss.reshape(1).float()), None, None
 
 
+class WeightedCrossEntropyFunction(torch.autograd.Function):
+    """CrossEntropyFunction with per-class weights (f32 [J] or None) and the focal factor (1 - p)^gamma, through dfd_ce_loss_w.
+    The mean is torch's: over the targets' weights with class indices, over N with probabilities.  The weights get no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, label_smoothing: float, focal_gamma: float, class_weight):
+        if targets.is_floating_point():
+            if targets.shape != logits.shape:
+                raise ValueError(f"probability targets must have the logits' shape {tuple(logits.shape)}, got {tuple(targets.shape)}")
+            targets = _c(targets.float())
+        loss, dlogits = K.ce_loss_w(_c(logits), targets, label_smoothing, focal_gamma, class_weight, 1.0, ctx.needs_input_grad[0])
+        ctx.save_for_backward(dlogits)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        (dlogits,) = ctx.saved_tensors
+        return K.axpby(dlogits, None, 1.0, 0.0, a_dev=gloss.reshape(1).float()), None, None, None, None
+
+
 __all__ = ["BNRef", "CrossEntropyFunction", "HeadConvFunction", "HeadCtx", "HeadFunction", "HeadTailEvalFunction", "Layer", "MBConvCtx",
-           "MBConvFunction", "StemCtx", "StemFunction", "bn_backward", "cut_layers"]
+           "MBConvFunction", "StemCtx", "StemFunction", "WeightedCrossEntropyFunction", "bn_backward", "cut_layers"]

@@ -16,6 +16,7 @@ from __future__ import annotations
 import contextlib
 import functools
 import ctypes
+import math
 import threading
 import weakref
 from dataclasses import dataclass
@@ -1166,6 +1167,41 @@ def ce_loss_soft(logits: torch.Tensor, targets: torch.Tensor, label_smoothing: f
     dlogits = torch.empty_like(logits) if want_grad else None
     check(_L().dfd_ce_loss_soft(_p(logits), _p(targets), N, J, label_smoothing, grad_scale, _p(row_loss), _p(loss),
                                 _p(dlogits), _stream()), "dfd_ce_loss_soft")
+    return loss, dlogits
+
+
+def ce_loss_w(logits: torch.Tensor, targets: torch.Tensor, label_smoothing: float, focal_gamma: float = 0.0,
+              class_weight: torch.Tensor | None = None, grad_scale: float = 1.0, want_grad: bool = True,
+              row_loss: torch.Tensor | None = None, dlogits: torch.Tensor | None = None):
+    """Class-weighted and focal cross entropy (ABI 147): `targets` are class indices (int64 [N]) or probabilities (f32 [N, J]),
+    `class_weight` is f32 [J] or None for all ones.  The mean follows torch: over sum_n w[t_n] with indices, over N with
+    probabilities.  `row_loss` / `dlogits`: caller-owned destinations, every element is overwritten."""
+    if logits.dtype != torch.float32 or logits.dim() != 2:
+        raise ValueError(f"ce_loss_w: logits must be f32 [N, J], got {logits.dtype} {tuple(logits.shape)}")
+    N, J = logits.shape
+    soft = targets.is_floating_point()
+    if soft and (targets.dtype != torch.float32 or targets.shape != logits.shape):
+        raise ValueError(f"ce_loss_w: probability targets must be f32 {tuple(logits.shape)}, got {targets.dtype} {tuple(targets.shape)}")
+    if not soft and (targets.dtype != torch.int64 or tuple(targets.shape) != (N,)):
+        raise ValueError(f"ce_loss_w: index targets must be int64 [{N}], got {targets.dtype} {tuple(targets.shape)}")
+    if class_weight is not None and (class_weight.dtype != torch.float32 or tuple(class_weight.shape) != (J,)):
+        raise ValueError(f"ce_loss_w: class_weight must be f32 [{J}], got {class_weight.dtype} {tuple(class_weight.shape)}")
+    if not (math.isfinite(focal_gamma) and focal_gamma >= 0.0) or not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f"ce_loss_w: focal_gamma must be finite and >= 0 and label_smoothing in [0, 1), got {focal_gamma!r}, {label_smoothing!r}")
+    dev = logits.device
+    for out, shape in ((row_loss, (N,)), (dlogits, (N, J))):
+        if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32):
+            raise ValueError(f"ce_loss_w: bad destination {out.dtype} {tuple(out.shape)} for f32 {shape}")
+    if row_loss is None:
+        row_loss = torch.empty(N, dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    denom = torch.empty(1, dtype=torch.float32, device=dev)
+    if not want_grad:
+        dlogits = None
+    elif dlogits is None:
+        dlogits = torch.empty_like(logits)
+    check(_L().dfd_ce_loss_w(_p(logits), _p(targets), int(soft), N, J, label_smoothing, focal_gamma, _p(class_weight), grad_scale,
+                             _p(denom), _p(row_loss), _p(loss), _p(dlogits), _stream()), "dfd_ce_loss_w")
     return loss, dlogits
 
 

@@ -20,7 +20,7 @@ from ._lib import (
     CLIP_STATE_LEN, CLIP_STEPS,
 )
 from .arena import GradArena
-from .functions import CrossEntropyFunction
+from .functions import CrossEntropyFunction, WeightedCrossEntropyFunction
 
 _CHUNK = 4096          # elements per workgroup of the fused kernel (~1000 workgroups for EfficientNet-B0)
 _CLIP_MODES = {"norm": CLIP_MODE_NORM, "value": CLIP_MODE_VALUE}
@@ -38,10 +38,45 @@ def check_clip(limit, mode: str) -> tuple[float | None, str]:
     return limit, mode
 
 
+def check_class_weight(weight) -> torch.Tensor | None:
+    """f32 [J] on the CPU from a sequence or tensor of class weights (None stays None); ValueError unless it is a non-empty vector
+    of finite numbers >= 0."""
+    if weight is None:
+        return None
+    try:
+        w = torch.as_tensor(weight, dtype=torch.float64).detach().cpu()
+    except (TypeError, ValueError, RuntimeError) as exc:
+        raise ValueError(f"class weights must be a sequence of numbers, got {weight!r}") from exc
+    if w.dim() != 1 or w.numel() < 1:
+        raise ValueError(f"class weights must be a vector with one entry per class, got shape {tuple(w.shape)}")
+    if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+        raise ValueError(f"class weights must be finite and >= 0, got {w.tolist()}")
+    return w.float()
+
+
+def check_focal_gamma(gamma) -> float:
+    gamma = float(gamma)
+    if not math.isfinite(gamma) or gamma < 0.0:
+        raise ValueError(f"focal_gamma must be a finite number >= 0 (0: off), got {gamma!r}")
+    return gamma
+
+
 class HipCrossEntropyLoss(nn.Module):
-    def __init__(self, label_smoothing: float = 0.0) -> None:
+    """nn.CrossEntropyLoss(label_smoothing=, weight=) on the device, plus the focal factor (1 - p)^focal_gamma of Lin et al. 2017
+    on every term.  `weight` is kept as an f32 buffer (it follows .to(device), and a captured step reads it at a fixed address:
+    `criterion.weight.copy_(new)` reaches the next replay).  Without weights and with focal_gamma 0 the module launches exactly
+    dfd_ce_loss / dfd_ce_loss_soft; otherwise dfd_ce_loss_w.  The mean is torch's: over sum_n weight[t_n] for class indices, over
+    N for probability targets."""
+
+    def __init__(self, label_smoothing: float = 0.0, weight=None, focal_gamma: float = 0.0) -> None:
         super().__init__()
         self.label_smoothing = float(label_smoothing)
+        self.focal_gamma = check_focal_gamma(focal_gamma)
+        self.register_buffer("weight", check_class_weight(weight))
+
+    def extra_repr(self) -> str:
+        w = None if self.weight is None else [round(v, 4) for v in self.weight.tolist()]
+        return f"label_smoothing={self.label_smoothing}, weight={w}, focal_gamma={self.focal_gamma}"
 
     def forward(self, logits: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
         if not logits.is_cuda:
@@ -49,7 +84,17 @@ class HipCrossEntropyLoss(nn.Module):
         # like nn.CrossEntropyLoss: integer targets are class indices [N], floating targets are class probabilities [N, J]
         if targets.is_floating_point() and targets.shape != logits.shape:
             raise ValueError(f"probability targets must have the logits' shape {tuple(logits.shape)}, got {tuple(targets.shape)}")
-        return CrossEntropyFunction.apply(logits.float(), targets, self.label_smoothing)
+        if self.weight is None and self.focal_gamma == 0.0:
+            return CrossEntropyFunction.apply(logits.float(), targets, self.label_smoothing)
+        weight = self.weight
+        if weight is not None:
+            if weight.numel() != logits.shape[-1]:
+                raise ValueError(f"{weight.numel()} class weights for logits of {logits.shape[-1]} classes")
+            if weight.device != logits.device:          # a criterion nobody moved: once, at its first use (never inside a capture,
+                self.weight = weight = weight.to(logits.device)     # whose first sight of a batch shape runs eagerly)
+        if not targets.is_floating_point() and targets.dtype != torch.int64:
+            targets = targets.long()
+        return WeightedCrossEntropyFunction.apply(logits.float(), targets, self.label_smoothing, self.focal_gamma, weight)
 
 
 class HipAdamW(torch.optim.Optimizer):

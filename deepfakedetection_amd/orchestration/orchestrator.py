@@ -171,7 +171,8 @@ _EXTRA_TRAIN_ENV = (("ft_batch_size", "FT_BATCH_SIZE"), ("pretrained", "PRETRAIN
                     ("trivial_augment", "TRIVIAL_AUGMENT"), ("clip_grad", "CLIP_GRAD"), ("clip_mode", "CLIP_MODE"),
                     ("jpeg_p", "JPEG_P"), ("jpeg_quality_min", "JPEG_QUALITY_MIN"), ("jpeg_quality_max", "JPEG_QUALITY_MAX"),
                     ("blur_p", "BLUR_P"), ("blur_sigma_min", "BLUR_SIGMA_MIN"), ("blur_sigma_max", "BLUR_SIGMA_MAX"),
-                    ("val_auc", "VAL_AUC"), ("select_metric", "SELECT_METRIC"))
+                    ("val_auc", "VAL_AUC"), ("select_metric", "SELECT_METRIC"),
+                    ("class_weights", "CLASS_WEIGHTS"), ("focal_gamma", "FOCAL_GAMMA"), ("balanced_sampling", "BALANCED_SAMPLING"))
 
 
 def _first_set(*values: Any) -> Any:

@@ -47,7 +47,7 @@ from ..orchestration.train_env import (
     apply_seed, as_bool, create_console, env_float, env_int, env_path, env_str, maybe_load_checkpoint, prepare_training_environment,
     save_best_checkpoint, save_latest_checkpoint,
 )
-from ._inputs import blur_settings, device_batches, get_loaders, jpeg_settings, make_loader, policy_settings
+from ._inputs import balanced_sampling, blur_settings, device_batches, get_loaders, jpeg_settings, make_loader, policy_settings
 
 DATA_ROOT = Path.home() / "code" / "DeepfakeDetection" / "data" / "Dataset"
 LOG_EVERY = 10
@@ -300,6 +300,60 @@ def make_mixer(settings: MixSettings | None, num_classes: int, device: str):
                       switch_prob=settings.switch_prob, mode=settings.mode, num_classes=num_classes)
 
 
+@dataclass(frozen=True)
+class LossSettings:
+    class_weights: tuple[float, ...] | str | None      # the weights, "balanced" until resolve_loss_settings() has the counts, or None
+    focal_gamma: float
+
+    def describe(self) -> str:
+        w = "none" if self.class_weights is None else self.class_weights if isinstance(self.class_weights, str) \
+            else "[" + ", ".join(f"{v:.4g}" for v in self.class_weights) + "]"
+        return f"class_weights={w} | focal_gamma={self.focal_gamma:g}"
+
+
+def loss_settings(num_classes: int) -> LossSettings | None:
+    """$CLASS_WEIGHTS (YAML training.class_weights: `balanced`, or one weight per class — a YAML list, comma-separated in the
+    environment) and $FOCAL_GAMMA (training.focal_gamma, a float >= 0; absent or 0: off).  Both absent: None, and the criterion is
+    the plain one.  ValueError for a list that has not `num_classes` finite entries >= 0 and for a negative or non-finite gamma."""
+    from ..optim import check_class_weight, check_focal_gamma
+
+    raw = env_str("CLASS_WEIGHTS", "").strip()
+    gamma = check_focal_gamma(env_float("FOCAL_GAMMA", 0.0))
+    weights: tuple[float, ...] | str | None = None
+    if raw.lower() == "balanced":
+        weights = "balanced"
+    elif raw and raw.lower() not in {"none", "0", "false", "off", "no"}:
+        fields = [f.strip() for f in raw.strip("[]() ").split(",") if f.strip()]
+        try:
+            values = [float(f) for f in fields]
+        except ValueError as exc:
+            raise ValueError(f"training.class_weights must be `balanced` or a list of numbers, got {raw!r}") from exc
+        if len(values) != num_classes:
+            raise ValueError(f"training.class_weights has {len(values)} entries for {num_classes} classes: {raw!r}")
+        weights = tuple(check_class_weight(values).double().tolist())
+    return None if weights is None and not gamma else LossSettings(class_weights=weights, focal_gamma=gamma)
+
+
+def balanced_class_weights(counts, names=None) -> tuple[float, ...]:
+    """w_j = n / (J * n_j) from the pictures per class of the whole training split (scikit-learn's `balanced`); a class without
+    a picture is a ValueError that names it."""
+    counts = [int(c) for c in counts]
+    empty = [str(names[j]) if names is not None and j < len(names) else str(j) for j, c in enumerate(counts) if c < 1]
+    if empty or not counts:
+        raise ValueError(f"training.class_weights: balanced needs a training picture of every class, none of: {', '.join(empty) or 'any class'}")
+    n, J = sum(counts), len(counts)
+    return tuple(n / (J * c) for c in counts)
+
+
+def resolve_loss_settings(settings: LossSettings | None, targets, num_classes: int, names=None) -> LossSettings | None:
+    """`balanced` made into numbers from the training dataset's `targets` — the whole split, not a rank's shard, so that every
+    rank gets the same weights."""
+    if settings is None or settings.class_weights != "balanced":
+        return settings
+    counts = torch.bincount(torch.as_tensor(list(targets), dtype=torch.int64), minlength=num_classes).tolist()
+    return LossSettings(class_weights=balanced_class_weights(counts, names), focal_gamma=settings.focal_gamma)
+
+
 def _load_pretrained(model: nn.Module, name: str) -> None:
     hint = env_str("PRETRAINED", "")
     if hint.lower() in ("0", "false", "no", "none"):
@@ -320,13 +374,29 @@ def _load_pretrained(model: nn.Module, name: str) -> None:
     console.print("[bold yellow]⚠️  No local pretrained weights[/] (set training.pretrained); starting from random init")
 
 
-def _make_criterion_and_optimizer(use_cuda: bool):
+def _make_criterion_and_optimizer(use_cuda: bool, loss_cfg: LossSettings | None = None):
+    """The TRAINING criterion (label smoothing 0.1; `loss_cfg`: resolved class weights and focal gamma) and the optimizer class."""
+    weights = None if loss_cfg is None else loss_cfg.class_weights
+    gamma = 0.0 if loss_cfg is None else loss_cfg.focal_gamma
+    if isinstance(weights, str):
+        raise ValueError("class_weights: balanced must be resolved from the training targets first (resolve_loss_settings)")
     if use_cuda:
         from ..optim import HipAdamW, HipCrossEntropyLoss
 
-        return HipCrossEntropyLoss(label_smoothing=0.1), HipAdamW
+        if weights is None and not gamma:
+            return HipCrossEntropyLoss(label_smoothing=0.1), HipAdamW
+        return HipCrossEntropyLoss(label_smoothing=0.1, weight=weights, focal_gamma=gamma), HipAdamW
     # device: cpu — the reference's own torch path; only non-HIP (plug-in) modules can run there
-    return nn.CrossEntropyLoss(label_smoothing=0.1), optim.AdamW
+    if gamma:
+        raise RuntimeError("the focal loss (training.focal_gamma) runs on a HIP device only (no CPU fallback)")
+    weight = None if weights is None else torch.tensor(weights, dtype=torch.float32)
+    return nn.CrossEntropyLoss(weight=weight, label_smoothing=0.1), optim.AdamW
+
+
+def _make_eval_criterion(use_cuda: bool) -> nn.Module:
+    """What evaluate() reports as val_loss: always the plain label-smoothed cross entropy, whatever the training criterion is
+    weighted by, so that validation losses compare between runs and with earlier checkpoints."""
+    return _make_criterion_and_optimizer(use_cuda)[0]
 
 
 def evaluate(model: nn.Module, dl: DataLoader, device: str, tail=None, criterion: nn.Module | None = None,
@@ -516,6 +586,7 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
     policy_settings()       # a bad training.rand_augment_* / trivial_augment is a ValueError here, not a class-count message below
     clip_cfg = clip_settings()      # and so is a bad training.clip_grad / clip_mode
     metric_cfg = metric_settings()  # and a bad training.select_metric
+    loss_cfg = loss_settings(num_classes)   # and a bad training.class_weights / focal_gamma
     if metric_cfg.val_auc and not use_cuda:
         console.print("[bold yellow]training.val_auc / select_metric: auc ignored[/]: the AUC kernels need a CUDA device; accuracy is followed")
         metric_cfg = MetricSettings(val_auc=False, select="acc")
@@ -543,8 +614,19 @@ def run(spec: TrainerSpec) -> None:  # noqa: PLR0915
     model.to(memory_format=torch.channels_last)
     model = model.to(device)
     broadcast_module_state(model)
-    criterion, make_opt = _make_criterion_and_optimizer(use_cuda)
-    eval_criterion = criterion if spec.report_loss else None
+    # class weights / focal loss ($CLASS_WEIGHTS, $FOCAL_GAMMA) shape the training criterion only: val_loss stays the plain loss
+    loss_cfg = resolve_loss_settings(loss_cfg, getattr(train_dl.dataset, "targets", ()), num_classes,
+                                     getattr(train_dl.dataset, "classes", None))
+    if loss_cfg is None:
+        criterion, make_opt = _make_criterion_and_optimizer(use_cuda)
+        eval_criterion = criterion if spec.report_loss else None
+    else:
+        criterion, make_opt = _make_criterion_and_optimizer(use_cuda, loss_cfg)
+        criterion = criterion.to(device)
+        eval_criterion = _make_eval_criterion(use_cuda) if spec.report_loss else None
+        console.print(f"[bold]Loss[/]: {loss_cfg.describe()} (training only; val_loss is the unweighted loss)")
+    if balanced_sampling():
+        console.print("[bold]Sampling[/]: class-balanced epochs (training.balanced_sampling), drawn with replacement")
     mixer = make_mixer(mix_settings(), num_classes, device)      # Mixup / CutMix ($MIXUP_ALPHA, $CUTMIX_ALPHA)
     scaler = torch.amp.GradScaler(enabled=False)        # bf16 needs no loss scaling; calls kept for parity
     opt_extra = {"grad_scale": 1.0 / world} if use_cuda else {}

@@ -13,8 +13,8 @@ import torch
 from torch.utils.data import DataLoader
 
 from .. import data as D
-from ..dp import ShardedSampler
-from ..orchestration.train_env import env_float, env_int, env_str, load_transform_toggles, require_num_classes
+from ..dp import BalancedShardedSampler, ShardedSampler
+from ..orchestration.train_env import as_bool, env_float, env_int, env_str, load_transform_toggles, require_num_classes
 
 
 def _rgb(image):
@@ -221,11 +221,21 @@ def build_transforms(img_size: int, gpu_tail: bool = False, *, rotation_default:
     return D.Compose(train), D.Compose(val)
 
 
+def balanced_sampling() -> bool:
+    """$BALANCED_SAMPLING (YAML training.balanced_sampling, default off): the training loaders draw class-balanced epochs."""
+    return as_bool(env_str("BALANCED_SAMPLING", "0"))
+
+
 def make_loader(dataset, batch_size: int, num_workers: int, *, shuffle: bool, rank: int = 0, world: int = 1,
-                seed: int = 0) -> DataLoader:
+                seed: int = 0, balanced: bool | None = None) -> DataLoader:
+    """`balanced` (default: balanced_sampling()) gives a training loader (shuffle=True) dp.BalancedShardedSampler over the
+    dataset's `targets`, at any `world`; a validation loader (shuffle=False) never gets it."""
     extra = {"prefetch_factor": 2} if num_workers > 0 else {}
-    # training shards are padded to equal length (equal step counts for the all-reduce); validation shards are not
-    sampler = ShardedSampler(len(dataset), rank, world, shuffle=shuffle, seed=seed, pad=shuffle) if world > 1 else None
+    if shuffle and (balanced_sampling() if balanced is None else balanced):
+        sampler = BalancedShardedSampler(dataset.targets, rank, world, seed=seed)
+    else:
+        # training shards are padded to equal length (equal step counts for the all-reduce); validation shards are not
+        sampler = ShardedSampler(len(dataset), rank, world, shuffle=shuffle, seed=seed, pad=shuffle) if world > 1 else None
     # pipelines that end in D.PlanGeometry ship variable-size decoded images: packed by D.collate_raw
     tf = getattr(dataset, "transform", None)
     if tf is not None and any(isinstance(op, D.PlanGeometry) for op in getattr(tf, "ops", ())):

@@ -92,7 +92,8 @@ typedef void* dfd_stream;          /* a hipStream_t */
  * 144 = dfd_blur_u8 (Gaussian-blur augmentation: Pillow's three box passes along x and three along y, byte-exact);
  * 145 = dfd_softmax_argmax returns index 0 for a row that holds a NaN or an infinity (it returned 0x7fffffff), dfd_ce_loss with
  * label_smoothing 0 keeps a finite loss beside a -inf logit off the target (it returned NaN); finite inputs give the same bits;
- * 146 = dfd_roc_curve / dfd_roc_ws, dfd_roc_sweep, dfd_confusion (exact ROC curve, rank statistic, threshold sweep and confusion matrix). */
+ * 146 = dfd_roc_curve / dfd_roc_ws, dfd_roc_sweep, dfd_confusion (exact ROC curve, rank statistic, threshold sweep and confusion matrix);
+ * 147 = dfd_ce_loss_w (cross entropy with per-class weights and the focal modulating factor, index or probability targets). */
 int dfd_version(void);
 
 /* Planner knobs: the tier switches and grid sizes by which tests and per-layer scripts reach a kernel tier.  Process-wide plain ints:
@@ -412,6 +413,24 @@ int dfd_ce_loss(const float* logits, const int64_t* targets, int N, int J,
 int dfd_ce_loss_soft(const float* logits, const float* targets, int N, int J,
                      float label_smoothing, float grad_scale, float* row_loss, float* loss,
                      float* dlogits, dfd_stream stream);
+/* Class-weighted and focal cross entropy (ABI 147).  targets: int64 [N] class indices (soft = 0) or f32 [N][J] probabilities
+ * (soft != 0).  With p = softmax(logits) per row, ls = label_smoothing in [0, 1), gamma = focal_gamma >= 0 and w = class_weight
+ * (f32 [J]; NULL: all ones):
+ *   q[n][j]     = (1 - ls) * (j == targets[n]) + ls / J      (indices)     or     targets[n][j] * (1 - ls) + ls / J
+ *   row_loss[n] = -sum_j w[j] * q[n][j] * (1 - p[n][j])^gamma * logp[n][j]   ((1 - p)^0 = 1 also at p = 1)
+ *   loss        = sum_n row_loss[n] / D,   D = sum_n w[targets[n]] for indices, N for probabilities
+ * which are the rules of torch's cross_entropy(weight=, label_smoothing=, reduction="mean"): with gamma 0 the loss is torch's.
+ * At D = 0 (every target names a class of weight 0) the loss is NaN, as torch's is, whatever the rows sum to.  A term whose q is 0 is 0 whatever its logit is (a -inf logit off the target with ls = 0 keeps the loss
+ * finite and has gradient 0).  dlogits (optional) = grad_scale / D * (g[n][k] - p[n][k] * sum_j g[n][j]) with
+ *   g[n][j] = w[j] * q[n][j] * (gamma * (1 - p)^(gamma - 1) * p * logp - (1 - p)^gamma),   the bracket 0 at p = 1 for gamma > 0.
+ * denom: one float of device scratch the caller owns (D of the weighted index case is summed there first, in a fixed order;
+ * its content afterwards is unspecified).  No atomics: equal inputs give equal bits.  Two launches, three with indices and
+ * weights.  NULL logits / targets / denom / row_loss / loss, N < 1, J < 1, gamma < 0 or not finite, ls outside [0, 1):
+ * DFD_EINVAL, nothing is launched.  Index targets are not range-checked (one outside [0, J) matches no class). */
+int dfd_ce_loss_w(const float* logits, const void* targets, int soft, int N, int J,
+                  float label_smoothing, float focal_gamma, const float* class_weight,
+                  float grad_scale, float* denom, float* row_loss, float* loss,
+                  float* dlogits, dfd_stream stream);
 /* probs (optional) = softmax(logits) per row, preds = its arg max, the lowest index on ties.  A row that holds a NaN or an
  * infinity has NaN probabilities and preds 0 (torch.argmax(torch.softmax(row))): preds is always an index into the row. */
 int dfd_softmax_argmax(const float* logits, int N, int J, float* probs, int64_t* preds,
