@@ -142,6 +142,9 @@ SIGNATURES: dict[str, tuple] = {
     "dfd_confusion": (c_int, [P, P, c_int, c_int, P, P, P]),
     # ---- ABI 147
     "dfd_ce_loss_w": (c_int, [P, P, c_int, c_int, c_int, c_float, c_float, P, c_float, P, P, P, P, P]),
+    # ---- ABI 148
+    "dfd_bgemm_plan": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "dfd_attn_softmax_plan": (c_int, [c_int, c_int, _PI, _PI]),
     # ---- ABI 111
     "dfd_bn_eval_coeffs_multi": (c_int, [P, c_int, P]),
     "dfd_sum_batch_begin": (c_int, []),

@@ -790,14 +790,29 @@ k_bgemm_kred(const void* __restrict__ A, MatDesc da, const void* __restrict__ B,
     }
 }
 
+// which kernel serves (M, N, K): the ONE place this is decided — dfd_bgemm launches by it, dfd_bgemm_plan reports it
+enum { BG_PLAN_GENERAL = 0, BG_PLAN_SMALL = 1, BG_PLAN_KRED = 2 };
+static size_t bgemm_lds(int M, int N, int K) { return ((size_t)K * ((M + 3) & ~3) + (size_t)K * ((N + 3) & ~3)) * 4; }
+static int bgemm_plan(int M, int N, int K, int round_a, int round_b) {
+    const size_t lds = bgemm_lds(M, N, K);                        // both panels of k_bgemm, f32
+    const bool small = M <= 16 && N <= 16 && lds > 48 * 1024 && !round_a && !round_b;
+    const bool kred = M <= 8 && N <= 8 && K >= 512 && !round_a && !round_b;
+    if (!small && lds > 150 * 1024) return DFD_EUNSUPPORTED;
+    return kred ? BG_PLAN_KRED : small ? BG_PLAN_SMALL : BG_PLAN_GENERAL;
+}
+extern "C" int dfd_bgemm_plan(int M, int N, int K, int round_a, int round_b) {
+    if (M < 1 || N < 1 || K < 1) return DFD_EINVAL;
+    return bgemm_plan(M, N, K, round_a, round_b);
+}
+
 extern "C" int dfd_bgemm(int dt_a, const void* A, const dfd_mat* sa, int dt_b, const void* B, const dfd_mat* sb, int dt_c,
                          void* C, const dfd_mat* sc, const float* bias, float alpha, int nb, int nh, int M, int N, int K,
                          int round_a, int round_b, dfd_stream stream) {
     if (!A || !B || !C || !sa || !sb || !sc || nb < 1 || nh < 1 || M < 1 || N < 1 || K < 1) return DFD_EINVAL;
-    const size_t lds = ((size_t)K * ((M + 3) & ~3) + (size_t)K * ((N + 3) & ~3)) * 4;
-    const bool small = M <= 16 && N <= 16 && lds > 48 * 1024 && !round_a && !round_b;
-    const bool kred = M <= 8 && N <= 8 && K >= 512 && !round_a && !round_b;
-    if (!small && lds > 150 * 1024) return DFD_EUNSUPPORTED;
+    const int plan = bgemm_plan(M, N, K, round_a, round_b);
+    if (plan < 0) return plan;
+    const bool small = plan == BG_PLAN_SMALL, kred = plan == BG_PLAN_KRED;
+    const size_t lds = bgemm_lds(M, N, K);
     const MatDesc da{sa->sb, sa->sh, sa->sr, sa->sc}, db{sb->sb, sb->sh, sb->sr, sb->sc}, dc{sc->sb, sc->sh, sc->sr, sc->sc};
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)(nb * nh));
@@ -884,7 +899,7 @@ k_attn_softmax_fwd(const float* __restrict__ S, const float* __restrict__ w1, co
     {
         const int NP = H * R;
         int TEAM = 1;
-        while (TEAM < 32 && TEAM * 2 * NP <= DFD_THREADS) TEAM *= 2;
+        while (TEAM < 32 && TEAM * 2 * NP <= DFD_THREADS) TEAM *= 2;       // restated on the host: attn_softmax_plan
         const int pr = t / TEAM, m = t - pr * TEAM;
         const int h = pr < NP ? pr / R : 0, r2 = pr < NP ? pr - h * R : 0;
         const bool rowok = pr < NP && (long)blockIdx.x * R + r2 < rows;
@@ -971,7 +986,7 @@ k_attn_softmax_bwd(const float* __restrict__ dT2, const float* __restrict__ P, c
     {   // row sums of dP * P: TEAM threads per (h, row) pair, as in the forward kernel
         const int NP = H * R;
         int TEAM = 1;
-        while (TEAM < 32 && TEAM * 2 * NP <= DFD_THREADS) TEAM *= 2;
+        while (TEAM < 32 && TEAM * 2 * NP <= DFD_THREADS) TEAM *= 2;       // restated on the host: attn_softmax_plan
         const int pr = t / TEAM, m = t - pr * TEAM;
         const int h = pr < NP ? pr / R : 0, r2 = pr < NP ? pr - h * R : 0;
         const bool rowok = pr < NP && (long)blockIdx.x * R + r2 < rows;
@@ -1007,15 +1022,31 @@ k_attn_softmax_bwd(const float* __restrict__ dT2, const float* __restrict__ P, c
         }
     }
 }
+// R rows per workgroup and TEAM threads per (head, row) pair for (H, Nk): the ONE place R is decided (both launchers and
+// dfd_attn_softmax_plan call it).  TEAM is computed inside the kernels from (H, R) — the loop below restates that rule (the
+// `while (TEAM < 32 && TEAM * 2 * NP <= DFD_THREADS)` of k_attn_softmax_fwd / _bwd, NP = H * R) and must change with it.
+static int attn_softmax_plan(int H, int Nk, int* R_out, int* team_out) {
+    if (H < 1 || H > ATT_MAX_H || Nk < 1 || Nk > 256) return DFD_EINVAL;
+    int R = 256 / Nk;
+    if (R > 64) R = 64;
+    while (H * R > 256) --R;
+    if (R < 1) return DFD_EUNSUPPORTED;
+    int team = 1;
+    while (team < 32 && team * 2 * H * R <= DFD_THREADS) team *= 2;
+    if (R_out) *R_out = R;
+    if (team_out) *team_out = team;
+    return DFD_OK;
+}
+extern "C" int dfd_attn_softmax_plan(int H, int Nk, int* R, int* team) { return attn_softmax_plan(H, Nk, R, team); }
+
 extern "C" int dfd_attn_softmax_fwd(const float* S, const float* th_w1, const float* th_b1, const float* th_w2,
                                     const float* th_b2, float* P, float* T2, int B, int H, int Nq, int Nk, dfd_stream stream) {
     if (!S || !P || B < 1 || H < 1 || H > ATT_MAX_H || Nq < 1 || Nk < 1 || Nk > 256) return DFD_EINVAL;
     const bool talk = th_w1 != nullptr;
     if (talk && (!th_w2 || !T2)) return DFD_EINVAL;
-    int R = 256 / Nk;
-    if (R > 64) R = 64;
-    while (H * R > 256) --R;
-    if (R < 1) return DFD_EUNSUPPORTED;
+    int R;
+    const int plan = attn_softmax_plan(H, Nk, &R, nullptr);
+    if (plan != DFD_OK) return plan;
     const long rows = (long)B * Nq;
     const unsigned grid = (unsigned)((rows + R - 1) / R);
     if (talk) hipLaunchKernelGGL((k_attn_softmax_fwd<true>), dim3(grid), dim3(DFD_THREADS), 0, (hipStream_t)stream, S, th_w1, th_b1, th_w2, th_b2, P, T2, rows, H, Nq, Nk, R);
@@ -1027,10 +1058,9 @@ extern "C" int dfd_attn_softmax_bwd(const float* dT2, const float* P, const floa
     if (!dT2 || !P || !dS || B < 1 || H < 1 || H > ATT_MAX_H || Nq < 1 || Nk < 1 || Nk > 256) return DFD_EINVAL;
     const bool talk = th_w1 != nullptr;
     if (talk && (!th_w2 || !dT1)) return DFD_EINVAL;
-    int R = 256 / Nk;
-    if (R > 64) R = 64;
-    while (H * R > 256) --R;
-    if (R < 1) return DFD_EUNSUPPORTED;
+    int R;
+    const int plan = attn_softmax_plan(H, Nk, &R, nullptr);
+    if (plan != DFD_OK) return plan;
     const long rows = (long)B * Nq;
     const unsigned grid = (unsigned)((rows + R - 1) / R);
     if (talk) hipLaunchKernelGGL((k_attn_softmax_bwd<true>), dim3(grid), dim3(DFD_THREADS), 0, (hipStream_t)stream, dT2, P, th_w1, th_w2, dT1, dS, rows, H, Nq, Nk, R);

@@ -93,7 +93,9 @@ typedef void* dfd_stream;          /* a hipStream_t */
  * 145 = dfd_softmax_argmax returns index 0 for a row that holds a NaN or an infinity (it returned 0x7fffffff), dfd_ce_loss with
  * label_smoothing 0 keeps a finite loss beside a -inf logit off the target (it returned NaN); finite inputs give the same bits;
  * 146 = dfd_roc_curve / dfd_roc_ws, dfd_roc_sweep, dfd_confusion (exact ROC curve, rank statistic, threshold sweep and confusion matrix);
- * 147 = dfd_ce_loss_w (cross entropy with per-class weights and the focal modulating factor, index or probability targets). */
+ * 147 = dfd_ce_loss_w (cross entropy with per-class weights and the focal modulating factor, index or probability targets);
+ * 148 = dfd_bgemm_plan, dfd_attn_softmax_plan (which kernel dfd_bgemm runs, and the rows per workgroup and threads per (head, row)
+ * of dfd_attn_softmax_fwd / _bwd: host-side queries for the tests that name a tier; no kernel changed). */
 int dfd_version(void);
 
 /* Planner knobs: the tier switches and grid sizes by which tests and per-layer scripts reach a kernel tier.  Process-wide plain ints:
@@ -695,6 +697,10 @@ typedef struct { long sb, sh, sr, sc; } dfd_mat;
 int dfd_bgemm(int dt_a, const void* A, const dfd_mat* sa, int dt_b, const void* B, const dfd_mat* sb,
               int dt_c, void* C, const dfd_mat* sc, const float* bias, float alpha, int nb, int nh, int M,
               int N, int K, int round_a, int round_b, dfd_stream stream);
+/* Which kernel dfd_bgemm runs for (M, N, K) and the rounding flags (ABI 148; host code, the decision dfd_bgemm itself takes):
+ * 0 = the LDS-panel kernel with 4 x 4 register tiles, 1 = the chunked long-K kernel (M, N <= 16 and panels beyond 48 KiB),
+ * 2 = the K-parallel kernel (M, N <= 8, K >= 512), DFD_EUNSUPPORTED = panels beyond 150 KiB that neither of the two takes.  */
+int dfd_bgemm_plan(int M, int N, int K, int round_a, int round_b);
 /* Attention rows on S [B][H][Nq][Nk] f32:  [T1 = W1*S + b1 over heads ->] P = softmax_k(T1) [-> T2 = W2*P + b2]
  * th_w1 == NULL: no talking heads (T2 unused).  H <= 16, Nk <= 256.                                          */
 int dfd_attn_softmax_fwd(const float* S, const float* th_w1, const float* th_b1, const float* th_w2,
@@ -703,6 +709,9 @@ int dfd_attn_softmax_fwd(const float* S, const float* th_w1, const float* th_b1,
 /* dT2 -> dS (and dT1, the gradient at the softmax input, when talking heads are on)                           */
 int dfd_attn_softmax_bwd(const float* dT2, const float* P, const float* th_w1, const float* th_w2,
                          float* dT1, float* dS, int B, int H, int Nq, int Nk, dfd_stream stream);
+/* The launch shape of both for (H, Nk) (ABI 148; host code): *R = (b, query) rows per workgroup, *team = threads that share the
+ * maximum and the sums of one (head, row) pair.  Returns DFD_OK or the error the launchers return; R / team may be NULL.     */
+int dfd_attn_softmax_plan(int H, int Nk, int* R, int* team);
 /* learned attention bias table [H][T] <-> full [H][L] through idx [L] (int32)                                 */
 int dfd_bias_gather(const float* table, const int* idx, float* full, int H, int T, long L, dfd_stream stream);
 int dfd_bias_scatter(const float* dfull, const int* idx, float* dtable, int H, int T, long L, int accumulate,

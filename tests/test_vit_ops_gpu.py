@@ -737,7 +737,10 @@ def test_window_attention_at_every_fastervit_head_dim(monkeypatch, rd, hd, H, T,
 # ---------------------------------------------------------------------------------------------------------------------
 # fused window attention on the bf16 matrix cores (csrc/dfd_attn.hip) against plain torch f32 attention
 @pytest.mark.parametrize("n,T,H,with_bias", [(5, 53, 8, True), (4, 49, 16, True), (3, 16, 8, True), (9, 49, 4, False), (2, 64, 2, True),
-                                              (1, 1, 1, True), (6, 33, 3, True)])
+                                              (1, 1, 1, True), (6, 33, 3, True),
+                                              # the template switch at T = 32 itself, and one token either side of every 16-token tile edge
+                                              (5, 32, 2, True), (4, 31, 3, True), (3, 17, 2, True), (6, 15, 1, True), (2, 48, 4, True),
+                                              (5, 63, 2, True), (1, 2, 2, True)])
 def test_fused_window_attention_forward_and_backward(n, T, H, with_bias):
     """o = softmax(scale q k^T + bias) v read in place from the qkv projection output; backward recomputes P from the saved
     log-sum-exp.  Operands are bf16 (exact inputs for both sides); P and dS are rounded to bf16 for their products, so the
@@ -766,6 +769,8 @@ def test_fused_window_attention_forward_and_backward(n, T, H, with_bias):
     qd = qkv.cuda().view(n, T, 1, 3 * C)
     bd = bias.cuda() if with_bias else None
     o, L = K.wattn_fwd(qd, bd, H, scale)
+    o_only, no_L = K.wattn_fwd(qd, bd, H, scale, want_lse=False)
+    assert no_L is None and torch.equal(o, o_only)             # the log-sum-exp store is the only difference
     dqkv, dbias = K.wattn_bwd(qd, dO.cuda().view(n, T, 1, C), L, bd, H, scale, with_bias)
     torch.cuda.synchronize()
     tol = 1.6e-2
