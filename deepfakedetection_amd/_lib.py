@@ -145,6 +145,8 @@ SIGNATURES: dict[str, tuple] = {
     # ---- ABI 148
     "dfd_bgemm_plan": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "dfd_attn_softmax_plan": (c_int, [c_int, c_int, _PI, _PI]),
+    # ---- ABI 149
+    "dfd_rowtable_grad_plan": (c_int, [c_int, c_long, c_int, c_int, _PI, POINTER(c_long), _PI]),
     # ---- ABI 111
     "dfd_bn_eval_coeffs_multi": (c_int, [P, c_int, P]),
     "dfd_sum_batch_begin": (c_int, []),

@@ -1619,17 +1619,35 @@ static int rowtable_splits(long nw, int Tn, int C, int vec) {
     return s < 1 ? 1 : (int)s;
 }
 extern "C" size_t dfd_rowtable_grad_ws(int T, int C) { return (size_t)(ROWTAB_MAX_SPLITS + 2) * T * C * sizeof(float); }
-extern "C" int dfd_rowtable_grad(int dtype, const void* g, float* dtable, long rows, int T, int C, int accumulate, float* ws,
-                                 size_t ws_bytes, dfd_stream stream) {
-    if (!g || !dtable || !ws || rows < 1 || T < 1 || rows % T || C < 1 || (dtype != DFD_BF16 && dtype != DFD_F32)) return DFD_EINVAL;
+// the launch shape of dfd_rowtable_grad: the ONE place it is decided — dfd_rowtable_grad launches by it, dfd_rowtable_grad_plan reports it
+static int rowtable_plan(int dtype, long rows, int T, int C, int* splits, long* w_per, ChanMap* cm) {
+    if (rows < 1 || T < 1 || rows % T || C < 1 || (dtype != DFD_BF16 && dtype != DFD_F32)) return DFD_EINVAL;
     const int vec = dtype == DFD_BF16 ? Vec<bf16>::N : Vec<float>::N;
     if (C % vec) return DFD_EINVAL;
+    const long nw = rows / T;
+    *cm = make_chanmap(C, vec);
+    *splits = rowtable_splits(nw, T, C, vec);
+    *w_per = (nw + *splits - 1) / *splits;
+    return DFD_OK;
+}
+extern "C" int dfd_rowtable_grad_plan(int dtype, long rows, int T, int C, int* splits, long* w_per, int* rpb) {
+    int s = 0; long wp = 0; ChanMap cm;
+    const int code = rowtable_plan(dtype, rows, T, C, &s, &wp, &cm);
+    if (code != DFD_OK) return code;
+    if (splits) *splits = s;
+    if (w_per) *w_per = wp;
+    if (rpb) *rpb = cm.rpb;
+    return DFD_OK;
+}
+extern "C" int dfd_rowtable_grad(int dtype, const void* g, float* dtable, long rows, int T, int C, int accumulate, float* ws,
+                                 size_t ws_bytes, dfd_stream stream) {
+    if (!g || !dtable || !ws) return DFD_EINVAL;
+    int splits; long w_per; ChanMap cm;
+    const int code = rowtable_plan(dtype, rows, T, C, &splits, &w_per, &cm);
+    if (code != DFD_OK) return code;
     if (ws_bytes < dfd_rowtable_grad_ws(T, C)) return DFD_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const long nw = rows / T;
-    const ChanMap cm = make_chanmap(C, vec);
-    const int splits = rowtable_splits(nw, T, C, vec);
-    const long w_per = (nw + splits - 1) / splits;
     const dim3 grid(T, cm.nvc, splits);
     if (dtype == DFD_BF16) hipLaunchKernelGGL((k_rowtable_grad<bf16>), grid, dim3(DFD_THREADS), 0, st, (const bf16*)g, ws, nw, T, C, cm, w_per);
     else hipLaunchKernelGGL((k_rowtable_grad<float>), grid, dim3(DFD_THREADS), 0, st, (const float*)g, ws, nw, T, C, cm, w_per);

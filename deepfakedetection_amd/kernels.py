@@ -1742,6 +1742,14 @@ def rowtable_grad(g: torch.Tensor, T: int) -> torch.Tensor:
     return dtable
 
 
+def rowtable_grad_plan(dtype: torch.dtype, rows: int, T: int, C: int) -> tuple[int, int, int]:
+    """(splits, windows per split, row lanes) of rowtable_grad's launch for `rows` rows of C elements (host code, no launch)."""
+    splits, w_per, rpb = ctypes.c_int(-1), ctypes.c_long(-1), ctypes.c_int(-1)
+    check(_L().dfd_rowtable_grad_plan(_dt(dtype), rows, T, C, ctypes.byref(splits), ctypes.byref(w_per), ctypes.byref(rpb)),
+          "dfd_rowtable_grad_plan", f"rows={rows} T={T} C={C}")
+    return splits.value, w_per.value, rpb.value
+
+
 def avgpool_fwd(x: torch.Tensor, k: int, stride: int) -> torch.Tensor:
     _chk_nhwc(x)
     N, H, W, C = x.shape

@@ -95,7 +95,9 @@ typedef void* dfd_stream;          /* a hipStream_t */
  * 146 = dfd_roc_curve / dfd_roc_ws, dfd_roc_sweep, dfd_confusion (exact ROC curve, rank statistic, threshold sweep and confusion matrix);
  * 147 = dfd_ce_loss_w (cross entropy with per-class weights and the focal modulating factor, index or probability targets);
  * 148 = dfd_bgemm_plan, dfd_attn_softmax_plan (which kernel dfd_bgemm runs, and the rows per workgroup and threads per (head, row)
- * of dfd_attn_softmax_fwd / _bwd: host-side queries for the tests that name a tier; no kernel changed). */
+ * of dfd_attn_softmax_fwd / _bwd: host-side queries for the tests that name a tier; no kernel changed);
+ * 149 = dfd_rowtable_grad_plan (the window splits, windows per split and row lanes of dfd_rowtable_grad: host-side query; no kernel
+ * changed). */
 int dfd_version(void);
 
 /* Planner knobs: the tier switches and grid sizes by which tests and per-layer scripts reach a kernel tier.  Process-wide plain ints:
@@ -763,6 +765,10 @@ int dfd_add_rowtable(int dtype, const void* x, const float* table, void* out, lo
 size_t dfd_rowtable_grad_ws(int T, int C);       /* bytes of scratch for dfd_rowtable_grad (no initial contents required) */
 int dfd_rowtable_grad(int dtype, const void* g, float* dtable, long rows, int T, int C, int accumulate,
                       float* ws, size_t ws_bytes, dfd_stream stream);
+/* The launch shape of dfd_rowtable_grad for the same (dtype, rows, T, C) (ABI 149; host code, the decision dfd_rowtable_grad itself
+ * takes): *splits = slices of the rows / T windows summed apart (grid z), *w_per = windows per slice (the last one may hold fewer),
+ * *rpb = row lanes of a workgroup.  Any of the three may be NULL.  DFD_EINVAL where dfd_rowtable_grad rejects the shape. */
+int dfd_rowtable_grad_plan(int dtype, long rows, int T, int C, int* splits, long* w_per, int* rpb);
 /* nn.AvgPool2d(k, stride) without padding on NHWC (TokenInitializer) and its gradient (dx [N][H][W][C])         */
 int dfd_avgpool_fwd(int dtype, const void* x, void* out, int N, int H, int W, int k, int stride, int C,
                     dfd_stream stream);
