@@ -45,6 +45,16 @@ ROC_STATS_LEN = 5
 (ROC_P, ROC_N, ROC_G, ROC_NONFINITE, ROC_TWO_U) = range(5)
 CONFUSION_LDS_MAX_J = 128           # largest J whose J x J int32 histogram stays in LDS
 CONFUSION_MAX_J = 1024
+# csrc/dfd_calib.hip (the DFD_CALIB_* constants of include/dfd_hip.h)
+CALIB_MAX_N = 1 << 28
+CALIB_MAX_J = 1024
+CALIB_MAX_BINS = 64
+CALIB_MAX_BETAS = 64
+CALIB_THREAD_MAX_J = 16             # widest row that one thread takes; above it one wave per row
+CALIB_MAX_BLOCKS = 1024             # stage-1 workgroups at most
+CALIB_STAGE2_WIDTH = 64             # partials the stage-2 loop takes per trip
+CALIB_LAYOUT_THREAD, CALIB_LAYOUT_WAVE = 0, 1
+(CALIB_VALID, CALIB_NONFINITE, CALIB_OOB, CALIB_CORRECT) = range(4)
 
 
 class DwShape(Structure):
@@ -147,6 +157,13 @@ SIGNATURES: dict[str, tuple] = {
     "dfd_attn_softmax_plan": (c_int, [c_int, c_int, _PI, _PI]),
     # ---- ABI 149
     "dfd_rowtable_grad_plan": (c_int, [c_int, c_long, c_int, c_int, _PI, POINTER(c_long), _PI]),
+    # ---- ABI 150
+    "dfd_calib_bins_ws": (c_size_t, [c_int, c_int]),
+    "dfd_calib_bins": (c_int, [P, P, c_int, c_int, c_int, P, c_size_t, P, P, P, P]),
+    "dfd_calib_nll_ws": (c_size_t, [c_int, c_int, c_int]),
+    "dfd_calib_nll": (c_int, [P, P, c_int, c_int, POINTER(c_double), c_int, P, c_size_t, P, P, P]),
+    "dfd_calib_plan": (c_int, [c_int, c_int, _PI]),
+    "dfd_softmax_argmax_t": (c_int, [P, c_int, c_int, c_float, P, P, P]),
     # ---- ABI 111
     "dfd_bn_eval_coeffs_multi": (c_int, [P, c_int, P]),
     "dfd_sum_batch_begin": (c_int, []),

@@ -1285,6 +1285,115 @@ def confusion_counts(truth: torch.Tensor, pred: torch.Tensor, num_classes: int, 
     return counts, oob
 
 
+# ------------------------------------------------------------------ calibration (ABI 150, csrc/dfd_calib.hip)
+CALIB_MAX_N, CALIB_MAX_J, CALIB_MAX_BINS, CALIB_MAX_BETAS = _lib.CALIB_MAX_N, _lib.CALIB_MAX_J, _lib.CALIB_MAX_BINS, _lib.CALIB_MAX_BETAS
+CALIB_THREAD_MAX_J, CALIB_MAX_BLOCKS, CALIB_STAGE2_WIDTH = _lib.CALIB_THREAD_MAX_J, _lib.CALIB_MAX_BLOCKS, _lib.CALIB_STAGE2_WIDTH
+CALIB_LAYOUT_THREAD, CALIB_LAYOUT_WAVE = _lib.CALIB_LAYOUT_THREAD, _lib.CALIB_LAYOUT_WAVE
+
+
+@dataclass(frozen=True)
+class CalibPlan:
+    """dfd_calib_plan's answer: the row layout, the rows a workgroup takes per trip, the stage-1 workgroups and the trips of the
+    stage-2 loop of calib_bins / calib_nll at (n, J)."""
+
+    layout: int
+    rows: int
+    blocks: int
+    trips: int
+
+
+def _calib_rows(op: str, rows: torch.Tensor, targets: torch.Tensor) -> tuple[int, int]:
+    if rows.dim() != 2 or rows.dtype != torch.float32 or targets.dtype != torch.int64 or tuple(targets.shape) != (rows.shape[0],):
+        raise ValueError(f"{op}: expected f32 [n, J] rows and int64 [n] targets, got {rows.dtype} {tuple(rows.shape)} and "
+                         f"{targets.dtype} {tuple(targets.shape)}")
+    n, J = rows.shape
+    if not 0 <= n <= CALIB_MAX_N or not 1 <= J <= CALIB_MAX_J:
+        raise ValueError(f"{op}: takes 0..{CALIB_MAX_N} rows of 1..{CALIB_MAX_J} classes, got [{n}, {J}]")
+    return n, J
+
+
+def _calib_ws(op: str, ws: torch.Tensor | None, need: int, device) -> torch.Tensor:
+    if ws is None:
+        return torch.empty(max(need // 8, 1), dtype=torch.float64, device=device).view(torch.uint8)
+    if ws.dtype != torch.uint8 or ws.numel() < need or ws.device != device or ws.data_ptr() % 8:
+        raise ValueError(f"{op}: ws must be an 8-byte aligned uint8 tensor of at least {need} bytes on {device}")
+    return ws
+
+
+def calib_bins_ws(n: int, J: int) -> int:
+    """Bytes of workspace calib_bins needs for n rows of J classes."""
+    if not 0 <= n <= CALIB_MAX_N or not 1 <= J <= CALIB_MAX_J:
+        raise ValueError(f"calib_bins takes 0..{CALIB_MAX_N} rows of 1..{CALIB_MAX_J} classes, got [{n}, {J}]")
+    return _L().dfd_calib_bins_ws(n, J)
+
+
+def calib_nll_ws(n: int, J: int, K: int) -> int:
+    """Bytes of workspace calib_nll needs for n rows of J classes at K betas; it covers calib_bins_ws(n, J) too."""
+    if not 0 <= n <= CALIB_MAX_N or not 1 <= J <= CALIB_MAX_J or not 1 <= K <= CALIB_MAX_BETAS:
+        raise ValueError(f"calib_nll takes 0..{CALIB_MAX_N} rows of 1..{CALIB_MAX_J} classes at 1..{CALIB_MAX_BETAS} betas, got [{n}, {J}], {K}")
+    return _L().dfd_calib_nll_ws(n, J, K)
+
+
+def calib_plan(n: int, J: int) -> CalibPlan:
+    """Which layout and launch shape calib_bins / calib_nll use for n rows of J classes (host code)."""
+    out = (ctypes.c_int * 4)()
+    check(_L().dfd_calib_plan(int(n), int(J), out), "dfd_calib_plan", f"n={n} J={J}")
+    return CalibPlan(*out)
+
+
+def calib_bins(probs: torch.Tensor, targets: torch.Tensor, bins: int = 15, ws: torch.Tensor | None = None, out=None):
+    """f32 [n, J] probabilities and int64 [n] targets -> (bins int64 [M, 3] = rows / right predictions / sum of llrint(conf 2^32)
+    per confidence bin, stats int64 [4] = valid / nonfinite / out-of-range / right rows, brier f64 [1] = the summed squared
+    error of the valid rows): include/dfd_hip.h.  Three launches, no host sync.  `ws`: uint8 scratch of calib_bins_ws bytes."""
+    n, J = _calib_rows("calib_bins", probs, targets)
+    M = int(bins)
+    if not 1 <= M <= CALIB_MAX_BINS:
+        raise ValueError(f"calib_bins: bins must be 1..{CALIB_MAX_BINS}, got {M}")
+    device = probs.device
+    ws = _calib_ws("calib_bins", ws, calib_bins_ws(n, J), device)
+    o_bins, o_stats, o_brier = out if out is not None else (None, None, None)
+    table = _dst(o_bins, (M, 3), device, torch.int64)
+    stats = _dst(o_stats, (4,), device, torch.int64)
+    brier = _dst(o_brier, (1,), device, torch.float64)
+    check(_L().dfd_calib_bins(_p(probs), _p(targets), n, J, M, _p(ws), ws.numel(), _p(table), _p(stats), _p(brier), _stream()),
+          "dfd_calib_bins", f"n={n} J={J} M={M}")
+    return table, stats, brier
+
+
+def calib_nll(logits: torch.Tensor, targets: torch.Tensor, betas, ws: torch.Tensor | None = None, out=None):
+    """f32 [n, J] logits, int64 [n] targets and K <= CALIB_MAX_BETAS host floats beta = 1 / T (finite, > 0) -> (out f64 [K, 3] =
+    the summed negative log-likelihood of softmax(beta z) and its first and second derivative in beta, stats int64 [2] =
+    nonfinite / out-of-range rows, which the sums leave out): include/dfd_hip.h.  One pass over the logits for all K; two
+    launches, no host sync.  The betas travel by value in the launch."""
+    n, J = _calib_rows("calib_nll", logits, targets)
+    values = [float(b) for b in betas]
+    K = len(values)
+    if not 1 <= K <= CALIB_MAX_BETAS or not all(math.isfinite(b) and b > 0.0 for b in values):
+        raise ValueError(f"calib_nll: expected 1..{CALIB_MAX_BETAS} finite betas > 0, got {values}")
+    device = logits.device
+    ws = _calib_ws("calib_nll", ws, calib_nll_ws(n, J, K), device)
+    o_out, o_stats = out if out is not None else (None, None)
+    sums = _dst(o_out, (K, 3), device, torch.float64)
+    stats = _dst(o_stats, (2,), device, torch.int64)
+    check(_L().dfd_calib_nll(_p(logits), _p(targets), n, J, (ctypes.c_double * K)(*values), K, _p(ws), ws.numel(), _p(sums), _p(stats),
+                             _stream()), "dfd_calib_nll", f"n={n} J={J} K={K}")
+    return sums, stats
+
+
+def softmax_argmax_t(logits: torch.Tensor, inv_temperature: float, want_probs: bool = True):
+    """softmax_argmax of inv_temperature * logits (f32 [N, J]); inv_temperature finite and > 0.  At 1.0 the same bits."""
+    beta = float(inv_temperature)
+    if not (math.isfinite(beta) and beta > 0.0):
+        raise ValueError(f"softmax_argmax_t: inv_temperature must be finite and > 0, got {inv_temperature!r}")
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise ValueError(f"softmax_argmax_t: logits must be f32 [N, J], got {logits.dtype} {tuple(logits.shape)}")
+    N, J = logits.shape
+    probs = torch.empty_like(logits) if want_probs else None
+    preds = torch.empty(N, dtype=torch.int64, device=logits.device)
+    check(_L().dfd_softmax_argmax_t(_p(logits), N, J, beta, _p(probs), _p(preds), _stream()), "dfd_softmax_argmax_t")
+    return probs, preds
+
+
 # ------------------------------------------------------------------ Grad-CAM (ABI 136)
 def gradcam_map(act: torch.Tensor, grad: torch.Tensor) -> torch.Tensor:
     """Target-layer activation and its gradient, NHWC [N, h, w, C] (f32 or bf16) -> the ReLU'd Grad-CAM map f32 [N, h, w]:

@@ -1,10 +1,17 @@
-"""Exact evaluation metrics on the device: ROC-AUC, equal error rate, a threshold sweep and the confusion matrix.
+"""Exact evaluation metrics on the device: ROC-AUC, equal error rate, a threshold sweep, the confusion matrix, and the
+calibration of the probabilities (reliability bins, ECE / MCE, Brier score, NLL and a fitted temperature).
 
 The scores of a validation or inference pass stay on the device (`ScoreBook`); `binary_roc` sorts them with torch.sort and
 runs the counting kernels of csrc/dfd_metrics.hip through `kernels`.  What the kernels return are integers — the ROC curve by
 tie group and twice the Mann-Whitney U with ties counted half — so AUC is one correctly rounded division of Python integers
 and every figure derived here is a function of those integers alone: independent of the order of the samples, of the order
 inside a run of equal scores and of the launch geometry.  The host reads the results once, after the last launch.
+
+`calibration` bins the top-label confidence with csrc/dfd_calib.hip: the bins hold integers (rows, right predictions and the
+confidences as multiples of 2^-32), so ECE and MCE are again one division of Python integers each.  `fit_temperature` finds
+the single temperature T (Guo et al. 2017) that minimises the NLL of softmax(z / T): the NLL is convex in beta = 1 / T, and
+one launch evaluates it with its derivative for up to kernels.CALIB_MAX_BETAS values of beta, so the fit is a bracketing
+search with one read-back per round and no optimiser.
 
 `ScoreBook` and `gather_scores` are plain torch (they run on the CPU and under gloo as well); the metrics themselves need a
 HIP device, like every kernel front end.
@@ -19,25 +26,32 @@ import torch
 
 from . import kernels as K
 
-__all__ = ["RocResult", "ScoreBook", "binary_roc", "confusion", "eer_from_curve", "gather_scores", "ovr_auc"]
+__all__ = ["CalibrationResult", "RocResult", "ScoreBook", "TemperatureFit", "apply_temperature", "binary_roc", "calibration", "confusion",
+           "eer_from_curve", "fit_temperature", "gather_scores", "mean_nll", "ovr_auc"]
 
 
 class ScoreBook:
     """Preallocated device buffers for the class probabilities (f32 [capacity, J]), predictions and targets (int64
-    [capacity]) of one pass over a split.  append() copies a batch to a host-known offset: no synchronisation."""
+    [capacity]) of one pass over a split.  append() copies a batch to a host-known offset: no synchronisation.
+    keep_logits: a fourth buffer for the logits (f32 [capacity, J]), which calibration needs (fit_temperature)."""
 
-    def __init__(self, capacity: int, num_classes: int, device) -> None:
+    def __init__(self, capacity: int, num_classes: int, device, keep_logits: bool = False) -> None:
         self.capacity, self.num_classes, self.count = int(capacity), int(num_classes), 0
+        self._logits = torch.empty((self.capacity, self.num_classes), dtype=torch.float32, device=device) if keep_logits else None
         self._probs = torch.empty((self.capacity, self.num_classes), dtype=torch.float32, device=device)
         self._preds = torch.empty(self.capacity, dtype=torch.int64, device=device)
         self._targets = torch.empty(self.capacity, dtype=torch.int64, device=device)
 
-    def append(self, probs: torch.Tensor | None, preds: torch.Tensor | None, targets: torch.Tensor) -> None:
+    def append(self, probs: torch.Tensor | None, preds: torch.Tensor | None, targets: torch.Tensor,
+               logits: torch.Tensor | None = None) -> None:
         n = int(targets.shape[0])
+        if logits is not None and self._logits is None:
+            raise ValueError("ScoreBook.append: logits handed to a book built without keep_logits")
         if self.count + n > self.capacity:
             raise ValueError(f"ScoreBook overflow: {self.count} + {n} rows into a capacity of {self.capacity}")
         rows = slice(self.count, self.count + n)
-        for dst, src, shape in ((self._probs, probs, (n, self.num_classes)), (self._preds, preds, (n,)), (self._targets, targets, (n,))):
+        for dst, src, shape in ((self._probs, probs, (n, self.num_classes)), (self._preds, preds, (n,)), (self._targets, targets, (n,)),
+                                (self._logits, logits, (n, self.num_classes))):
             if src is None:
                 continue
             if tuple(src.shape) != shape:
@@ -59,6 +73,12 @@ class ScoreBook:
     @property
     def targets(self) -> torch.Tensor:
         return self._targets[: self.count]
+
+    @property
+    def logits(self) -> torch.Tensor:
+        if self._logits is None:
+            raise ValueError("ScoreBook.logits: the book was built without keep_logits")
+        return self._logits[: self.count]
 
 
 def eer_from_curve(fps: np.ndarray, tps: np.ndarray, n_pos: int, n_neg: int) -> float | None:
@@ -191,6 +211,143 @@ def confusion(truth: torch.Tensor, pred: torch.Tensor, num_classes: int) -> torc
     if bad:
         raise ValueError(f"confusion: {bad} pairs have a label outside [0, {num_classes})")
     return counts
+
+
+Q_ONE = 1 << 32                 # the confidences are summed as integers q = llrint(conf * 2^32)
+
+
+@dataclass
+class CalibrationResult:
+    """What calibration found.  ece / mce / brier / accuracy are None when no row is valid.  count, accuracy and confidence are
+    the per-bin arrays of the reliability diagram (nan in an empty bin); bins is the device's integer table [M, 3]."""
+
+    ece: float | None
+    mce: float | None
+    brier: float | None
+    accuracy_total: float | None
+    valid: int
+    nonfinite: int
+    count: np.ndarray
+    accuracy: np.ndarray
+    confidence: np.ndarray
+    bins: np.ndarray
+    brier_sum: float
+
+
+def calibration(probs: torch.Tensor, targets: torch.Tensor, bins: int = 15) -> CalibrationResult:
+    """Expected and maximum calibration error of the top-label confidence over `bins` equal-width right-closed bins (Guo et al.
+    2017), and the Brier score, of f32 probabilities [n, J] on the device against int64 targets.  With the integers of
+    kernels.calib_bins, ece = sum_b |right_b 2^32 - sum q_b| / (valid 2^32) and mce = max_b |right_b 2^32 - sum q_b| /
+    (rows_b 2^32): one correctly rounded division each.  Rows with a NaN or an infinity are left out and counted in
+    `nonfinite`; a target outside [0, J) raises ValueError.  One read-back after the last launch."""
+    probs = probs.detach().float().contiguous()
+    targets = targets.detach().reshape(-1).to(torch.int64).contiguous()
+    table_d, stats_d, brier_d = K.calib_bins(probs, targets, bins)
+    packed = torch.cat([table_d.reshape(-1), stats_d, brier_d.view(torch.int64)]).cpu().numpy()        # the one synchronisation
+    M = int(bins)
+    table = packed[: 3 * M].reshape(M, 3).copy()
+    valid, nonfinite, oob, right = (int(v) for v in packed[3 * M: 3 * M + 4])
+    brier_sum = float(packed[3 * M + 4:].view(np.float64)[0])
+    if oob:
+        raise ValueError(f"calibration: {oob} targets are outside [0, {probs.shape[1]})")
+    count = table[:, 0].astype(np.int64)
+    gaps = [abs(int(c) * Q_ONE - int(q)) for _, c, q in table.tolist()]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        accuracy = np.where(count > 0, table[:, 1] / np.maximum(count, 1), np.nan)
+        confidence = np.array([int(q) / (int(r) * Q_ONE) if r else float("nan") for r, _, q in table.tolist()], dtype=np.float64)
+    if valid == 0:
+        return CalibrationResult(None, None, None, None, 0, nonfinite, count, accuracy, confidence, table, brier_sum)
+    ece = sum(gaps) / (valid * Q_ONE)
+    mce = max(g / (int(r) * Q_ONE) for g, r in zip(gaps, count.tolist()) if r)
+    return CalibrationResult(ece, mce, brier_sum / valid, right / valid, valid, nonfinite, count, accuracy, confidence, table, brier_sum)
+
+
+@dataclass
+class TemperatureFit:
+    """What fit_temperature found: the temperature, the mean NLL of the valid rows at T = 1 and at `temperature`, whether the
+    minimum lies at or beyond a bound (temperature is then that bound), and the bracketing rounds run."""
+
+    temperature: float
+    nll_before: float | None
+    nll_after: float | None
+    at_bound: bool
+    rounds: int
+    valid: int = 0
+    nonfinite: int = 0
+
+
+FIT_ROUND_BETAS = 32            # geometrically spaced betas per bracketing round
+FIT_MAX_ROUNDS = 8
+FIT_BRACKET_TOL = 1e-9          # stop at hi / lo - 1 <= this
+
+
+def _geometric(lo: float, hi: float, count: int) -> list[float]:
+    """`count` values from lo to hi inclusive with a constant ratio; the ends are lo and hi themselves."""
+    ratio = hi / lo
+    return [lo] + [lo * ratio ** (i / (count - 1)) for i in range(1, count - 1)] + [hi]
+
+
+def fit_temperature(logits: torch.Tensor, targets: torch.Tensor, t_min: float = 0.05, t_max: float = 100.0) -> TemperatureFit:
+    """The temperature T in [t_min, t_max] that minimises the NLL of softmax(logits / T) (f32 [n, J] on the device) against
+    int64 targets.  The NLL is convex in beta = 1 / T, so its derivative g never decreases: the first launch looks at the two
+    bounds and at beta = 1; a g >= 0 at 1 / t_max or <= 0 at 1 / t_min returns that bound (at_bound).  Otherwise rounds of
+    FIT_ROUND_BETAS geometrically spaced betas shrink the bracket to the adjacent pair where g changes sign, until hi / lo - 1
+    <= FIT_BRACKET_TOL or FIT_MAX_ROUNDS rounds, and one secant step inside the bracket gives beta.  One read-back per round
+    and no host loop over samples.  A target outside [0, J) raises ValueError; no valid row raises ValueError."""
+    if not (0.0 < t_min < 1.0 < t_max and np.isfinite(t_max)):
+        raise ValueError(f"fit_temperature: need 0 < t_min < 1 < t_max, got {t_min!r}, {t_max!r}")
+    logits = logits.detach().float().contiguous()
+    targets = targets.detach().reshape(-1).to(torch.int64).contiguous()
+    n = logits.shape[0]
+
+    def evaluate(betas):
+        sums_d, stats_d = K.calib_nll(logits, targets, betas)
+        packed = torch.cat([sums_d.reshape(-1).view(torch.int64), stats_d]).cpu().numpy()             # the round's one synchronisation
+        return packed[:-2].view(np.float64).reshape(-1, 3), int(packed[-2]), int(packed[-1])
+
+    lo, hi = 1.0 / float(t_max), 1.0 / float(t_min)
+    first, nonfinite, oob = evaluate([lo, 1.0, hi])
+    if oob:
+        raise ValueError(f"fit_temperature: {oob} targets are outside [0, {logits.shape[1]})")
+    valid = n - nonfinite
+    if valid <= 0:
+        raise ValueError("fit_temperature: no row with finite logits")
+    nll_before = float(first[1, 0]) / valid
+    if first[0, 1] >= 0.0:
+        return TemperatureFit(float(t_max), nll_before, float(first[0, 0]) / valid, True, 0, valid, nonfinite)
+    if first[2, 1] <= 0.0:
+        return TemperatureFit(float(t_min), nll_before, float(first[2, 0]) / valid, True, 0, valid, nonfinite)
+    g_lo, g_hi = float(first[0, 1]), float(first[2, 1])
+    rounds = 0
+    while rounds < FIT_MAX_ROUNDS and hi / lo - 1.0 > FIT_BRACKET_TOL:
+        betas = _geometric(lo, hi, FIT_ROUND_BETAS)
+        g = evaluate(betas)[0][:, 1]
+        rounds += 1
+        i = next((i for i in range(1, FIT_ROUND_BETAS) if g[i] > 0.0), FIT_ROUND_BETAS - 1)      # g[0] < 0 < g[-1] by the bracket
+        lo, hi, g_lo, g_hi = betas[i - 1], betas[i], float(g[i - 1]), float(g[i])
+    beta = lo - g_lo * (hi - lo) / (g_hi - g_lo) if g_hi > g_lo else lo
+    beta = min(max(beta, lo), hi)
+    final = evaluate([beta])[0]
+    return TemperatureFit(1.0 / beta, nll_before, float(final[0, 0]) / valid, False, rounds, valid, nonfinite)
+
+
+def mean_nll(logits: torch.Tensor, targets: torch.Tensor, temperature: float = 1.0) -> float | None:
+    """The mean negative log-likelihood of softmax(logits / temperature) over the rows with finite logits, summed in f64 on the
+    device; None when there is none.  A target outside [0, J) raises ValueError.  One launch pair, one read-back."""
+    sums_d, stats_d = K.calib_nll(logits.detach().float().contiguous(), targets.detach().reshape(-1).to(torch.int64).contiguous(),
+                                  [1.0 / float(temperature)])
+    packed = torch.cat([sums_d.reshape(-1).view(torch.int64), stats_d]).cpu().numpy()
+    nonfinite, oob = int(packed[-2]), int(packed[-1])
+    if oob:
+        raise ValueError(f"mean_nll: {oob} targets are outside [0, {logits.shape[1]})")
+    valid = logits.shape[0] - nonfinite
+    return float(packed[:1].view(np.float64)[0]) / valid if valid > 0 else None
+
+
+def apply_temperature(logits: torch.Tensor, temperature: float) -> tuple[torch.Tensor, torch.Tensor]:
+    """(softmax(logits / temperature), its arg max) of f32 logits [n, J] on the device; at temperature 1 the bits of
+    kernels.softmax_argmax."""
+    return K.softmax_argmax_t(logits.detach().float().contiguous(), 1.0 / float(temperature))
 
 
 def gather_scores(scores: torch.Tensor, labels: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:

@@ -28,6 +28,7 @@ import contextlib
 import importlib
 import io
 import json
+import math
 import os
 import sys
 from collections.abc import Iterator
@@ -303,11 +304,13 @@ def build_inference_loader(*, dataset, batch_size: int, num_workers: int) -> Dat
                       persistent_workers=num_workers > 0, **extra)
 
 
-def class_probabilities(model: nn.Module, images: torch.Tensor, device: torch.device, amp: bool = False, tail=None):
+def class_probabilities(model: nn.Module, images: torch.Tensor, device: torch.device, amp: bool = False, tail=None,
+                        return_logits: bool = False):
     """logits -> (softmax probabilities, arg-max) for one batch (orchestrator.py:589-592).  amp: run the forward in a
     bf16 autocast region (opt-in `inference.amp: bf16`; the reference's inference is f32, which stays the default).
     tail: the D.GpuInputTail a data.collate_raw batch goes through (default: _GPU_EVAL_TAIL; the robustness pass hands in
-    one that perturbs the cropped bytes first)."""
+    one that perturbs the cropped bytes first).  return_logits: hand back (probabilities, arg-max, f32 logits) instead
+    (`inference.calibration` keeps them)."""
     with torch.inference_mode(), torch.autocast(device_type=device.type, dtype=torch.bfloat16, enabled=amp and device.type == "cuda"):
         if isinstance(images, (tuple, list)):          # data.collate_raw batch: resize / crop / normalise on the device
             images = (tail if tail is not None else _GPU_EVAL_TAIL)(images, device)
@@ -315,11 +318,41 @@ def class_probabilities(model: nn.Module, images: torch.Tensor, device: torch.de
         if logits.is_cuda:
             from .. import kernels  # HIP softmax/argmax epilogue
 
-            probs, preds = kernels.softmax_argmax(logits.float().contiguous(), True)
+            logits = logits.float().contiguous()
+            probs, preds = kernels.softmax_argmax(logits, True)
         else:
             probs = torch.softmax(logits, dim=1)
             preds = torch.argmax(probs, dim=1)
+    if return_logits:
+        return probs, preds, logits.float()
     return probs, preds
+
+
+def calibration_settings(infer_cfg: dict[str, Any]) -> tuple[int, str | float] | None:
+    """Extra key `inference.calibration: {bins: 15, temperature: fit}`: (bins, "fit" or the temperature to apply) or None without
+    the key.  temperature: `fit` (the default: fitted on the validation split), `off` (1.0) or a number > 0.  ValueError for
+    anything else or for bins outside 1..64."""
+    raw = infer_cfg.get("calibration")
+    if raw is None or raw is False:
+        return None
+    if raw is True:
+        raw = {}
+    if not isinstance(raw, dict):
+        raise ValueError(f"inference.calibration must be a mapping like {{bins: 15, temperature: fit}}, got {raw!r}")
+    from .._lib import CALIB_MAX_BINS
+
+    bins = int(raw.get("bins", 15))
+    if not 1 <= bins <= CALIB_MAX_BINS:
+        raise ValueError(f"inference.calibration.bins must be 1..{CALIB_MAX_BINS}, got {bins}")
+    temperature = raw.get("temperature", "fit")
+    if temperature is False or temperature is None or str(temperature).strip().lower() in ("off", "none", "false", "no"):
+        return bins, 1.0                        # YAML reads a bare `off` as false
+    if temperature is True or str(temperature).strip().lower() in ("fit", "true", "on", "yes"):
+        return bins, "fit"
+    value = float(temperature)
+    if not (math.isfinite(value) and value > 0.0):
+        raise ValueError(f"inference.calibration.temperature must be fit, off or a number > 0, got {temperature!r}")
+    return bins, value
 
 
 def robustness_levels(infer_cfg: dict[str, Any]) -> list[tuple[str, float | int]]:
@@ -420,9 +453,12 @@ def confusion_counts(truth: np.ndarray, pred: np.ndarray) -> np.ndarray:
     return cm
 
 
-def _save_plots(cm: np.ndarray, labels: list[str], truth: np.ndarray, scores: np.ndarray | None, plots: Path, roc=None) -> None:
+def _save_plots(cm: np.ndarray, labels: list[str], truth: np.ndarray, scores: np.ndarray | None, plots: Path, roc=None,
+                reliability=None) -> None:
     """confusion_matrix.png / roc_curve.png; skipped quietly when matplotlib/sklearn are absent.  roc: a metrics.RocResult
-    (inference.device_metrics) whose integer curve is drawn instead of sklearn's."""
+    (inference.device_metrics) whose integer curve is drawn instead of sklearn's.  reliability: (temperature, the
+    metrics.CalibrationResult at T = 1, the one at `temperature`) of inference.calibration, drawn as reliability.png: the
+    accuracy per confidence bin against the diagonal, before and after."""
     try:
         import matplotlib
 
@@ -443,6 +479,23 @@ def _save_plots(cm: np.ndarray, labels: list[str], truth: np.ndarray, scores: np
     fig.tight_layout()
     fig.savefig(plots / "confusion_matrix.png")
     plt.close(fig)
+    if reliability is not None:
+        temperature, before, after = reliability
+        fig, axes = plt.subplots(1, 2, figsize=(10, 5), sharey=True)
+        for ax, res, title in ((axes[0], before, "T = 1"), (axes[1], after, f"T = {temperature:.4g}")):
+            M_bins = len(res.count)
+            centres = (np.arange(M_bins) + 0.5) / M_bins
+            ax.bar(centres, np.nan_to_num(res.accuracy), width=1.0 / M_bins, edgecolor="black", alpha=0.7)
+            ax.plot([0, 1], [0, 1], linestyle="--", color="gray")
+            ece = "n/a" if res.ece is None else f"{res.ece:.4f}"
+            ax.set_title(f"{title}  (ECE {ece})")
+            ax.set_xlabel("Confidence")
+            ax.set_xlim(0, 1)
+            ax.set_ylim(0, 1)
+        axes[0].set_ylabel("Accuracy")
+        fig.tight_layout()
+        fig.savefig(plots / "reliability.png")
+        plt.close(fig)
     points = None
     if roc is not None:
         if roc.n_pos and roc.n_neg and not roc.nonfinite:
@@ -569,6 +622,23 @@ def _split_metrics_device(name: str, split: str, book, num_classes: int, thresho
     return record, probs_t, preds_t, targets_t, cm, roc
 
 
+def _calibrate_book(book, temperature: float, bins: int | None):
+    """inference.calibration on a pass kept with its logits: the book's probabilities and predictions become softmax / arg max
+    of logits / temperature (kernels.softmax_argmax_t).  With `bins`, the calibration figures of those probabilities are
+    returned as (the record's keys, the metrics.CalibrationResult); None without (the validation pass needs none)."""
+    from .. import metrics as M
+
+    probs, preds = M.apply_temperature(book.logits, temperature)
+    book.probs.copy_(probs)
+    book.preds.copy_(preds)
+    if bins is None:
+        return None
+    res = M.calibration(book.probs, book.targets, bins)
+    figures = {"temperature": float(temperature), "ece": res.ece, "mce": res.mce, "brier": res.brier,
+               "nll": M.mean_nll(book.logits, book.targets, temperature)}
+    return figures, res
+
+
 def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: dict[str, Any], run_paths: RunPaths) -> None:
     tty = getattr(sys.stdout, "isatty", None)
     out = Console(file=sys.stdout, force_terminal=bool(tty()) if callable(tty) else False)
@@ -619,18 +689,52 @@ def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: 
         device_metrics = False
     if device_metrics:
         from ..metrics import ScoreBook
+    # extra key: the passes keep their logits too; one temperature T (fitted on the validation split, or given) rescales them
+    # and ECE / MCE / Brier / NLL of the rescaled probabilities join every record (metrics.calibration, csrc/dfd_calib.hip)
+    calib = calibration_settings(infer_cfg)
+    if calib is not None and not device_metrics:
+        out.print("[bold yellow]inference.calibration ignored[/]: needs inference.device_metrics on a CUDA device")
+        calib = None
+    temperature, calib_doc = 1.0, None
+    if calib is not None:
+        calib_doc = {"temperature": 1.0, "bins": calib[0], "fitted_on": None, "n": 0, "nll_before": None, "nll_after": None}
+        if calib[1] != "fit":
+            temperature = float(calib[1])
+
+    def forward(images, tail=None):
+        """(probabilities, arg-max, the logits under inference.calibration or None) of one batch."""
+        if calib is not None:
+            return class_probabilities(model, images, device, amp, tail=tail, return_logits=True)
+        return (*class_probabilities(model, images, device, amp, tail=tail), None)
 
     threshold = 0.5
-    if num_classes == 2:
+    if num_classes == 2 or (calib is not None and calib[1] == "fit"):
         val_dir = root / data_cfg.get("val_split", "val")
+        val_seen = False
         if val_dir.exists():
             val_set = D.ImageFolder(val_dir, transform=transform)
             if len(val_set) > 0 and device_metrics:
-                book = ScoreBook(len(val_set), num_classes, device)
+                val_seen = True
+                book = ScoreBook(len(val_set), num_classes, device, keep_logits=calib is not None)
                 for images, targets in build_inference_loader(dataset=val_set, batch_size=batch_size, num_workers=num_workers):
-                    probs, _ = class_probabilities(model, images, device, amp)
-                    book.append(probs, None, targets.to(device, non_blocking=True))
-                threshold = _first_set(_device_threshold(book), threshold)
+                    probs, _, logits = forward(images)
+                    book.append(probs, None, targets.to(device, non_blocking=True), logits=logits)
+                if calib is not None and calib[1] == "fit":
+                    from ..metrics import fit_temperature
+
+                    fit = fit_temperature(book.logits, book.targets)
+                    calib_doc.update(fitted_on=str(data_cfg.get("val_split", "val")), n=book.count, nll_before=fit.nll_before,
+                                     nll_after=fit.nll_after)
+                    if fit.at_bound:
+                        out.print(f"[bold yellow]inference.calibration[/]: the fitted temperature sits at its bound "
+                                  f"{fit.temperature:g}; T = 1 is used")
+                        calib_doc["temperature_fit"] = "at_bound"
+                    else:
+                        temperature = fit.temperature
+                if calib is not None:
+                    _calibrate_book(book, temperature, None)
+                if num_classes == 2:
+                    threshold = _first_set(_device_threshold(book), threshold)
             elif len(val_set) > 0:
                 scores, truth = [], []
                 for images, targets in build_inference_loader(dataset=val_set, batch_size=batch_size, num_workers=num_workers):
@@ -640,6 +744,11 @@ def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: 
                 s, t = torch.cat(scores).numpy(), torch.cat(truth).numpy()
                 if s.size and np.unique(t).size > 1:
                     threshold = best_balanced_accuracy_threshold(s, t)
+        if calib is not None and calib[1] == "fit" and not val_seen:
+            out.print("[bold yellow]inference.calibration[/]: no validation split to fit the temperature on; T = 1 is used")
+            calib_doc["temperature_fit"] = "unavailable"
+    if calib_doc is not None:
+        calib_doc["temperature"] = float(temperature)
 
     split_dir = root / split
     if not split_dir.exists():
@@ -654,14 +763,14 @@ def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: 
     progress = Progress(TextColumn("[bold blue]{task.description}"), BarColumn(bar_width=None), MofNCompleteColumn(),
                         TimeElapsedColumn(), TimeRemainingColumn(), TextColumn("{task.fields[speed]}"), console=out)
     all_probs, all_preds, all_targets = [], [], []
-    book = ScoreBook(len(dataset), num_classes, device) if device_metrics else None
+    book = ScoreBook(len(dataset), num_classes, device, keep_logits=calib is not None) if device_metrics else None
     seen, start = 0, perf_counter()
     with progress:
         task = progress.add_task("inference", total=len(loader), speed="")
         for images, targets in loader:
-            probs, preds = class_probabilities(model, images, device, amp)
+            probs, preds, logits = forward(images)
             if book is not None:
-                book.append(probs, preds, targets.to(device, non_blocking=True))       # no host round trip per batch
+                book.append(probs, preds, targets.to(device, non_blocking=True), logits=logits)     # no host round trip per batch
             else:
                 all_probs.append(probs.cpu())
                 all_preds.append(preds.cpu())
@@ -669,8 +778,21 @@ def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: 
             seen += targets.size(0)
             progress.update(task, advance=1, speed=f"{seen / max(perf_counter() - start, 1e-6):.1f} img/s")
 
-    roc = None
-    if book is not None:
+    roc = reliability = None
+    if calib is not None:
+        from .. import metrics as M
+
+        raw = M.calibration(book.probs, book.targets, calib[0])                        # softmax at T = 1, as the pass left it
+        raw_figures = {"ece": raw.ece, "mce": raw.mce, "brier": raw.brier, "nll": M.mean_nll(book.logits, book.targets, 1.0)}
+        figures, calibrated = _calibrate_book(book, temperature, calib[0])
+        metrics, probs_t, preds_t, targets_t, cm, roc = _split_metrics_device(name, split, book, num_classes, threshold)
+        metrics.update(figures)
+        metrics["uncalibrated"] = raw_figures
+        if "temperature_fit" in calib_doc:
+            metrics["temperature_fit"] = calib_doc["temperature_fit"]
+        reliability = (temperature, raw, calibrated)
+        (run_paths.run_dir / "calibration.json").write_text(json.dumps(calib_doc, indent=2) + "\n", encoding="utf-8")
+    elif book is not None:
         metrics, probs_t, preds_t, targets_t, cm, roc = _split_metrics_device(name, split, book, num_classes, threshold)
     else:
         probs_t, preds_t, targets_t = torch.cat(all_probs), torch.cat(all_preds), torch.cat(all_targets)
@@ -679,7 +801,7 @@ def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: 
     truth_np = targets_t.numpy()
     multi_label = torch.unique(targets_t).numel() > 1
     _save_plots(cm, list(dataset.classes), truth_np, probs_t[:, 1].numpy() if num_classes == 2 and multi_label else None,
-                run_paths.plots, roc=roc)
+                run_paths.plots, roc=roc, reliability=reliability)
     with (run_paths.logs / "metrics.jsonl").open("a", encoding="utf-8") as handle:
         handle.write(json.dumps(metrics) + "\n")
     extras = " ".join(f"{k}={v:.4f}" for k, v in metrics.items() if isinstance(v, float) and k != "accuracy")
@@ -700,13 +822,17 @@ def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: 
             if book is not None:
                 book.reset()
             for images, targets in build_inference_loader(dataset=dataset, batch_size=batch_size, num_workers=num_workers):
-                probs, preds = class_probabilities(model, images, device, amp, tail=tail)
+                probs, preds, logits = forward(images, tail)
                 if book is not None:
-                    book.append(probs, preds, targets.to(device, non_blocking=True))
+                    book.append(probs, preds, targets.to(device, non_blocking=True), logits=logits)
                 else:
                     level_probs.append(probs.cpu())
                     level_preds.append(preds.cpu())
-            if book is not None:
+            if calib is not None:
+                figures = _calibrate_book(book, temperature, calib[0])[0]
+                perturbed = _split_metrics_device(name, split, book, num_classes, threshold)[0]
+                perturbed.update(figures)
+            elif book is not None:
                 perturbed = _split_metrics_device(name, split, book, num_classes, threshold)[0]
             else:
                 perturbed, _, _ = _split_metrics(name, split, torch.cat(level_probs), torch.cat(level_preds), targets_t, num_classes,

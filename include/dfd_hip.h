@@ -97,7 +97,9 @@ typedef void* dfd_stream;          /* a hipStream_t */
  * 148 = dfd_bgemm_plan, dfd_attn_softmax_plan (which kernel dfd_bgemm runs, and the rows per workgroup and threads per (head, row)
  * of dfd_attn_softmax_fwd / _bwd: host-side queries for the tests that name a tier; no kernel changed);
  * 149 = dfd_rowtable_grad_plan (the window splits, windows per split and row lanes of dfd_rowtable_grad: host-side query; no kernel
- * changed). */
+ * changed);
+ * 150 = dfd_calib_bins / _ws, dfd_calib_nll / _ws, dfd_calib_plan, dfd_softmax_argmax_t (reliability bins, Brier sum, NLL of
+ * temperature-scaled logits with two derivatives, softmax / arg max at a temperature); dfd_softmax_argmax itself is unchanged. */
 int dfd_version(void);
 
 /* Planner knobs: the tier switches and grid sizes by which tests and per-layer scripts reach a kernel tier.  Process-wide plain ints:
@@ -577,6 +579,59 @@ int dfd_roc_curve(const float* score, const int64_t* label, int n, int64_t posit
 int dfd_roc_sweep(const float* thr, const int64_t* cum_pos, const int64_t* cum_neg, const int64_t* stats, int cap, const double* cuts,
                   int T, int64_t* tp, int64_t* fp, dfd_stream stream);
 int dfd_confusion(const int64_t* truth, const int64_t* pred, int n, int J, int64_t* counts, int64_t* oob, dfd_stream stream);
+
+/* Calibration of the probabilities on the device (csrc/dfd_calib.hip, ABI 150).  Rows are samples, J <= DFD_CALIB_MAX_J classes,
+ * n <= DFD_CALIB_MAX_N rows.  In both reducing entry points a row that holds a NaN or an infinity is counted as `nonfinite` and
+ * otherwise left out; a finite row whose target is outside [0, J) is counted as `oob` and otherwise left out; the rest are valid.
+ *
+ * dfd_calib_bins: `probs` f32 [n][J], `targets` int64 [n], M <= DFD_CALIB_MAX_BINS bins.  Per valid row conf = max_j probs[i][j],
+ * pred = the lowest index that attains it (dfd_softmax_argmax's tie rule), bin = #{k in 1..M-1 : (double)conf > (double)k / (double)M}
+ * (compared in f64, right-closed bins: conf <= 0 lands in bin 0, conf >= 1 in bin M - 1) and q = llrint((double)conf * 2^32).
+ *   bins[M][3]  = {rows, rows with pred == target, sum of q} per bin (int64)
+ *   stats[4]    = {valid rows, nonfinite rows, oob rows, valid rows with pred == target}
+ *   *brier      = sum over valid rows of sum_j (probs[i][j] - [j == target])^2, in f64
+ * An f32 conf >= 2^-9 is a multiple of 2^-32 and conf >= 1 / J, so up to J = 512 q is exact; sum q < 2^61.  The integers are
+ * exact and independent of the order of the rows and of the launch geometry (integer adds only, LDS histogram per workgroup).
+ * brier is a two-stage f64 sum in a fixed order: equal inputs give equal bits.  Probabilities are expected in [0, 1]; a finite
+ * conf outside is binned by the rule above.  Three launches (zero, bin, sum).
+ *
+ * dfd_calib_nll: `logits` f32 [n][J], `targets` int64 [n], `betas` K <= DFD_CALIB_MAX_BETAS f64 values IN HOST MEMORY (they are
+ * checked here and travel by value in the launch), each finite and > 0.  All arithmetic in f64; per valid row and beta, with
+ * a_j = beta z_j, m = max_j a_j, s = sum_j exp(a_j - m), p_j = exp(a_j - m) / s:
+ *   out[k][0] (nll) += m + log s - a_y,   out[k][1] (g = d nll / d beta) += sum_j p_j z_j - z_y,
+ *   out[k][2] (h = d2 nll / d beta2) += sum_j p_j z_j^2 - (sum_j p_j z_j)^2
+ *   stats[2]   = {nonfinite rows, oob rows}
+ * One pass over the logits serves every beta (a row is read once and held in registers); the same two-stage fixed-order f64
+ * sum: equal inputs give equal bits.  Two launches.
+ *
+ * ws: dfd_calib_bins_ws(n, J) / dfd_calib_nll_ws(n, J, K) bytes of scratch, 8-byte aligned, no initial contents required.
+ * n == 0 is valid (zeros).  n, J, M or K outside its range, a beta that is not finite and > 0, or a NULL pointer: DFD_EINVAL
+ * (the _ws queries: 0), nothing is launched; a small ws: DFD_EWORKSPACE.
+ *
+ * dfd_calib_plan: out[4] = {row layout (DFD_CALIB_LAYOUT_THREAD: one thread per row, J <= DFD_CALIB_THREAD_MAX_J;
+ * DFD_CALIB_LAYOUT_WAVE: one wave per row with wave shuffles), rows per workgroup and trip, stage-1 workgroups (at most
+ * DFD_CALIB_MAX_BLOCKS; a workgroup strides over the rest), trips of the stage-2 loop (DFD_CALIB_STAGE2_WIDTH partials per
+ * trip)} of both entry points above: host code, for the tests that name a tier.
+ *
+ * dfd_softmax_argmax_t: dfd_softmax_argmax of beta * z: p_j = exp((z_j - max_j z) * beta) / sum, beta = inv_temperature finite
+ * and > 0 (else DFD_EINVAL); the same rules for non-finite rows and ties; at beta == 1.0f the same bits as dfd_softmax_argmax. */
+#define DFD_CALIB_MAX_N (1 << 28)
+#define DFD_CALIB_MAX_J 1024
+#define DFD_CALIB_MAX_BINS 64
+#define DFD_CALIB_MAX_BETAS 64
+#define DFD_CALIB_THREAD_MAX_J 16
+#define DFD_CALIB_MAX_BLOCKS 1024
+#define DFD_CALIB_STAGE2_WIDTH 64
+#define DFD_CALIB_LAYOUT_THREAD 0
+#define DFD_CALIB_LAYOUT_WAVE 1
+size_t dfd_calib_bins_ws(int n, int J);
+int dfd_calib_bins(const float* probs, const int64_t* targets, int n, int J, int M, void* ws, size_t ws_bytes, int64_t* bins,
+                   int64_t* stats, double* brier, dfd_stream stream);
+size_t dfd_calib_nll_ws(int n, int J, int K);
+int dfd_calib_nll(const float* logits, const int64_t* targets, int n, int J, const double* betas, int K, void* ws, size_t ws_bytes,
+                  double* out, int64_t* stats, dfd_stream stream);
+int dfd_calib_plan(int n, int J, int* out);
+int dfd_softmax_argmax_t(const float* logits, int N, int J, float inv_temperature, float* probs, int64_t* preds, dfd_stream stream);
 
 /* Input tail on the device (trainers/efficientnet.py:111-234): a uint8 NHWC
  * batch [N][H][W][3] -> RandomHorizontalFlip -> ToTensor (/255) -> Normalize((x-mean)/std) ->
