@@ -56,7 +56,7 @@ class ScoreBook:
                 continue
             if tuple(src.shape) != shape:
                 raise ValueError(f"ScoreBook.append: expected shape {shape}, got {tuple(src.shape)}")
-            dst[rows].copy_(src, non_blocking=True)
+            dst[rows].copy_(src, non_blocking=self._targets.is_cuda)    # a host book is read back at once: no pending copy
         self.count += n
 
     def reset(self) -> None:

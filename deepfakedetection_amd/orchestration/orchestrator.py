@@ -47,6 +47,8 @@ from torch import nn
 from torch.utils.data import DataLoader
 
 from .. import data as D
+from .. import metrics as M
+from .._lib import BLUR_MAX_PIXELS, CALIB_MAX_BINS
 from .config_schema import OrchestratorConfig
 from .model_registry import get_model_spec
 from .train_env import apply_seed, as_bool, require_num_classes
@@ -339,8 +341,6 @@ def calibration_settings(infer_cfg: dict[str, Any]) -> tuple[int, str | float] |
         raw = {}
     if not isinstance(raw, dict):
         raise ValueError(f"inference.calibration must be a mapping like {{bins: 15, temperature: fit}}, got {raw!r}")
-    from .._lib import CALIB_MAX_BINS
-
     bins = int(raw.get("bins", 15))
     if not 1 <= bins <= CALIB_MAX_BINS:
         raise ValueError(f"inference.calibration.bins must be 1..{CALIB_MAX_BINS}, got {bins}")
@@ -579,9 +579,7 @@ SWEEP_STEPS = 501           # best_balanced_accuracy_threshold's grid
 def _device_threshold(book) -> float | None:
     """best_balanced_accuracy_threshold of a validation pass kept in a metrics.ScoreBook, from the device sweep; None when
     the pass saw one class only (or scores that are not finite): the caller keeps its default."""
-    from ..metrics import binary_roc
-
-    res = binary_roc(book.probs[:, 1], book.targets, cuts=np.linspace(0.0, 1.0, SWEEP_STEPS, dtype=np.float64), strict=False)
+    res = M.binary_roc(book.probs[:, 1], book.targets, cuts=np.linspace(0.0, 1.0, SWEEP_STEPS, dtype=np.float64), strict=False)
     if not res.n_pos or not res.n_neg or res.nonfinite:
         return None
     return res.best_balanced_accuracy_threshold()
@@ -592,8 +590,6 @@ def _split_metrics_device(name: str, split: str, book, num_classes: int, thresho
     AUC, the equal error rate and the confusion matrix from the device kernels (exact, no sklearn), plus `eer` and
     `balanced_accuracy` (mean recall over the classes that occur, at the record's predictions).  Returns (record, host
     probabilities, host predictions, host targets, confusion matrix, the binary RocResult or None): one transfer of the book."""
-    from .. import metrics as M
-
     probs_d, preds_d, targets_d = book.probs, book.preds, book.targets
     roc = None
     if num_classes == 2:
@@ -622,234 +618,236 @@ def _split_metrics_device(name: str, split: str, book, num_classes: int, thresho
     return record, probs_t, preds_t, targets_t, cm, roc
 
 
-def _calibrate_book(book, temperature: float, bins: int | None):
-    """inference.calibration on a pass kept with its logits: the book's probabilities and predictions become softmax / arg max
-    of logits / temperature (kernels.softmax_argmax_t).  With `bins`, the calibration figures of those probabilities are
-    returned as (the record's keys, the metrics.CalibrationResult); None without (the validation pass needs none)."""
-    from .. import metrics as M
-
-    probs, preds = M.apply_temperature(book.logits, temperature)
-    book.probs.copy_(probs)
-    book.preds.copy_(preds)
-    if bins is None:
-        return None
-    res = M.calibration(book.probs, book.targets, bins)
-    figures = {"temperature": float(temperature), "ece": res.ece, "mce": res.mce, "brier": res.brier,
-               "nll": M.mean_nll(book.logits, book.targets, temperature)}
-    return figures, res
+def _validation_threshold(book) -> float | None:
+    """The balanced-accuracy threshold of a binary validation pass, swept where the book lives; None: keep the default."""
+    if book.probs.is_cuda:
+        return _device_threshold(book)
+    scores, truth = book.probs[:, 1].numpy(), book.targets.numpy()
+    return best_balanced_accuracy_threshold(scores, truth) if scores.size and np.unique(truth).size > 1 else None
 
 
-def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: dict[str, Any], run_paths: RunPaths) -> None:
-    tty = getattr(sys.stdout, "isatty", None)
-    out = Console(file=sys.stdout, force_terminal=bool(tty()) if callable(tty) else False)
+def _score_pass(model: nn.Module, dataset, s: InferenceSettings, book=None, tail=None, progress: Progress | None = None):
+    """One pass over `dataset` into `book`, which is returned: a metrics.ScoreBook, emptied first; None: a new one, on the device
+    under inference.device_metrics (its rows arrive without a host round trip), with the logits under inference.calibration."""
+    if book is None:
+        book = M.ScoreBook(len(dataset), s.num_classes, s.device if s.device_metrics else "cpu", keep_logits=s.calibration is not None)
+    book.reset()
+    loader = build_inference_loader(dataset=dataset, batch_size=s.batch_size, num_workers=s.num_workers)
+    start = perf_counter()
+    with progress if progress is not None else contextlib.nullcontext():
+        task = progress.add_task("inference", total=len(loader), speed="") if progress is not None else None
+        for images, targets in loader:
+            probs, preds, logits = class_probabilities(model, images, s.device, s.amp, tail=tail, return_logits=True)
+            book.append(probs, preds, targets.to(book.targets.device, non_blocking=True),
+                        logits=logits if s.calibration is not None else None)
+            if progress is not None:
+                progress.update(task, advance=1, speed=f"{book.count / max(perf_counter() - start, 1e-6):.1f} img/s")
+    return book
+
+
+@dataclass
+class PassResult:
+    """One judged pass: its metrics.jsonl record, what it was judged on (host tensors of its own) and what the plots take."""
+    record: dict[str, Any]
+    probs: torch.Tensor
+    preds: torch.Tensor
+    targets: torch.Tensor
+    cm: np.ndarray
+    roc: Any                        # the binary metrics.RocResult of a device book, else None
+    reliability: Any                # (temperature, CalibrationResult at T = 1, at T) of a clean pass under calibration, else None
+
+
+def _judge(s: InferenceSettings, book, threshold: float, calib: _Calibration | None, clean: bool = False) -> PassResult:
+    """A filled book -> the pass's result: rescaled first under inference.calibration, then judged where the book lives."""
+    figures, reliability = calib.apply(book, clean) if calib is not None else ({}, None)
+    if book.probs.is_cuda:
+        record, probs, preds, targets, cm, roc = _split_metrics_device(s.name, s.split, book, s.num_classes, threshold)
+    else:
+        probs, targets, roc = book.probs.clone(), book.targets.clone(), None        # the book is filled again by the next level
+        record, preds, cm = _split_metrics(s.name, s.split, probs, book.preds.clone(), targets, s.num_classes, threshold)
+    record.update(figures)
+    return PassResult(record, probs, preds, targets, cm, roc, reliability)
+
+
+def _emit(record: dict[str, Any], run_paths: RunPaths, out: Console, head: str) -> None:
+    """One line more in logs/metrics.jsonl, and the console row: `head`, the accuracy, then the record's other float fields."""
+    with (run_paths.logs / "metrics.jsonl").open("a", encoding="utf-8") as handle:
+        handle.write(json.dumps(record) + "\n")
+    extras = " ".join(f"{k}={v:.4f}" for k, v in record.items() if isinstance(v, float) and k != "accuracy")
+    out.print(f"{head} {record['accuracy']:.4f} {extras}")
+
+
+class _Calibration:
+    """inference.calibration of one job: the bins, the mode ("fit" or the temperature given), the temperature in force and the
+    calibration.json document.  The passes it judges are kept with their logits (ScoreBook(keep_logits=True))."""
+
+    def __init__(self, bins: int, mode: str | float) -> None:
+        self.bins, self.mode, self.temperature = bins, mode, 1.0 if mode == "fit" else float(mode)
+        self.doc = dict(temperature=self.temperature, bins=bins, fitted_on=None, n=0, nll_before=None, nll_after=None)
+
+    def fit(self, book, fitted_on: str, out: Console) -> None:
+        """Settle the temperature on the validation pass (None: there was none) and leave that pass rescaled for the threshold sweep."""
+        if self.mode == "fit" and book is None:
+            out.print("[bold yellow]inference.calibration[/]: no validation split to fit the temperature on; T = 1 is used")
+            self.doc["temperature_fit"] = "unavailable"
+        elif self.mode == "fit":
+            fit = M.fit_temperature(book.logits, book.targets)
+            self.doc.update(fitted_on=fitted_on, n=book.count, nll_before=fit.nll_before, nll_after=fit.nll_after)
+            if fit.at_bound:
+                out.print(f"[bold yellow]inference.calibration[/]: the fitted temperature sits at its bound "
+                          f"{fit.temperature:g}; T = 1 is used")
+                self.doc["temperature_fit"] = "at_bound"
+            else:
+                self.temperature = self.doc["temperature"] = float(fit.temperature)
+        if book is not None:
+            self._rescale(book)
+
+    def _rescale(self, book) -> None:
+        probs, preds = M.apply_temperature(book.logits, self.temperature)       # softmax / arg max of logits / T
+        book.probs.copy_(probs)
+        book.preds.copy_(preds)
+
+    def _figures(self, book, temperature: float):
+        res = M.calibration(book.probs, book.targets, self.bins)
+        return {"ece": res.ece, "mce": res.mce, "brier": res.brier, "nll": M.mean_nll(book.logits, book.targets, temperature)}, res
+
+    def apply(self, book, clean: bool = False):
+        """Rescale a pass -> (its record's calibration keys, None).  clean: plus the figures at T = 1 and _save_plots' reliability."""
+        before = self._figures(book, 1.0) if clean else None
+        self._rescale(book)
+        after = self._figures(book, self.temperature)
+        keys = {"temperature": float(self.temperature), **after[0]}
+        if clean:
+            keys.update(uncalibrated=before[0], **{k: v for k, v in self.doc.items() if k == "temperature_fit"})
+        return keys, (self.temperature, before[1], after[1]) if clean else None
+
+    def write(self, run_dir: Path) -> None:
+        (run_dir / "calibration.json").write_text(json.dumps(self.doc, indent=2) + "\n", encoding="utf-8")
+
+
+@dataclass(frozen=True)
+class InferenceSettings:
+    """What the inference job reads from the YAML, every fallback applied (inference_settings)."""
+    name: str
+    root: Path
+    split: str
+    val_split: str
+    num_classes: int
+    image_size: int
+    batch_size: int
+    num_workers: int
+    amp: bool                                       # extra key `amp: bf16`; default: f32 as the reference
+    device: torch.device
+    fp8_weights: bool                               # extra key (FasterViT, with `amp: bf16`): Linear weights as MX fp8 (fp8 MFMA)
+    transform: D.Compose                            # extra key `gpu_resize`: the workers only decode, the device does the rest
+    device_metrics: bool                            # extra key: the passes stay on the device, judged by the exact counting kernels
+    calibration: tuple[int, str | float] | None     # extra key (calibration_settings): the passes keep their logits, T rescales them
+    robustness: tuple[tuple[str, float | int], ...]         # the robustness_levels that can run (the device pipeline's batch is perturbed)
+    cam_limit: int | None                           # None also where Grad-CAM cannot run
+
+
+def inference_settings(config: dict[str, Any], model_cfg: dict[str, Any], out: Console) -> InferenceSettings:
+    """The job's settings from the configuration alone (no model, no data): an extra key that cannot take effect warns on `out`."""
+    on = ("1", "true", "yes", "on")
     name = model_cfg["name"]
-    spec = get_model_spec(name)
     data_cfg = config.get("data") or {}
     infer_cfg = model_cfg.get("inference") or {}        # reference uses .get("inference", {}) and breaks on None (SURVEY App. D)
     split = infer_cfg.get("split") or data_cfg.get("test_split", "test")
     batch_size = int(infer_cfg.get("batch_size", 64))
-    amp = str(infer_cfg.get("amp", "")).lower() in ("bf16", "bfloat16", "true", "1")       # extra key, default: f32 as the reference
     out.print(f"[bold]Model[/]: {name} | split={split} | batch={batch_size}")
-    num_classes = int(model_cfg.get("num_classes", data_cfg.get("num_classes", 2)))
-    image_size = int(_first_set(infer_cfg.get("img_size"), data_cfg.get("img_size"), spec.default_image_size))
-    num_workers = int(infer_cfg.get("num_workers", 4))
-
-    device_name = config.get("device") or "cuda"
-    if device_name.startswith("cuda") and not torch.cuda.is_available():
+    image_size = int(_first_set(infer_cfg.get("img_size"), data_cfg.get("img_size"), get_model_spec(name).default_image_size))
+    device = torch.device(config.get("device") or "cuda")
+    if device.type == "cuda" and not torch.cuda.is_available():
         out.print("[bold yellow]⚠️  CUDA requested but unavailable[/]: using CPU")
-        device_name = "cpu"
-    device = torch.device(device_name)
-
-    model = load_model(name, num_classes, _resolve_weights(infer_cfg, name, out), device, image_size)
-    if str(infer_cfg.get("fp8_weights", "")).lower() in ("1", "true", "yes", "on") and hasattr(model, "fp8_weights"):
-        model.fp8_weights = True       # extra key (FasterViT, with `amp: bf16`): Linear weights as MX fp8 on the scaled fp8 MFMA
+        device = torch.device("cpu")
     eval_toggles = resolve_transform_mapping(model_cfg, phase="eval")
-    transform = build_eval_transforms(image_size, toggles=eval_toggles)
-    device_pipeline = False
-    if str(infer_cfg.get("gpu_resize", "")).lower() in ("1", "true", "yes", "on") and device.type == "cuda":
-        # extra key: the workers only decode; Resize + CenterCrop + ToTensor + Normalize run on the device (bit-exact with the
-        # PIL pipeline above, tests/test_ops_gpu.py::test_resize_crop_matches_pillow_bit_for_bit).  The device pipeline IS the default
-        # eval pipeline: with any eval toggle switched off the results would silently differ from the PIL path, so it only engages
-        # when the resolved toggles are the defaults (ADVICE r3).
+    transform, gpu_resize = build_eval_transforms(image_size, toggles=eval_toggles), False
+    if str(infer_cfg.get("gpu_resize", "")).lower() in on and device.type == "cuda":
+        # The device pipeline (bit-exact with PIL, tests/test_ops_gpu.py::test_resize_crop_matches_pillow_bit_for_bit) IS the default
+        # eval pipeline: with an eval toggle off its results would silently differ, so it engages only under the default toggles.
         switched_off = sorted(k for k in ("ensure_rgb", "val_resize", "val_center_crop", "val_to_tensor", "val_normalize")
                               if not as_bool((eval_toggles or {}).get(k, True)))
         if switched_off:
             out.print(f"[bold yellow]inference.gpu_resize ignored[/]: eval toggles {switched_off} are off; the PIL pipeline honours them")
         else:
             transform = D.Compose([D.Lambda(_to_rgb), D.PlanGeometry("center", image_size, image_size)])
-            device_pipeline = True
+            gpu_resize = True
     root = Path(data_cfg.get("root")).expanduser()
-    if not root.is_absolute():
-        root = (Path.cwd() / root).resolve()
-    # extra key: probabilities, predictions and targets stay on the device (metrics.ScoreBook) and AUC, EER, the threshold sweep
-    # and the confusion matrix come from the exact counting kernels; off (the default): the host path below, unchanged
     device_metrics = as_bool(infer_cfg.get("device_metrics", False))
     if device_metrics and device.type != "cuda":
         out.print("[bold yellow]inference.device_metrics ignored[/]: needs a CUDA device; the host metrics run")
         device_metrics = False
-    if device_metrics:
-        from ..metrics import ScoreBook
-    # extra key: the passes keep their logits too; one temperature T (fitted on the validation split, or given) rescales them
-    # and ECE / MCE / Brier / NLL of the rescaled probabilities join every record (metrics.calibration, csrc/dfd_calib.hip)
-    calib = calibration_settings(infer_cfg)
-    if calib is not None and not device_metrics:
+    calibration = calibration_settings(infer_cfg)
+    if calibration is not None and not device_metrics:
         out.print("[bold yellow]inference.calibration ignored[/]: needs inference.device_metrics on a CUDA device")
-        calib = None
-    temperature, calib_doc = 1.0, None
-    if calib is not None:
-        calib_doc = {"temperature": 1.0, "bins": calib[0], "fitted_on": None, "n": 0, "nll_before": None, "nll_after": None}
-        if calib[1] != "fit":
-            temperature = float(calib[1])
+        calibration = None
+    levels = robustness_levels(infer_cfg)
+    if levels and not gpu_resize:           # the perturbation is applied to the cropped uint8 batch of the device pipeline
+        out.print("[bold yellow]inference.robustness skipped[/]: needs inference.gpu_resize on a CUDA device")
+        levels = []
+    elif image_size * image_size > BLUR_MAX_PIXELS and any(kind == "blur_sigma" for kind, _ in levels):
+        out.print(f"[bold yellow]inference.robustness blur_sigma skipped[/]: dfd_blur_u8 takes at most {BLUR_MAX_PIXELS} pixels")
+        levels = [(kind, level) for kind, level in levels if kind != "blur_sigma"]
+    limit = cam_limit(infer_cfg)
+    if limit is not None and device.type != "cuda":
+        out.print("[bold yellow]inference.cam skipped[/]: Grad-CAM runs on the HIP device only")
+        limit = None
+    return InferenceSettings(
+        name=name, root=root if root.is_absolute() else (Path.cwd() / root).resolve(), split=split,
+        val_split=str(data_cfg.get("val_split", "val")), num_classes=int(model_cfg.get("num_classes", data_cfg.get("num_classes", 2))),
+        image_size=image_size, batch_size=batch_size, num_workers=int(infer_cfg.get("num_workers", 4)),
+        amp=str(infer_cfg.get("amp", "")).lower() in ("bf16", "bfloat16", "true", "1"), device=device,
+        fp8_weights=str(infer_cfg.get("fp8_weights", "")).lower() in on, transform=transform,
+        device_metrics=device_metrics, calibration=calibration, robustness=tuple(levels), cam_limit=limit)
 
-    def forward(images, tail=None):
-        """(probabilities, arg-max, the logits under inference.calibration or None) of one batch."""
-        if calib is not None:
-            return class_probabilities(model, images, device, amp, tail=tail, return_logits=True)
-        return (*class_probabilities(model, images, device, amp, tail=tail), None)
 
+def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: dict[str, Any], run_paths: RunPaths) -> None:
+    tty = getattr(sys.stdout, "isatty", None)
+    out = Console(file=sys.stdout, force_terminal=bool(tty()) if callable(tty) else False)
+    s = inference_settings(config, model_cfg, out)
+    model = load_model(s.name, s.num_classes, _resolve_weights(model_cfg.get("inference") or {}, s.name, out), s.device, s.image_size)
+    if s.fp8_weights and hasattr(model, "fp8_weights"):
+        model.fp8_weights = True
+    calib = _Calibration(*s.calibration) if s.calibration is not None else None
     threshold = 0.5
-    if num_classes == 2 or (calib is not None and calib[1] == "fit"):
-        val_dir = root / data_cfg.get("val_split", "val")
-        val_seen = False
-        if val_dir.exists():
-            val_set = D.ImageFolder(val_dir, transform=transform)
-            if len(val_set) > 0 and device_metrics:
-                val_seen = True
-                book = ScoreBook(len(val_set), num_classes, device, keep_logits=calib is not None)
-                for images, targets in build_inference_loader(dataset=val_set, batch_size=batch_size, num_workers=num_workers):
-                    probs, _, logits = forward(images)
-                    book.append(probs, None, targets.to(device, non_blocking=True), logits=logits)
-                if calib is not None and calib[1] == "fit":
-                    from ..metrics import fit_temperature
+    if s.num_classes == 2 or (calib is not None and calib.mode == "fit"):
+        val_dir = s.root / s.val_split
+        val_set = D.ImageFolder(val_dir, transform=s.transform) if val_dir.exists() else ()
+        val_book = _score_pass(model, val_set, s) if len(val_set) > 0 else None
+        if calib is not None:
+            calib.fit(val_book, s.val_split, out)
+        if val_book is not None and s.num_classes == 2:
+            threshold = _first_set(_validation_threshold(val_book), threshold)
+        del val_book                                    # its device buffers go before the split's own book is made
 
-                    fit = fit_temperature(book.logits, book.targets)
-                    calib_doc.update(fitted_on=str(data_cfg.get("val_split", "val")), n=book.count, nll_before=fit.nll_before,
-                                     nll_after=fit.nll_after)
-                    if fit.at_bound:
-                        out.print(f"[bold yellow]inference.calibration[/]: the fitted temperature sits at its bound "
-                                  f"{fit.temperature:g}; T = 1 is used")
-                        calib_doc["temperature_fit"] = "at_bound"
-                    else:
-                        temperature = fit.temperature
-                if calib is not None:
-                    _calibrate_book(book, temperature, None)
-                if num_classes == 2:
-                    threshold = _first_set(_device_threshold(book), threshold)
-            elif len(val_set) > 0:
-                scores, truth = [], []
-                for images, targets in build_inference_loader(dataset=val_set, batch_size=batch_size, num_workers=num_workers):
-                    probs, _ = class_probabilities(model, images, device, amp)
-                    scores.append(probs[:, 1].cpu())
-                    truth.append(targets.cpu())
-                s, t = torch.cat(scores).numpy(), torch.cat(truth).numpy()
-                if s.size and np.unique(t).size > 1:
-                    threshold = best_balanced_accuracy_threshold(s, t)
-        if calib is not None and calib[1] == "fit" and not val_seen:
-            out.print("[bold yellow]inference.calibration[/]: no validation split to fit the temperature on; T = 1 is used")
-            calib_doc["temperature_fit"] = "unavailable"
-    if calib_doc is not None:
-        calib_doc["temperature"] = float(temperature)
-
-    split_dir = root / split
+    split_dir = s.root / s.split
     if not split_dir.exists():
         out.print(f"[bold red]Split not found:[/] {split_dir}")
         raise SystemExit(1)
-    dataset = D.ImageFolder(split_dir, transform=transform)
-    require_num_classes(dataset, num_classes, split=split, dataset_root=split_dir)
+    dataset = D.ImageFolder(split_dir, transform=s.transform)
+    require_num_classes(dataset, s.num_classes, split=s.split, dataset_root=split_dir)
     if len(dataset) == 0:
         out.print(f"[bold yellow]No images found in[/] {split_dir}")
         return
-    loader = build_inference_loader(dataset=dataset, batch_size=batch_size, num_workers=num_workers)
     progress = Progress(TextColumn("[bold blue]{task.description}"), BarColumn(bar_width=None), MofNCompleteColumn(),
                         TimeElapsedColumn(), TimeRemainingColumn(), TextColumn("{task.fields[speed]}"), console=out)
-    all_probs, all_preds, all_targets = [], [], []
-    book = ScoreBook(len(dataset), num_classes, device, keep_logits=calib is not None) if device_metrics else None
-    seen, start = 0, perf_counter()
-    with progress:
-        task = progress.add_task("inference", total=len(loader), speed="")
-        for images, targets in loader:
-            probs, preds, logits = forward(images)
-            if book is not None:
-                book.append(probs, preds, targets.to(device, non_blocking=True), logits=logits)     # no host round trip per batch
-            else:
-                all_probs.append(probs.cpu())
-                all_preds.append(preds.cpu())
-                all_targets.append(targets.cpu())
-            seen += targets.size(0)
-            progress.update(task, advance=1, speed=f"{seen / max(perf_counter() - start, 1e-6):.1f} img/s")
-
-    roc = reliability = None
+    book = _score_pass(model, dataset, s, progress=progress)            # one book for this pass and every level below
+    clean = _judge(s, book, threshold, calib, clean=True)
     if calib is not None:
-        from .. import metrics as M
-
-        raw = M.calibration(book.probs, book.targets, calib[0])                        # softmax at T = 1, as the pass left it
-        raw_figures = {"ece": raw.ece, "mce": raw.mce, "brier": raw.brier, "nll": M.mean_nll(book.logits, book.targets, 1.0)}
-        figures, calibrated = _calibrate_book(book, temperature, calib[0])
-        metrics, probs_t, preds_t, targets_t, cm, roc = _split_metrics_device(name, split, book, num_classes, threshold)
-        metrics.update(figures)
-        metrics["uncalibrated"] = raw_figures
-        if "temperature_fit" in calib_doc:
-            metrics["temperature_fit"] = calib_doc["temperature_fit"]
-        reliability = (temperature, raw, calibrated)
-        (run_paths.run_dir / "calibration.json").write_text(json.dumps(calib_doc, indent=2) + "\n", encoding="utf-8")
-    elif book is not None:
-        metrics, probs_t, preds_t, targets_t, cm, roc = _split_metrics_device(name, split, book, num_classes, threshold)
-    else:
-        probs_t, preds_t, targets_t = torch.cat(all_probs), torch.cat(all_preds), torch.cat(all_targets)
-        metrics, preds_t, cm = _split_metrics(name, split, probs_t, preds_t, targets_t, num_classes, threshold)
-    accuracy = metrics["accuracy"]
-    truth_np = targets_t.numpy()
-    multi_label = torch.unique(targets_t).numel() > 1
-    _save_plots(cm, list(dataset.classes), truth_np, probs_t[:, 1].numpy() if num_classes == 2 and multi_label else None,
-                run_paths.plots, roc=roc, reliability=reliability)
-    with (run_paths.logs / "metrics.jsonl").open("a", encoding="utf-8") as handle:
-        handle.write(json.dumps(metrics) + "\n")
-    extras = " ".join(f"{k}={v:.4f}" for k, v in metrics.items() if isinstance(v, float) and k != "accuracy")
-    out.print(f"[bold]Accuracy[/]: {accuracy:.4f} {extras}")
-    levels = robustness_levels(infer_cfg)
-    if levels and not device_pipeline:
-        # the perturbation is applied to the cropped uint8 batch on the device, which only the device pipeline has
-        out.print("[bold yellow]inference.robustness skipped[/]: needs inference.gpu_resize on a CUDA device")
-    elif levels:
-        from .._lib import BLUR_MAX_PIXELS
-
-        if image_size * image_size > BLUR_MAX_PIXELS and any(kind == "blur_sigma" for kind, _ in levels):
-            out.print(f"[bold yellow]inference.robustness blur_sigma skipped[/]: dfd_blur_u8 takes at most {BLUR_MAX_PIXELS} pixels")
-            levels = [(kind, level) for kind, level in levels if kind != "blur_sigma"]
-        for kind, level in levels:
-            tail = robustness_tail(kind, level)
-            level_probs, level_preds = [], []
-            if book is not None:
-                book.reset()
-            for images, targets in build_inference_loader(dataset=dataset, batch_size=batch_size, num_workers=num_workers):
-                probs, preds, logits = forward(images, tail)
-                if book is not None:
-                    book.append(probs, preds, targets.to(device, non_blocking=True), logits=logits)
-                else:
-                    level_probs.append(probs.cpu())
-                    level_preds.append(preds.cpu())
-            if calib is not None:
-                figures = _calibrate_book(book, temperature, calib[0])[0]
-                perturbed = _split_metrics_device(name, split, book, num_classes, threshold)[0]
-                perturbed.update(figures)
-            elif book is not None:
-                perturbed = _split_metrics_device(name, split, book, num_classes, threshold)[0]
-            else:
-                perturbed, _, _ = _split_metrics(name, split, torch.cat(level_probs), torch.cat(level_preds), targets_t, num_classes,
-                                                 threshold)                     # judged at the clean pass's threshold
-            perturbed["perturbation"] = {kind: level}
-            with (run_paths.logs / "metrics.jsonl").open("a", encoding="utf-8") as handle:
-                handle.write(json.dumps(perturbed) + "\n")
-            extras = " ".join(f"{k}={v:.4f}" for k, v in perturbed.items() if isinstance(v, float) and k != "accuracy")
-            out.print(f"[bold]Robustness[/] {kind}={level:g}: accuracy {perturbed['accuracy']:.4f} {extras}")
-    limit = cam_limit(infer_cfg)
-    if limit is not None:
-        if device.type != "cuda":
-            out.print("[bold yellow]inference.cam skipped[/]: Grad-CAM runs on the HIP device only")
-        else:
-            count = write_cam_overlays(model, dataset, probs_t, preds_t, limit, run_paths.run_dir / "cam",
-                                       batch_size=batch_size, num_workers=num_workers)
-            out.print(f"[bold]Grad-CAM[/]: {count} overlays in {run_paths.run_dir / 'cam'}")
+        calib.write(run_paths.run_dir)
+    scores = clean.probs[:, 1].numpy() if s.num_classes == 2 and torch.unique(clean.targets).numel() > 1 else None
+    _save_plots(clean.cm, list(dataset.classes), clean.targets.numpy(), scores, run_paths.plots, roc=clean.roc,
+                reliability=clean.reliability)
+    _emit(clean.record, run_paths, out, "[bold]Accuracy[/]:")
+    for kind, level in s.robustness:
+        _score_pass(model, dataset, s, book, tail=robustness_tail(kind, level))
+        perturbed = _judge(s, book, threshold, calib).record        # at the clean pass's threshold and temperature
+        perturbed["perturbation"] = {kind: level}
+        _emit(perturbed, run_paths, out, f"[bold]Robustness[/] {kind}={level:g}: accuracy")
+    if s.cam_limit is not None:
+        count = write_cam_overlays(model, dataset, clean.probs, clean.preds, s.cam_limit, run_paths.run_dir / "cam",
+                                   batch_size=s.batch_size, num_workers=s.num_workers)
+        out.print(f"[bold]Grad-CAM[/]: {count} overlays in {run_paths.run_dir / 'cam'}")
 
 
 def orchestrate(config_path: Path, *, mode: str) -> None:

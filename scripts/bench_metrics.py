@@ -10,8 +10,8 @@ One JSON line per size; `--out` appends them to a file (profiles/metrics_eval.js
            dfd_confusion: `--reps` eager repetitions between two device events, per round; the same captured into one graph and
            replayed (null when the capture is refused); and the sort + gather alone.  Nothing in it reads back: the one transfer
            of the results (stats, 2 x 501 counts, 4 cells) is timed apart as `readback_ms`.
-  host     what orchestrator._run_inference_job does without inference.device_metrics: one .cpu() of the probabilities, the
-           predictions and the targets per batch of `--batch` (a synchronisation each), then _split_metrics (sklearn's
+  host     what the orchestrator's inference job does without inference.device_metrics: one blocking copy of the probabilities,
+           the predictions and the targets per batch of `--batch` into a host metrics.ScoreBook, then _split_metrics (sklearn's
            roc_auc_score where sklearn is present, and the Python loop of confusion_counts) and the [501, n] numpy sweep of
            best_balanced_accuracy_threshold.  Host clock, `--host-rounds` rounds.
 """
@@ -110,6 +110,7 @@ def part_device(n: int, args) -> dict:
 
 
 def part_host(n: int, args) -> dict:
+    from deepfakedetection_amd.metrics import ScoreBook
     from deepfakedetection_amd.orchestration import orchestrator as O
 
     try:
@@ -124,12 +125,10 @@ def part_host(n: int, args) -> dict:
     auc = None
     for _ in range(args.host_rounds):
         t0 = perf_counter()
-        all_probs, all_preds, all_targets = [], [], []
+        book = ScoreBook(n, 2, "cpu")
         for i in range(0, n, args.batch):
-            all_probs.append(probs[i:i + args.batch].cpu())
-            all_preds.append(preds[i:i + args.batch].cpu())
-            all_targets.append(targets[i:i + args.batch].cpu())
-        probs_t, preds_t, targets_t = torch.cat(all_probs), torch.cat(all_preds), torch.cat(all_targets)
+            book.append(probs[i:i + args.batch], preds[i:i + args.batch], targets[i:i + args.batch])
+        probs_t, preds_t, targets_t = book.probs, book.preds, book.targets
         t1 = perf_counter()
         record, _, _ = O._split_metrics("bench", "test", probs_t, preds_t, targets_t, 2, 0.5)
         t2 = perf_counter()

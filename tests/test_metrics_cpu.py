@@ -226,12 +226,18 @@ def test_selection_follows_the_chosen_metric():
 
 
 def test_inference_switch_defaults_to_off_and_warns_off_device():
-    import inspect
+    import io
+
+    from rich.console import Console
 
     from deepfakedetection_amd.orchestration import orchestrator as O
 
-    src = inspect.getsource(O._run_inference_job)
-    assert 'infer_cfg.get("device_metrics", False)' in src and "inference.device_metrics ignored" in src
+    config = {"device": "cpu", "data": {"root": "data", "num_classes": 2}}
+    for infer, want_warning in (({}, False), ({"device_metrics": False}, False), ({"device_metrics": True}, True)):
+        text = io.StringIO()
+        settings = O.inference_settings(config, {"name": "efficientnet_b0", "inference": infer}, Console(file=text, width=200))
+        assert settings.device_metrics is False and settings.device == torch.device("cpu")
+        assert ("inference.device_metrics ignored" in text.getvalue()) == want_warning
 
 
 @pytest.fixture(scope="module")

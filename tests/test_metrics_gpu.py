@@ -291,24 +291,24 @@ def test_confusion_leaves_out_of_range_labels_out(J):
 
 
 # ------------------------------------------------------------------ end to end
-def _write_pngs(root: Path) -> None:
+def _write_pngs(root: Path, classes=("fake", "real")) -> None:
     rng = np.random.default_rng(5)
     for split in ("val", "test"):
-        for cls in ("fake", "real"):
+        for cls in classes:
             folder = root / split / cls
             folder.mkdir(parents=True)
             for i in range(4):
                 Image.fromarray(rng.integers(0, 256, size=(24, 24, 3), dtype=np.uint8)).save(folder / f"{cls}_{i}.png")
 
 
-def _config(tmp_path: Path, out: str, device_metrics: bool) -> Path:
+def _config(tmp_path: Path, out: str, device_metrics: bool, num_classes: int = 2) -> Path:
     import yaml
 
     infer = {"split": "test", "batch_size": 8, "num_workers": 0, "img_size": 64, "gpu_resize": True, "robustness": {"blur_sigma": [2]}}
     if device_metrics:
         infer["device_metrics"] = True
     cfg = {"seed": 1, "device": "cuda",
-           "data": {"root": str(tmp_path / "data"), "val_split": "val", "test_split": "test", "num_classes": 2, "img_size": 64},
+           "data": {"root": str(tmp_path / "data"), "val_split": "val", "test_split": "test", "num_classes": num_classes, "img_size": 64},
            "models": {"efficientnet_b0": {"output_dir": str(tmp_path / out), "inference": infer}}, "selection": ["efficientnet_b0"]}
     path = tmp_path / f"{out}.yaml"
     path.write_text(yaml.safe_dump(cfg))
@@ -352,6 +352,31 @@ def test_inference_with_device_metrics(tmp_path, monkeypatch):
     assert len(sweeps) == 1 and sweeps[0] == rows[0]["threshold"]                      # the validation sweep ran on the device
     (run,) = [p for p in (tmp_path / "device").iterdir() if p.is_dir()]
     assert (run / "plots" / "roc_curve.png").exists()
+
+
+def test_three_class_inference_agrees_between_host_and_device(tmp_path, monkeypatch):
+    """Above two classes there is no threshold and no validation pass; the AUC is the macro one-vs-rest mean."""
+    from deepfakedetection_amd.orchestration import orchestrator as O
+
+    _write_pngs(tmp_path / "data", classes=("a", "b", "c"))
+    O.orchestrate(_config(tmp_path, "plain", False, 3), mode="inference")
+    books = []
+    real = O._split_metrics_device
+    monkeypatch.setattr(O, "_split_metrics_device",
+                        lambda name, split, book, J, thr: (books.append((book.probs.cpu().numpy().copy(), book.targets.cpu().numpy().copy())),
+                                                           real(name, split, book, J, thr))[1])
+    O.orchestrate(_config(tmp_path, "device", True, 3), mode="inference")
+    plain, rows = _rows(tmp_path / "plain"), _rows(tmp_path / "device")
+    assert len(plain) == len(rows) == 2 == len(books)
+    for before, after, (probs, truth) in zip(plain, rows, books):
+        assert "threshold" not in before and "threshold" not in after
+        assert before.get("perturbation") == after.get("perturbation")
+        for key in ("accuracy", "confusion_matrix"):
+            assert after[key] == before[key], key
+        assert probs.shape == (12, 3) and sorted(set(truth.tolist())) == [0, 1, 2]      # every class occurs: the AUC is defined
+        assert after["roc_auc"] == sum(R.auc(probs[:, j], truth, positive=j) for j in range(3)) / 3
+        assert after["eer"] is not None and after["balanced_accuracy"] is not None
+    assert rows[1]["perturbation"] == {"blur_sigma": 2.0} and "perturbation" not in rows[0]
 
 
 class _Recording(torch.nn.Module):

@@ -64,7 +64,7 @@ def test_eval_logits_f32(variant, flavour, size):
         want = ref(x)
     with torch.inference_mode():
         got_cl = hip(x.cuda().to(memory_format=torch.channels_last))     # training-style input
-        got_nchw = hip(x.cuda())                                          # inference-style input (orchestrator.py:588)
+        got_nchw = hip(x.cuda())                                          # inference-style input (orchestrator.class_probabilities)
     assert rel_err(got_cl, want) <= 1e-3, rel_err(got_cl, want)            # north_star: logits within 1e-3 rel f32
     assert torch.equal(got_cl.cpu(), got_nchw.cpu())
     assert torch.equal(got_cl.argmax(1).cpu(), want.argmax(1))            # bit-exact class indices
