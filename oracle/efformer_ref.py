@@ -233,10 +233,13 @@ class Block(nn.Module):
         self.ls2 = Scale(dim)
         self.dp = dp
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, masks=None) -> torch.Tensor:
+        """masks: optional (token-mixer, MLP) per-sample DropPath scales to use instead of drawing them (tests inject the
+        engine's); they apply wherever a drawn mask would (training mode, dp > 0)."""
+        m1, m2 = masks if masks is not None else (None, None)
         if self.token_mixer is not None:
-            x = x + drop_path(self.ls1(self.token_mixer(x)), self.dp, self.training)
-        return x + drop_path(self.ls2(self.mlp(x)), self.dp, self.training)
+            x = x + drop_path(self.ls1(self.token_mixer(x)), self.dp, self.training, m1)
+        return x + drop_path(self.ls2(self.mlp(x)), self.dp, self.training, m2)
 
 
 class Stage(nn.Module):

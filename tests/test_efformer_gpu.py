@@ -266,6 +266,39 @@ def test_bf16_autocast_step_and_reproducibility():
         assert cos >= 0.97, f"{name}: cosine {cos:.4f}"
 
 
+def test_bf16_autocast_step_with_drop_path_and_reproducibility():
+    """S2 with the package's own drop-path rate (0.02): the engine's Philox masks reach the logits (they differ from the same
+    weights without DropPath), and the same step from the same Philox state gives the same bits."""
+    Hip, _, _, HipCE = _imports()
+    g = torch.Generator().manual_seed(2)
+    x, y = torch.randn(4, 3, 224, 224, generator=g).cuda(), torch.randint(0, 2, (4,), generator=g).cuda()
+
+    def steps(hip, count):
+        outs = []
+        for _ in range(count):
+            hip.rng(x.device).reseed(0)                  # the same masks again: a step advances the Philox offset
+            hip.zero_grad(set_to_none=True)
+            with torch.autocast("cuda", dtype=torch.bfloat16):
+                logits = hip(x)
+                loss = HipCE(0.1)(logits, y)
+            loss.backward()
+            assert torch.isfinite(loss).item() and all(torch.isfinite(p.grad).all() for p in hip.parameters())
+            outs.append((logits.detach().clone(), hip.stages[3].blocks[7].mlp.fc1.conv.weight.grad.clone(),
+                         hip.stages[2].blocks[8].token_mixer.attention_biases.grad.clone()))
+        return outs
+
+    torch.manual_seed(0)
+    hip = Hip("s2", 2)
+    randomise(hip, 3)                                    # LayerScale O(0.3): the branches DropPath scales are visible
+    assert hip.stages[3].blocks[7].drop_path == pytest.approx(0.02) and hip.stages[0].blocks[1].drop_path > 0
+    first, second = steps(hip.cuda().train(), 2)
+    assert all(torch.equal(a, b) for a, b in zip(first, second))
+    plain = Hip("s2", 2, drop_path_rate=0.0)
+    plain.load_state_dict(hip.state_dict())
+    (without,) = steps(plain.cuda().train(), 1)
+    assert not torch.equal(first[0], without[0])
+
+
 def test_refuses_cpu_and_wrong_resolution():
     Hip, _, _, _ = _imports()
     m = Hip("s1", 2, 224)
