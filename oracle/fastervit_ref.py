@@ -91,7 +91,8 @@ class PosEmb1D(nn.Module):
 
     def table(self, seq_length: int) -> torch.Tensor:
         s = int(seq_length ** 0.5)
-        ar = torch.arange(0, s, dtype=torch.float32, device=self.cpb_mlp[0].weight.device)
+        w = self.cpb_mlp[0].weight                                                   # f32; float64 where a test casts the module
+        ar = torch.arange(0, s, dtype=w.dtype, device=w.device)
         grid = torch.stack(torch.meshgrid([ar, ar], indexing="ij")).unsqueeze(0)      # [1, 2, s, s]
         grid = (grid - s // 2) / (s // 2)
         return self.cpb_mlp(grid.flatten(2).transpose(1, 2))                         # [1, s*s, dim]
