@@ -55,6 +55,17 @@ CALIB_MAX_BLOCKS = 1024             # stage-1 workgroups at most
 CALIB_STAGE2_WIDTH = 64             # partials the stage-2 loop takes per trip
 CALIB_LAYOUT_THREAD, CALIB_LAYOUT_WAVE = 0, 1
 (CALIB_VALID, CALIB_NONFINITE, CALIB_OOB, CALIB_CORRECT) = range(4)
+# csrc/dfd_fuse.hip (the DFD_FUSE_* constants of include/dfd_hip.h)
+FUSE_MAX_MODELS = 8
+FUSE_MAX_CANDS = 8
+FUSE_MAX_J = 1024
+FUSE_MAX_N = 1 << 28
+FUSE_MAX_TERMS = 45                 # nll + K gradient entries + the K (K + 1) / 2 of the Hessian's upper triangle at K = 8
+FUSE_THREAD_MAX_KJ = 16             # largest K * J that one thread takes; above it one wave per row
+FUSE_MAX_BLOCKS = 1024              # stage-1 workgroups at most
+FUSE_STAGE2_WIDTH = 64              # partials the stage-2 loop takes per trip
+FUSE_LAYOUT_THREAD, FUSE_LAYOUT_WAVE = 0, 1
+FUSE_LOGIT, FUSE_PROB = 0, 1
 
 
 class DwShape(Structure):
@@ -164,6 +175,12 @@ SIGNATURES: dict[str, tuple] = {
     "dfd_calib_nll": (c_int, [P, P, c_int, c_int, POINTER(c_double), c_int, P, c_size_t, P, P, P]),
     "dfd_calib_plan": (c_int, [c_int, c_int, _PI]),
     "dfd_softmax_argmax_t": (c_int, [P, c_int, c_int, c_float, P, P, P]),
+    # ---- ABI 151
+    "dfd_fuse_scores": (c_int, [P, c_int, c_int, c_int, c_int, POINTER(c_double), POINTER(c_double), P, P, P, P, P]),
+    "dfd_fuse_nll_ws": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dfd_fuse_nll": (c_int, [P, c_int, P, c_int, c_int, POINTER(c_double), c_int, P, c_size_t, P, P, P]),
+    "dfd_fuse_agree": (c_int, [P, c_int, P, c_int, c_int, P, P, P, P]),
+    "dfd_fuse_plan": (c_int, [c_int, c_int, c_int, _PI]),
     # ---- ABI 111
     "dfd_bn_eval_coeffs_multi": (c_int, [P, c_int, P]),
     "dfd_sum_batch_begin": (c_int, []),

@@ -1394,6 +1394,133 @@ def softmax_argmax_t(logits: torch.Tensor, inv_temperature: float, want_probs: b
     return probs, preds
 
 
+# ------------------------------------------------------------------ the ensemble (ABI 151, csrc/dfd_fuse.hip)
+FUSE_MAX_MODELS, FUSE_MAX_CANDS, FUSE_MAX_J, FUSE_MAX_N = _lib.FUSE_MAX_MODELS, _lib.FUSE_MAX_CANDS, _lib.FUSE_MAX_J, _lib.FUSE_MAX_N
+FUSE_THREAD_MAX_KJ, FUSE_MAX_BLOCKS, FUSE_STAGE2_WIDTH = _lib.FUSE_THREAD_MAX_KJ, _lib.FUSE_MAX_BLOCKS, _lib.FUSE_STAGE2_WIDTH
+FUSE_LAYOUT_THREAD, FUSE_LAYOUT_WAVE, FUSE_LOGIT, FUSE_PROB = _lib.FUSE_LAYOUT_THREAD, _lib.FUSE_LAYOUT_WAVE, _lib.FUSE_LOGIT, _lib.FUSE_PROB
+
+
+@dataclass(frozen=True)
+class FusePlan:
+    """dfd_fuse_plan's answer: the row layout, the rows a workgroup takes per trip, the stage-1 workgroups and the trips of
+    fuse_nll's stage-2 loop at (n, J, K)."""
+
+    layout: int
+    rows: int
+    blocks: int
+    trips: int
+
+
+def fuse_terms(K: int) -> int:
+    """The f64 results per candidate of fuse_nll: the NLL, K gradient entries and the upper triangle of the Hessian."""
+    return 1 + K + K * (K + 1) // 2
+
+
+def _fuse_members(op: str, members, dtype: torch.dtype, dim: int):
+    """The K buffers of one shape, dtype and device -> (the list, the array of their addresses through the gate)."""
+    members = list(members)
+    K = len(members)
+    if not 1 <= K <= FUSE_MAX_MODELS:
+        raise ValueError(f"{op}: takes 1..{FUSE_MAX_MODELS} members, got {K}")
+    first = members[0]
+    for m in members:
+        if m.dim() != dim or m.dtype != dtype or m.shape != first.shape or m.device != first.device:
+            raise ValueError(f"{op}: every member must be {dtype} with {dim} dimensions, one shape and one device, got "
+                             f"{[(m.dtype, tuple(m.shape)) for m in members]}")
+    n = first.shape[0]
+    if not 0 <= n <= FUSE_MAX_N or (dim == 2 and not 1 <= first.shape[1] <= FUSE_MAX_J):
+        raise ValueError(f"{op}: takes 0..{FUSE_MAX_N} rows of 1..{FUSE_MAX_J} classes, got {tuple(first.shape)}")
+    return members, (ctypes.c_void_p * K)(*[_p(m) for m in members])
+
+
+def _fuse_targets(op: str, targets: torch.Tensor, n: int) -> None:
+    if targets.dtype != torch.int64 or tuple(targets.shape) != (n,):
+        raise ValueError(f"{op}: expected int64 [{n}] targets, got {targets.dtype} {tuple(targets.shape)}")
+
+
+def fuse_plan(n: int, J: int, K: int) -> FusePlan:
+    """Which layout and launch shape fuse_scores / fuse_nll use for n rows of J classes from K members (host code)."""
+    out = (ctypes.c_int * 4)()
+    check(_L().dfd_fuse_plan(int(n), int(J), int(K), out), "dfd_fuse_plan", f"n={n} J={J} K={K}")
+    return FusePlan(*out)
+
+
+def fuse_nll_ws(n: int, J: int, K: int, C: int) -> int:
+    """Bytes of workspace fuse_nll needs for n rows of J classes from K members at C candidates."""
+    if not 0 <= n <= FUSE_MAX_N or not 1 <= J <= FUSE_MAX_J or not 1 <= K <= FUSE_MAX_MODELS or not 1 <= C <= FUSE_MAX_CANDS:
+        raise ValueError(f"fuse_nll takes 0..{FUSE_MAX_N} rows of 1..{FUSE_MAX_J} classes from 1..{FUSE_MAX_MODELS} members at "
+                         f"1..{FUSE_MAX_CANDS} candidates, got [{n}, {J}], {K}, {C}")
+    return _L().dfd_fuse_nll_ws(n, J, K, C)
+
+
+def fuse_scores(logits_list, coef, mode: int = FUSE_LOGIT, beta=None, want_probs: bool = True, want_logits: bool = True, out=None):
+    """K f32 [n, J] logit buffers, K host coefficients (and, in FUSE_PROB mode, K inverse temperatures beta > 0) -> (probs f32
+    [n, J] or None, preds int64 [n], fused logits f32 [n, J] or None, stats int64 [1] = rows with a non-finite logit, which
+    hold NaN and pred 0): include/dfd_hip.h.  FUSE_LOGIT: softmax(sum_k coef_k z_k); FUSE_PROB: sum_k coef_k softmax(beta_k z_k),
+    coef_k >= 0 summing to 1.  f64 arithmetic, rounded once on store; two launches, no host sync.  `out`: (probs, preds, logits,
+    stats) destinations, a None among the first three taken by want_probs / want_logits."""
+    members, ptrs = _fuse_members("fuse_scores", logits_list, torch.float32, 2)
+    K = len(members)
+    n, J = members[0].shape
+    values = [float(c) for c in coef]
+    betas = [1.0] * K if beta is None else [float(b) for b in beta]
+    if mode not in (FUSE_LOGIT, FUSE_PROB) or len(values) != K or len(betas) != K or not all(math.isfinite(v) for v in values + betas):
+        raise ValueError(f"fuse_scores: expected mode 0 or 1 and {K} finite coefficients (and betas), got {mode}, {values}, {betas}")
+    if mode == FUSE_PROB and (min(values) < 0.0 or abs(math.fsum(values) - 1.0) > 1e-12 or min(betas) <= 0.0):
+        raise ValueError(f"fuse_scores: the probability pool takes coefficients >= 0 that sum to 1 and betas > 0, got {values}, {betas}")
+    device = members[0].device
+    o_probs, o_preds, o_logits, o_stats = out if out is not None else (None, None, None, None)
+    probs = _dst(o_probs, (n, J), device) if want_probs or o_probs is not None else None
+    fused = _dst(o_logits, (n, J), device) if want_logits or o_logits is not None else None
+    preds = _dst(o_preds, (n,), device, torch.int64)
+    stats = _dst(o_stats, (1,), device, torch.int64)
+    check(_L().dfd_fuse_scores(ptrs, K, n, J, mode, (ctypes.c_double * K)(*values), (ctypes.c_double * K)(*betas), _p(probs), _p(fused),
+                               _p(preds), _p(stats), _stream()), "dfd_fuse_scores", f"n={n} J={J} K={K} mode={mode}")
+    return probs, preds, fused, stats
+
+
+def fuse_nll(logits_list, targets: torch.Tensor, cands, ws: torch.Tensor | None = None, out=None):
+    """K f32 [n, J] logit buffers, int64 [n] targets and C <= FUSE_MAX_CANDS host coefficient vectors of length K -> (out f64
+    [C, fuse_terms(K)] = per candidate the summed NLL of softmax(sum_k a_k z_k), its gradient in a and the upper triangle of its
+    Hessian, row by row, stats int64 [2] = nonfinite / out-of-range rows, which the sums leave out): include/dfd_hip.h.  Two
+    launches, no host sync.  The addresses and the candidates travel by value in the launch."""
+    members, ptrs = _fuse_members("fuse_nll", logits_list, torch.float32, 2)
+    K = len(members)
+    n, J = members[0].shape
+    _fuse_targets("fuse_nll", targets, n)
+    rows = [[float(v) for v in cand] for cand in cands]
+    C = len(rows)
+    if not 1 <= C <= FUSE_MAX_CANDS or any(len(r) != K or not all(math.isfinite(v) for v in r) for r in rows):
+        raise ValueError(f"fuse_nll: expected 1..{FUSE_MAX_CANDS} candidates of {K} finite coefficients, got {rows}")
+    device = members[0].device
+    ws = _calib_ws("fuse_nll", ws, fuse_nll_ws(n, J, K, C), device)
+    o_out, o_stats = out if out is not None else (None, None)
+    sums = _dst(o_out, (C, fuse_terms(K)), device, torch.float64)
+    stats = _dst(o_stats, (2,), device, torch.int64)
+    flat = [v for r in rows for v in r]
+    check(_L().dfd_fuse_nll(ptrs, K, _p(targets), n, J, (ctypes.c_double * len(flat))(*flat), C, _p(ws), ws.numel(), _p(sums), _p(stats),
+                            _stream()), "dfd_fuse_nll", f"n={n} J={J} K={K} C={C}")
+    return sums, stats
+
+
+def fuse_agree(preds_list, targets: torch.Tensor, num_classes: int, out=None):
+    """K int64 [n] prediction buffers and int64 [n] targets -> (pair int64 [K, K, 4] = rows where members (a, b) are both right /
+    a right and b wrong / a wrong and b right / both wrong, hist int64 [K + 1] = rows by the number of members that are right,
+    stats int64 [2] = valid rows / rows whose target is outside [0, num_classes)).  Integers only; two launches, no host sync."""
+    members, ptrs = _fuse_members("fuse_agree", preds_list, torch.int64, 1)
+    K, n, J = len(members), members[0].shape[0], int(num_classes)
+    _fuse_targets("fuse_agree", targets, n)
+    if not 1 <= J <= FUSE_MAX_J:
+        raise ValueError(f"fuse_agree: num_classes must be 1..{FUSE_MAX_J}, got {J}")
+    device = members[0].device
+    o_pair, o_hist, o_stats = out if out is not None else (None, None, None)
+    pair = _dst(o_pair, (K, K, 4), device, torch.int64)
+    hist = _dst(o_hist, (K + 1,), device, torch.int64)
+    stats = _dst(o_stats, (2,), device, torch.int64)
+    check(_L().dfd_fuse_agree(ptrs, K, _p(targets), n, J, _p(pair), _p(hist), _p(stats), _stream()), "dfd_fuse_agree", f"n={n} J={J} K={K}")
+    return pair, hist, stats
+
+
 # ------------------------------------------------------------------ Grad-CAM (ABI 136)
 def gradcam_map(act: torch.Tensor, grad: torch.Tensor) -> torch.Tensor:
     """Target-layer activation and its gradient, NHWC [N, h, w, C] (f32 or bf16) -> the ReLU'd Grad-CAM map f32 [N, h, w]:

@@ -13,6 +13,12 @@ the single temperature T (Guo et al. 2017) that minimises the NLL of softmax(z /
 one launch evaluates it with its derivative for up to kernels.CALIB_MAX_BETAS values of beta, so the fit is a bracketing
 search with one read-back per round and no optimiser.
 
+`fuse` combines the logits of K models with csrc/dfd_fuse.hip: a log-linear pool softmax(sum_k a_k z_k) or a linear pool of the
+members' probabilities.  `fit_fusion` fits the a_k of the log-linear pool on held-out logits: the NLL is convex in a, one launch
+returns it with its gradient and Hessian for eight step lengths at once, so the fit is a damped Newton method with one read-back
+per iteration.  `diversity` counts how the members' right and wrong predictions coincide; every figure it returns is one division
+of Python integers.
+
 `ScoreBook` and `gather_scores` are plain torch (they run on the CPU and under gloo as well); the metrics themselves need a
 HIP device, like every kernel front end.
 """
@@ -26,8 +32,9 @@ import torch
 
 from . import kernels as K
 
-__all__ = ["CalibrationResult", "RocResult", "ScoreBook", "TemperatureFit", "apply_temperature", "binary_roc", "calibration", "confusion",
-           "eer_from_curve", "fit_temperature", "gather_scores", "mean_nll", "ovr_auc"]
+__all__ = ["CalibrationResult", "DiversityResult", "FusionFit", "RocResult", "ScoreBook", "TemperatureFit", "apply_temperature", "binary_roc",
+           "calibration", "confusion", "diversity", "eer_from_curve", "fit_fusion", "fit_temperature", "fuse", "gather_scores", "mean_nll",
+           "ovr_auc"]
 
 
 class ScoreBook:
@@ -348,6 +355,202 @@ def apply_temperature(logits: torch.Tensor, temperature: float) -> tuple[torch.T
     """(softmax(logits / temperature), its arg max) of f32 logits [n, J] on the device; at temperature 1 the bits of
     kernels.softmax_argmax."""
     return K.softmax_argmax_t(logits.detach().float().contiguous(), 1.0 / float(temperature))
+
+
+def _members(op: str, tensors, dtype: torch.dtype) -> list[torch.Tensor]:
+    members = [t.detach().to(dtype).contiguous() for t in tensors]
+    if not members:
+        raise ValueError(f"{op}: no members")
+    return members
+
+
+def fuse(logits_list, coef=None, mode: str = "logit", temperatures=None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(probabilities f32 [n, J], their first arg max int64 [n], fused logits f32 [n, J]) of K models' f32 logits [n, J] on the
+    device.  mode "logit": softmax(sum_k coef_k z_k / T_k), the log-linear pool; "prob": sum_k coef_k softmax(z_k / T_k), the
+    linear pool, whose logits are log p; coef_k >= 0 summing to 1 there.  coef: equal weights 1 / K by default.  temperatures: one
+    per member (None entries and None itself: 1).  A row with a non-finite logit in any member holds NaN and predicts 0."""
+    if mode not in ("logit", "prob"):
+        raise ValueError(f"fuse: mode must be logit or prob, got {mode!r}")
+    members = _members("fuse", logits_list, torch.float32)
+    count = len(members)
+    coef = [1.0 / count] * count if coef is None else [float(c) for c in coef]
+    betas = [1.0 if t is None else 1.0 / float(t) for t in (temperatures if temperatures is not None else [None] * count)]
+    if len(coef) != count or len(betas) != count:
+        raise ValueError(f"fuse: {count} members, {len(coef)} coefficients and {len(betas)} temperatures")
+    if mode == "logit":
+        probs, preds, fused, _ = K.fuse_scores(members, [c * b for c, b in zip(coef, betas)], K.FUSE_LOGIT)
+    else:
+        probs, preds, fused, _ = K.fuse_scores(members, coef, K.FUSE_PROB, betas)
+    return probs, preds, fused
+
+
+@dataclass
+class FusionFit:
+    """What fit_fusion found: the coefficients of the log-linear pool, the mean NLL of the valid rows at `start` and at `coef`,
+    the Newton iterations run, whether an iterate left the box of coef_max (the data are separable: coef is then the last iterate
+    and no minimum), whether the gradient met the stopping rule, and the valid and non-finite rows."""
+
+    coef: list[float]
+    nll_before: float
+    nll_after: float
+    iterations: int
+    at_bound: bool
+    converged: bool
+    valid: int = 0
+    nonfinite: int = 0
+
+
+FUSION_STEPS = 8                # step lengths 1, 1/2, ..., 2^-7 per launch (kernels.FUSE_MAX_CANDS)
+FUSION_MAX_ITERATIONS = 30
+FUSION_GRADIENT_TOL = 1e-10     # stop at max |g| / valid <= this
+FUSION_ARMIJO = 1e-4
+
+
+def unpack_fusion_terms(row: np.ndarray, K: int) -> tuple[float, np.ndarray, np.ndarray]:
+    """One candidate's kernels.fuse_terms(K) doubles -> (nll, g [K], the symmetric H [K, K])."""
+    g = np.array(row[1:1 + K], dtype=np.float64)
+    H = np.zeros((K, K), dtype=np.float64)
+    H[np.triu_indices(K)] = row[1 + K:]
+    return float(row[0]), g, H + np.triu(H, 1).T
+
+
+def newton_fusion(evaluate, start, l2: float, coef_max: float):
+    """The damped Newton method of fit_fusion on `evaluate(candidates) -> ([(nll, g, H), ...], valid)`, sums over the valid rows:
+    (coef, the summed nll at start, the summed nll at coef, iterations, at_bound, converged, valid).  The ridge l2 valid / 2
+    |a - start|^2 joins nll, g and H here.  Kept apart from the device so that a host reference can run the same steps."""
+    start = np.asarray(start, dtype=np.float64)
+    a = start.copy()
+    (first,), valid = evaluate([a.tolist()])
+    ridge = float(l2) * valid
+
+    def with_ridge(a, nll, g, H):
+        d = a - start
+        return nll + 0.5 * ridge * float(d @ d), g + ridge * d, H + ridge * np.eye(len(start))
+
+    nll, g, H = first
+    nll_before = nll
+    F, g, H = with_ridge(a, nll, g, H)
+    iterations, at_bound, converged = 0, False, False
+    while True:
+        if float(np.max(np.abs(g))) / valid <= FUSION_GRADIENT_TOL:
+            converged = True
+            break
+        if iterations >= FUSION_MAX_ITERATIONS:
+            break
+        try:
+            d = -np.linalg.solve(H, g)
+        except np.linalg.LinAlgError:
+            d = -g / max(float(np.max(np.abs(np.diag(H)))), 1.0)       # a singular Hessian (identical members): steepest descent
+        slope = float(g @ d)
+        if not np.isfinite(d).all() or slope >= 0.0:
+            d = -g / max(float(np.max(np.abs(np.diag(H)))), 1.0)
+            slope = float(g @ d)
+        steps = [2.0 ** -i for i in range(FUSION_STEPS)]
+        cands = [a + t * d for t in steps]
+        results, _ = evaluate([c.tolist() for c in cands])
+        iterations += 1
+        taken = None
+        for t, c, (c_nll, c_g, c_H) in zip(steps, cands, results):
+            c_F, c_g, c_H = with_ridge(c, c_nll, c_g, c_H)
+            if c_F <= F + FUSION_ARMIJO * t * slope:
+                taken = (c, c_nll, c_F, c_g, c_H)
+                break
+        if taken is None:                                               # no step length lowers the objective: the rounding floor
+            break
+        a, nll, F, g, H = taken
+        if float(np.max(np.abs(a))) > coef_max:
+            at_bound = True
+            break
+    return a.tolist(), nll_before, nll, iterations, at_bound, converged, valid
+
+
+def fit_fusion(logits_list, targets: torch.Tensor, start=None, l2: float = 0.0, coef_max: float = 32.0) -> FusionFit:
+    """The coefficients a of the log-linear pool softmax(sum_k a_k z_k) that minimise its NLL (plus l2 valid / 2 |a - start|^2) on K
+    models' f32 logits [n, J] on the device against int64 targets: a damped Newton method on a convex function.  Every launch
+    evaluates the candidates a + t d for t = 1, 1/2, ..., 2^-7 with their gradients and Hessians (kernels.fuse_nll); the first t
+    that satisfies the Armijo condition (c = 1e-4) is taken, and its g and H give the next direction: one launch pair and one
+    read-back per iteration.  Stops at max |g| / valid <= 1e-10 (converged) or after 30 iterations; an iterate whose largest
+    |a_k| exceeds coef_max stops the fit with at_bound (separable data have no minimum).  start: 1 / K each by default.  A target
+    outside [0, J) raises ValueError; no valid row raises ValueError."""
+    members = _members("fit_fusion", logits_list, torch.float32)
+    targets = targets.detach().reshape(-1).to(torch.int64).contiguous()
+    count = len(members)
+    n, J = members[0].shape
+    start = [1.0 / count] * count if start is None else [float(v) for v in start]
+    if len(start) != count or not (float(l2) >= 0.0 and coef_max > 0.0):
+        raise ValueError(f"fit_fusion: {count} members need {count} starting coefficients, l2 >= 0 and coef_max > 0")
+    seen = {}
+
+    def evaluate(cands):
+        sums_d, stats_d = K.fuse_nll(members, targets, cands)
+        packed = torch.cat([sums_d.reshape(-1).view(torch.int64), stats_d]).cpu().numpy()             # the iteration's one synchronisation
+        nonfinite, oob = int(packed[-2]), int(packed[-1])
+        if oob:
+            raise ValueError(f"fit_fusion: {oob} targets are outside [0, {J})")
+        if n - nonfinite <= 0:
+            raise ValueError("fit_fusion: no row with finite logits")
+        seen["nonfinite"] = nonfinite
+        table = packed[:-2].view(np.float64).reshape(len(cands), -1)
+        return [unpack_fusion_terms(row, count) for row in table], n - nonfinite
+
+    coef, before, after, iterations, at_bound, converged, valid = newton_fusion(evaluate, start, l2, coef_max)
+    return FusionFit(coef, before / valid, after / valid, iterations, at_bound, converged, valid, seen["nonfinite"])
+
+
+@dataclass
+class DiversityResult:
+    """What diversity found, from the integer tables alone; every figure is one division of Python integers, None where its
+    denominator is 0.  The [K][K] lists are indexed by (member a, member b); pair holds the counts (both right, a right b wrong,
+    a wrong b right, both wrong), hist the rows by the number of members that are right."""
+
+    accuracy: list
+    disagreement: list
+    double_fault: list
+    yule_q: list
+    kappa: list
+    oracle_accuracy: float | None
+    majority_accuracy: float | None
+    hist: list
+    pair: list
+    valid: int
+
+
+def _ratio(num: int, den: int) -> float | None:
+    return num / den if den else None
+
+
+def diversity_from_counts(pair: list, hist: list, valid: int) -> DiversityResult:
+    """DiversityResult of the Python-integer tables pair [K][K][4] and hist [K + 1] over `valid` rows."""
+    K = len(hist) - 1
+    accuracy = [_ratio(pair[k][k][0], valid) for k in range(K)]
+    disagreement, double_fault, yule_q, kappa = ([[None] * K for _ in range(K)] for _ in range(4))
+    for a in range(K):
+        for b in range(K):
+            n11, n10, n01, n00 = pair[a][b]
+            disagreement[a][b] = _ratio(n10 + n01, valid)
+            double_fault[a][b] = _ratio(n00, valid)
+            yule_q[a][b] = _ratio(n11 * n00 - n10 * n01, n11 * n00 + n10 * n01)
+            chance = (n11 + n10) * (n11 + n01) + (n01 + n00) * (n10 + n00)       # valid^2 times the agreement expected by chance
+            kappa[a][b] = _ratio(valid * (n11 + n00) - chance, valid * valid - chance)
+    return DiversityResult(accuracy, disagreement, double_fault, yule_q, kappa, _ratio(valid - hist[0], valid),
+                           _ratio(sum(h for c, h in enumerate(hist) if 2 * c > K), valid), list(hist), pair, valid)
+
+
+def diversity(preds_list, targets: torch.Tensor, num_classes: int) -> DiversityResult:
+    """How K models' int64 predictions [n] on the device coincide on being right: per-member accuracy, and per pair the
+    disagreement rate, the double-fault rate, Yule's Q and Cohen's kappa of right / wrong (Kuncheva & Whitaker 2003), plus the
+    accuracy of an oracle (any member right) and of a majority (more than K / 2 right).  kernels.fuse_agree counts; one
+    read-back.  A target outside [0, num_classes) raises ValueError."""
+    members = _members("diversity", preds_list, torch.int64)
+    targets = targets.detach().reshape(-1).to(torch.int64).contiguous()
+    count = len(members)
+    pair_d, hist_d, stats_d = K.fuse_agree(members, targets, num_classes)
+    packed = [int(v) for v in torch.cat([pair_d.reshape(-1), hist_d, stats_d]).tolist()]       # the one synchronisation
+    valid, oob = packed[-2], packed[-1]
+    if oob:
+        raise ValueError(f"diversity: {oob} targets are outside [0, {num_classes})")
+    pair = [[packed[(a * count + b) * 4:(a * count + b) * 4 + 4] for b in range(count)] for a in range(count)]
+    return diversity_from_counts(pair, packed[4 * count * count:4 * count * count + count + 1], valid)
 
 
 def gather_scores(scores: torch.Tensor, labels: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:

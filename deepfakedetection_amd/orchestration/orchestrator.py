@@ -32,7 +32,7 @@ import math
 import os
 import sys
 from collections.abc import Iterator
-from dataclasses import dataclass
+from dataclasses import asdict, dataclass, replace
 from datetime import datetime
 from pathlib import Path
 from time import perf_counter
@@ -48,7 +48,7 @@ from torch.utils.data import DataLoader
 
 from .. import data as D
 from .. import metrics as M
-from .._lib import BLUR_MAX_PIXELS, CALIB_MAX_BINS
+from .._lib import BLUR_MAX_PIXELS, CALIB_MAX_BINS, FUSE_MAX_MODELS
 from .config_schema import OrchestratorConfig
 from .model_registry import get_model_spec
 from .train_env import apply_seed, as_bool, require_num_classes
@@ -355,6 +355,65 @@ def calibration_settings(infer_cfg: dict[str, Any]) -> tuple[int, str | float] |
     return bins, value
 
 
+@dataclass(frozen=True)
+class EnsembleSettings:
+    """The top-level `ensemble:` key, every default applied (ensemble_settings)."""
+    members: tuple[str, ...]                        # keys of `models`, in the order they are fused
+    mode: str                                       # "logit" (log-linear pool) | "prob" (linear pool)
+    weights: str | tuple[float, ...]                # "equal" | "fit" | one weight per member
+    l2: float
+    output_dir: Path
+
+
+def ensemble_settings(config: dict[str, Any], out: Console) -> EnsembleSettings | None:
+    """Extra top-level key `ensemble: {members: [...], mode: logit, weights: fit, l2: 0.0, output_dir: runs/ensemble}`, or None
+    without the key.  members: default the selection; each must be a key of `models` that the selection runs.  mode: `logit`
+    (softmax of the weighted sum of logits) or `prob` (weighted sum of probabilities).  weights: `equal`, `fit` (fitted on the
+    validation split; logit mode only) or a list with one finite number per member (prob mode: none negative, summing to 1).
+    ValueError for anything else.  A single member warns on `out`: it is fused, but there is nothing to combine."""
+    raw = config.get("ensemble")
+    if raw is None or raw is False:
+        return None
+    if raw is True:
+        raw = {}
+    if not isinstance(raw, dict):
+        raise ValueError(f"ensemble must be a mapping like {{members: [a, b], mode: logit, weights: fit}}, got {raw!r}")
+    models_cfg = config.get("models") or {}
+    selection = [str(n) for n in (config.get("selection") if config.get("selection") is not None else list(models_cfg))]
+    members = raw.get("members")
+    members = tuple(selection if members is None else [str(m) for m in members]) if members is None or isinstance(members, (list, tuple)) else None
+    if not members or not 1 <= len(members) <= FUSE_MAX_MODELS or len(set(members)) != len(members):
+        raise ValueError(f"ensemble.members must list 1..{FUSE_MAX_MODELS} distinct models, got {raw.get('members')!r}")
+    missing = [m for m in members if m not in models_cfg or m not in selection]
+    if missing:
+        raise ValueError(f"ensemble.members must be models that the selection runs; not among them: {', '.join(missing)}")
+    mode = str(raw.get("mode", "logit")).strip().lower()
+    if mode not in ("logit", "prob"):
+        raise ValueError(f"ensemble.mode must be logit or prob, got {raw.get('mode')!r}")
+    weights = raw.get("weights", "fit" if mode == "logit" else "equal")
+    if isinstance(weights, (list, tuple)):
+        try:
+            weights = tuple(float(w) for w in weights)
+        except (TypeError, ValueError):
+            weights = ()
+        if len(weights) != len(members) or not all(math.isfinite(w) for w in weights):
+            raise ValueError(f"ensemble.weights must hold one finite number per member ({len(members)}), got {raw.get('weights')!r}")
+        if mode == "prob" and (min(weights) < 0.0 or abs(math.fsum(weights) - 1.0) > 1e-12):
+            raise ValueError(f"ensemble.weights in prob mode must be >= 0 and sum to 1, got {list(weights)}")
+    else:
+        weights = str(weights).strip().lower()
+        if weights not in ("equal", "fit"):
+            raise ValueError(f"ensemble.weights must be equal, fit or a list with one number per member, got {raw.get('weights')!r}")
+        if weights == "fit" and mode == "prob":
+            raise ValueError("ensemble.weights: fit needs ensemble.mode: logit (the fit is that of the log-linear pool)")
+    l2 = float(raw.get("l2", 0.0))
+    if not (math.isfinite(l2) and l2 >= 0.0):
+        raise ValueError(f"ensemble.l2 must be a number >= 0, got {raw.get('l2')!r}")
+    if len(members) == 1:
+        out.print("[bold yellow]ensemble[/]: one member only; its scores are fused with nothing")
+    return EnsembleSettings(members, mode, weights, l2, Path(str(raw.get("output_dir") or "runs/ensemble")))
+
+
 def robustness_levels(infer_cfg: dict[str, Any]) -> list[tuple[str, float | int]]:
     """Extra key `inference.robustness: {blur_sigma: [1, 2, 3], jpeg_quality: [90, 70, 50]}`: the perturbation levels the test
     split is evaluated at once more after the metrics pass, as ("blur_sigma", sigma) / ("jpeg_quality", quality) in the order
@@ -519,12 +578,14 @@ def _save_plots(cm: np.ndarray, labels: list[str], truth: np.ndarray, scores: np
         plt.close(fig)
 
 
-def run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: dict[str, Any], run_paths: RunPaths) -> None:
+def run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: dict[str, Any], run_paths: RunPaths,
+                      capture: bool = False) -> MemberScores | None:
+    """capture (the job is a member of the `ensemble:` key): hand back what the ensemble fuses (MemberScores), else None."""
     console.print(f"[bold]→ inference {model_cfg['name']}[/]")
     log_path = run_paths.logs / "inference.log"
     log_path.unlink(missing_ok=True)
     with tee_output(log_path):
-        _run_inference_job(config_path=config_path, config=config, model_cfg=model_cfg, run_paths=run_paths)
+        return _run_inference_job(config_path=config_path, config=config, model_cfg=model_cfg, run_paths=run_paths, capture=capture)
 
 
 def _resolve_weights(infer_cfg: dict[str, Any], model_name: str, out: Console) -> Path | None:
@@ -626,11 +687,14 @@ def _validation_threshold(book) -> float | None:
     return best_balanced_accuracy_threshold(scores, truth) if scores.size and np.unique(truth).size > 1 else None
 
 
-def _score_pass(model: nn.Module, dataset, s: InferenceSettings, book=None, tail=None, progress: Progress | None = None):
+def _score_pass(model: nn.Module, dataset, s: InferenceSettings, book=None, tail=None, progress: Progress | None = None,
+                keep_logits: bool = False):
     """One pass over `dataset` into `book`, which is returned: a metrics.ScoreBook, emptied first; None: a new one, on the device
-    under inference.device_metrics (its rows arrive without a host round trip), with the logits under inference.calibration."""
+    under inference.device_metrics (its rows arrive without a host round trip), with the logits under inference.calibration or
+    `keep_logits` (a member of the ensemble)."""
+    keep_logits = keep_logits or s.calibration is not None
     if book is None:
-        book = M.ScoreBook(len(dataset), s.num_classes, s.device if s.device_metrics else "cpu", keep_logits=s.calibration is not None)
+        book = M.ScoreBook(len(dataset), s.num_classes, s.device if s.device_metrics else "cpu", keep_logits=keep_logits)
     book.reset()
     loader = build_inference_loader(dataset=dataset, batch_size=s.batch_size, num_workers=s.num_workers)
     start = perf_counter()
@@ -639,7 +703,7 @@ def _score_pass(model: nn.Module, dataset, s: InferenceSettings, book=None, tail
         for images, targets in loader:
             probs, preds, logits = class_probabilities(model, images, s.device, s.amp, tail=tail, return_logits=True)
             book.append(probs, preds, targets.to(book.targets.device, non_blocking=True),
-                        logits=logits if s.calibration is not None else None)
+                        logits=logits if keep_logits else None)
             if progress is not None:
                 progress.update(task, advance=1, speed=f"{book.count / max(perf_counter() - start, 1e-6):.1f} img/s")
     return book
@@ -801,7 +865,24 @@ def inference_settings(config: dict[str, Any], model_cfg: dict[str, Any], out: C
         device_metrics=device_metrics, calibration=calibration, robustness=tuple(levels), cam_limit=limit)
 
 
-def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: dict[str, Any], run_paths: RunPaths) -> None:
+@dataclass
+class MemberScores:
+    """What one inference job leaves for the ensemble (run_ensemble_job): device tensors of its own, the logits as the network
+    gave them (a fitted temperature is kept beside them, not applied)."""
+    settings: InferenceSettings
+    classes: list[str]
+    paths: list[str]                                # the split's sample paths, in the order of the rows
+    val: tuple[torch.Tensor, torch.Tensor] | None   # (logits, targets) of the validation split; None: there was none
+    val_paths: list[str]
+    clean: tuple[torch.Tensor, torch.Tensor]        # (logits, targets) of the clean pass
+    preds: torch.Tensor                             # the predictions the clean record judges (host)
+    levels: dict[tuple[str, float | int], torch.Tensor]     # the logits of every robustness level
+    temperature: float | None                       # inference.calibration's temperature, if any
+    record: dict[str, Any]                          # the clean pass's metrics.jsonl record
+
+
+def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: dict[str, Any], run_paths: RunPaths,
+                       capture: bool = False) -> MemberScores | None:
     tty = getattr(sys.stdout, "isatty", None)
     out = Console(file=sys.stdout, force_terminal=bool(tty()) if callable(tty) else False)
     s = inference_settings(config, model_cfg, out)
@@ -809,11 +890,15 @@ def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: 
     if s.fp8_weights and hasattr(model, "fp8_weights"):
         model.fp8_weights = True
     calib = _Calibration(*s.calibration) if s.calibration is not None else None
+    capture = capture and s.device_metrics          # the ensemble fuses logits kept on the device
     threshold = 0.5
-    if s.num_classes == 2 or (calib is not None and calib.mode == "fit"):
+    val_scores, val_paths = None, []
+    if s.num_classes == 2 or (calib is not None and calib.mode == "fit") or capture:
         val_dir = s.root / s.val_split
         val_set = D.ImageFolder(val_dir, transform=s.transform) if val_dir.exists() else ()
-        val_book = _score_pass(model, val_set, s) if len(val_set) > 0 else None
+        val_book = _score_pass(model, val_set, s, keep_logits=capture) if len(val_set) > 0 else None
+        if capture and val_book is not None:
+            val_scores, val_paths = (val_book.logits.clone(), val_book.targets.clone()), [str(path) for path, _ in val_set.samples]
         if calib is not None:
             calib.fit(val_book, s.val_split, out)
         if val_book is not None and s.num_classes == 2:
@@ -828,10 +913,11 @@ def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: 
     require_num_classes(dataset, s.num_classes, split=s.split, dataset_root=split_dir)
     if len(dataset) == 0:
         out.print(f"[bold yellow]No images found in[/] {split_dir}")
-        return
+        return None
     progress = Progress(TextColumn("[bold blue]{task.description}"), BarColumn(bar_width=None), MofNCompleteColumn(),
                         TimeElapsedColumn(), TimeRemainingColumn(), TextColumn("{task.fields[speed]}"), console=out)
-    book = _score_pass(model, dataset, s, progress=progress)            # one book for this pass and every level below
+    book = _score_pass(model, dataset, s, progress=progress, keep_logits=capture)   # one book for this pass and every level below
+    clean_scores = (book.logits.clone(), book.targets.clone()) if capture else None
     clean = _judge(s, book, threshold, calib, clean=True)
     if calib is not None:
         calib.write(run_paths.run_dir)
@@ -839,8 +925,11 @@ def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: 
     _save_plots(clean.cm, list(dataset.classes), clean.targets.numpy(), scores, run_paths.plots, roc=clean.roc,
                 reliability=clean.reliability)
     _emit(clean.record, run_paths, out, "[bold]Accuracy[/]:")
+    levels = {}
     for kind, level in s.robustness:
-        _score_pass(model, dataset, s, book, tail=robustness_tail(kind, level))
+        _score_pass(model, dataset, s, book, tail=robustness_tail(kind, level), keep_logits=capture)
+        if capture:
+            levels[(kind, level)] = book.logits.clone()
         perturbed = _judge(s, book, threshold, calib).record        # at the clean pass's threshold and temperature
         perturbed["perturbation"] = {kind: level}
         _emit(perturbed, run_paths, out, f"[bold]Robustness[/] {kind}={level:g}: accuracy")
@@ -848,6 +937,110 @@ def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: 
         count = write_cam_overlays(model, dataset, clean.probs, clean.preds, s.cam_limit, run_paths.run_dir / "cam",
                                    batch_size=s.batch_size, num_workers=s.num_workers)
         out.print(f"[bold]Grad-CAM[/]: {count} overlays in {run_paths.run_dir / 'cam'}")
+    if not capture:
+        return None
+    return MemberScores(settings=s, classes=list(dataset.classes), paths=[str(path) for path, _ in dataset.samples], val=val_scores,
+                        val_paths=val_paths, clean=clean_scores, preds=clean.preds, levels=levels,
+                        temperature=float(calib.temperature) if calib is not None else None, record=clean.record)
+
+
+def _fused_book(members: list[MemberScores], logits: list[torch.Tensor], targets: torch.Tensor, ens: EnsembleSettings, weights) -> M.ScoreBook:
+    """The members' logits of one pass, fused into a device book that keeps the fused logits."""
+    probs, preds, fused = M.fuse(logits, weights, ens.mode, [m.temperature for m in members])
+    book = M.ScoreBook(targets.shape[0], members[0].settings.num_classes, targets.device, keep_logits=True)
+    book.append(probs, preds, targets, logits=fused)
+    return book
+
+
+def _ensemble_figures(book) -> dict[str, Any]:
+    res = M.calibration(book.probs, book.targets)
+    return {"ece": res.ece, "mce": res.mce, "brier": res.brier, "nll": M.mean_nll(book.logits, book.targets)}
+
+
+def run_ensemble_job(ens: EnsembleSettings, names: list[str], members: list[MemberScores], run_paths: RunPaths) -> None:
+    """Fuse the members' kept logits (metrics.fuse), judge the fused passes as a member's are judged and write ensemble.json."""
+    console.print(f"[bold]→ ensemble of {', '.join(names)}[/]")
+    log_path = run_paths.logs / "ensemble.log"
+    log_path.unlink(missing_ok=True)
+    with tee_output(log_path):
+        _run_ensemble_job(ens, names, members, run_paths)
+
+
+def _run_ensemble_job(ens: EnsembleSettings, names: list[str], members: list[MemberScores], run_paths: RunPaths) -> None:
+    tty = getattr(sys.stdout, "isatty", None)
+    out = Console(file=sys.stdout, force_terminal=bool(tty()) if callable(tty) else False)
+    first, count = members[0], len(members)
+    for name, m in zip(names[1:], members[1:]):
+        if m.paths != first.paths or not torch.equal(m.clean[1], first.clean[1]):
+            raise ValueError(f"ensemble: {name} scored other samples or targets of split {first.settings.split!r} than {names[0]}")
+        if (m.val is None) != (first.val is None) or m.val_paths != first.val_paths or \
+                (m.val is not None and not torch.equal(m.val[1], first.val[1])):
+            raise ValueError(f"ensemble: {name} scored other samples or targets of split {first.settings.val_split!r} than {names[0]}")
+    s = replace(first.settings, name="ensemble", calibration=None)
+    temperatures = [m.temperature for m in members]
+    doc: dict[str, Any] = {"members": list(names), "mode": ens.mode, "weights": ens.weights if isinstance(ens.weights, str) else "given",
+                           "temperatures": temperatures, "fit": None}
+    weights = [1.0 / count] * count if isinstance(ens.weights, str) else list(ens.weights)
+    if ens.weights == "fit":
+        start = [w / (t if t is not None else 1.0) for w, t in zip(weights, temperatures)]         # 1 / (K T_k)
+        if first.val is None:
+            out.print("[bold yellow]ensemble[/]: no validation split to fit the weights on; the start 1 / (K T_k) is used")
+            doc["fit"] = "unavailable"
+        else:
+            fit = M.fit_fusion([m.val[0] for m in members], first.val[1], start=start, l2=ens.l2)
+            doc["fit"] = asdict(fit)
+            if fit.at_bound:
+                out.print("[bold yellow]ensemble[/]: the fitted weights left their bound (the validation split is separable); "
+                          "the start 1 / (K T_k) is used")
+            else:
+                temperatures = [None] * count                           # the fitted coefficients multiply the logits as they are
+                weights = list(fit.coef)
+    fold = ens.mode == "logit"
+    doc["coefficients"] = [w / (t if fold and t is not None else 1.0) for w, t in zip(weights, temperatures)]
+    pooled = [replace(m, temperature=t) for m, t in zip(members, temperatures)]
+
+    threshold = 0.5
+    if first.val is not None and s.num_classes == 2:
+        val_book = _fused_book(pooled, [m.val[0] for m in members], first.val[1], ens, weights)
+        threshold = _first_set(_validation_threshold(val_book), threshold)
+        del val_book
+    book = _fused_book(pooled, [m.clean[0] for m in members], first.clean[1], ens, weights)
+    clean = _judge(s, book, threshold, None, clean=True)
+    clean.record.update(_ensemble_figures(book))
+    scores = clean.probs[:, 1].numpy() if s.num_classes == 2 and torch.unique(clean.targets).numel() > 1 else None
+    _save_plots(clean.cm, first.classes, clean.targets.numpy(), scores, run_paths.plots, roc=clean.roc)
+    _emit(clean.record, run_paths, out, "[bold]Ensemble accuracy[/]:")
+    for kind, level in first.settings.robustness:
+        if not all((kind, level) in m.levels for m in members):
+            continue
+        book = _fused_book(pooled, [m.levels[(kind, level)] for m in members], first.clean[1], ens, weights)
+        perturbed = _judge(s, book, threshold, None).record             # at the clean pass's threshold and coefficients
+        perturbed.update(_ensemble_figures(book))
+        perturbed["perturbation"] = {kind: level}
+        _emit(perturbed, run_paths, out, f"[bold]Ensemble robustness[/] {kind}={level:g}: accuracy")
+
+    device = first.clean[1].device
+    div = M.diversity([m.preds.to(device) for m in members], first.clean[1], s.num_classes)    # of the predictions the records judge
+    doc["diversity"] = asdict(div)
+    doc["clean"] = {name: {"accuracy": rec.get("accuracy"), "roc_auc": rec.get("roc_auc")}
+                    for name, rec in [*zip(names, (m.record for m in members)), ("ensemble", clean.record)]}
+    doc["threshold"] = float(threshold)
+    (run_paths.run_dir / "ensemble.json").write_text(json.dumps(doc, indent=2) + "\n", encoding="utf-8")
+    out.print(f"[bold]Ensemble[/]: coefficients {doc['coefficients']} | oracle accuracy {div.oracle_accuracy} | {run_paths.run_dir / 'ensemble.json'}")
+
+
+def ensemble_obstacle(ens: EnsembleSettings, captured: dict[str, MemberScores | None]) -> str | None:
+    """Why the ensemble cannot run on what the member jobs left (None: it can): every member must have kept its scores on the
+    device, and all must share the split, the validation split and the classes."""
+    absent = [name for name in ens.members if captured.get(name) is None]
+    if absent:
+        return f"{', '.join(absent)} kept no scores: every member needs inference.device_metrics on a CUDA device (and a split with images)"
+    settings = [captured[name].settings for name in ens.members]
+    for key in ("split", "val_split", "num_classes"):
+        values = {getattr(s, key) for s in settings}
+        if len(values) > 1:
+            return f"the members differ in {key}: {sorted(map(str, values))}"
+    return None
 
 
 def orchestrate(config_path: Path, *, mode: str) -> None:
@@ -858,6 +1051,8 @@ def orchestrate(config_path: Path, *, mode: str) -> None:
         raise TypeError("models section must be a mapping of name -> config")
     selection = config.get("selection")
     names = list(models_cfg) if selection is None else [str(n) for n in selection]
+    ens = ensemble_settings(config, console) if mode == "inference" else None
+    captured: dict[str, MemberScores | None] = {}
     for name in names:
         base = models_cfg.get(name)
         if base is None:
@@ -869,9 +1064,19 @@ def orchestrate(config_path: Path, *, mode: str) -> None:
         if mode == "training":
             run_training_job(config, model_cfg, run_paths)
         elif mode == "inference":
-            run_inference_job(config_path=config_path, config=config, model_cfg=model_cfg, run_paths=run_paths)
+            member = ens is not None and name in ens.members
+            scores = run_inference_job(config_path=config_path, config=config, model_cfg=model_cfg, run_paths=run_paths, capture=member)
+            if member:
+                captured[name] = scores
         else:
             raise ValueError(f"Unknown mode '{mode}'")
+    if ens is not None:
+        obstacle = ensemble_obstacle(ens, captured)
+        if obstacle is not None:
+            console.print(f"[bold yellow]ensemble skipped[/]: {obstacle}")
+            return
+        run_paths = ensure_run_dirs(ens.output_dir, datetime.now().strftime("%Y%m%d-%H%M%S"))
+        run_ensemble_job(ens, list(ens.members), [captured[name] for name in ens.members], run_paths)
 
 
 def run_cli() -> None:

@@ -99,7 +99,9 @@ typedef void* dfd_stream;          /* a hipStream_t */
  * 149 = dfd_rowtable_grad_plan (the window splits, windows per split and row lanes of dfd_rowtable_grad: host-side query; no kernel
  * changed);
  * 150 = dfd_calib_bins / _ws, dfd_calib_nll / _ws, dfd_calib_plan, dfd_softmax_argmax_t (reliability bins, Brier sum, NLL of
- * temperature-scaled logits with two derivatives, softmax / arg max at a temperature); dfd_softmax_argmax itself is unchanged. */
+ * temperature-scaled logits with two derivatives, softmax / arg max at a temperature); dfd_softmax_argmax itself is unchanged;
+ * 151 = dfd_fuse_scores, dfd_fuse_nll / _ws, dfd_fuse_agree, dfd_fuse_plan (the ensemble of K models: fused scores of a logit or a
+ * probability pool, the pool's NLL with gradient and Hessian in its coefficients, right / wrong agreement tables). */
 int dfd_version(void);
 
 /* Planner knobs: the tier switches and grid sizes by which tests and per-layer scripts reach a kernel tier.  Process-wide plain ints:
@@ -632,6 +634,61 @@ int dfd_calib_nll(const float* logits, const int64_t* targets, int n, int J, con
                   double* out, int64_t* stats, dfd_stream stream);
 int dfd_calib_plan(int n, int J, int* out);
 int dfd_softmax_argmax_t(const float* logits, int N, int J, float inv_temperature, float* probs, int64_t* preds, dfd_stream stream);
+
+/* The ensemble of K <= DFD_FUSE_MAX_MODELS models on the device (csrc/dfd_fuse.hip, ABI 151).  Member k's logits are an f32 [n][J]
+ * buffer of its own; `ptrs` is an array of K device addresses IN HOST MEMORY (they travel by value in the launch), and so are coef,
+ * beta and cands.  J <= DFD_FUSE_MAX_J classes, n <= DFD_FUSE_MAX_N rows.  A row with a NaN or an infinity in any member is
+ * `nonfinite`; in the reducing entry points a finite row whose target is outside [0, J) is `oob`; both are left out of the sums.
+ *
+ * dfd_fuse_scores: all arithmetic in f64, one rounding to f32 on store.
+ *   mode DFD_FUSE_LOGIT (log-linear pool): f_j = sum_k coef[k] z_kj (k ascending), p = softmax(f); any finite coef; beta is not read.
+ *   mode DFD_FUSE_PROB (linear pool): p_j = sum_k coef[k] softmax(beta[k] z_k)_j, f_j = log p_j; coef[k] >= 0, |sum coef - 1| <=
+ *   1e-12 and beta[k] > 0, else DFD_EINVAL.
+ *   probs f32 [n][J] = p, logits_out f32 [n][J] = f (either may be NULL), preds int64 [n] = the lowest index that attains the
+ *   maximum of the STORED f32 probabilities, stats int64 [1] = nonfinite rows; such a row gets NaN in probs and logits_out and
+ *   pred 0 (dfd_softmax_argmax's contract for one model).  Two launches (zero, scores).
+ *
+ * dfd_fuse_nll: the logit pool at C <= DFD_FUSE_MAX_CANDS coefficient vectors cands[C][K] (finite).  With T = 1 + K + K (K + 1) / 2
+ * (at most DFD_FUSE_MAX_TERMS), out f64 [C][T] = {nll, g[0..K), H[0][0..K), H[1][1..K), ..., H[K-1][K-1]} summed over the valid rows:
+ *   nll += m + log s - f_y,  g[k] += E_p z_k - z_ky,  H[k][l] += E_p[z_k z_l] - E_p z_k E_p z_l  (l >= k),
+ * where f_j = sum_k a_k z_kj, m = max_j f_j, s = sum_j exp(f_j - m), p_j = exp(f_j - m) / s, E_p x = sum_j p_j x_j.
+ *   stats int64 [2] = {nonfinite rows, oob rows}.
+ * ws: dfd_fuse_nll_ws(n, J, K, C) bytes of scratch, 8-byte aligned, no initial contents required.  A two-stage f64 sum in an order
+ * that (n, J, K) alone fixes: equal inputs give equal bits.  Two launches.
+ *
+ * dfd_fuse_agree: pred_ptrs = K int64 [n] prediction buffers, targets int64 [n].  With r_k = (pred_k == target) per valid row:
+ *   pair int64 [K][K][4] = rows with (r_a, r_b) = {(1, 1), (1, 0), (0, 1), (0, 0)}, the diagonal included,
+ *   hist int64 [K + 1]   = rows by the number of members that are right,
+ *   stats int64 [2]      = {valid rows, rows whose target is outside [0, J)}.
+ * Integer adds only: independent of the order of the rows and of the launch geometry.  Two launches (zero, count).
+ *
+ * dfd_fuse_plan: out[4] = {row layout (DFD_FUSE_LAYOUT_THREAD: one thread per row, K J <= DFD_FUSE_THREAD_MAX_KJ;
+ * DFD_FUSE_LAYOUT_WAVE: one wave per row), rows per workgroup and trip, stage-1 workgroups (at most DFD_FUSE_MAX_BLOCKS; a
+ * workgroup strides over the rest), trips of dfd_fuse_nll's stage-2 loop (DFD_FUSE_STAGE2_WIDTH partials per trip)} of
+ * dfd_fuse_scores and dfd_fuse_nll: host code, for the tests that name a tier.
+ *
+ * n == 0 is valid (zeros; the member addresses may then be NULL).  n, J, K, C or mode outside its range, a coefficient that is
+ * not finite, or a NULL pointer: DFD_EINVAL (dfd_fuse_nll_ws: 0), nothing is launched; a small ws: DFD_EWORKSPACE. */
+#define DFD_FUSE_MAX_MODELS 8
+#define DFD_FUSE_MAX_CANDS 8
+#define DFD_FUSE_MAX_J 1024
+#define DFD_FUSE_MAX_N (1 << 28)
+#define DFD_FUSE_MAX_TERMS 45
+#define DFD_FUSE_THREAD_MAX_KJ 16
+#define DFD_FUSE_MAX_BLOCKS 1024
+#define DFD_FUSE_STAGE2_WIDTH 64
+#define DFD_FUSE_LAYOUT_THREAD 0
+#define DFD_FUSE_LAYOUT_WAVE 1
+#define DFD_FUSE_LOGIT 0
+#define DFD_FUSE_PROB 1
+int dfd_fuse_scores(const float* const* ptrs, int K, int n, int J, int mode, const double* coef, const double* beta, float* probs,
+                    float* logits_out, int64_t* preds, int64_t* stats, dfd_stream stream);
+size_t dfd_fuse_nll_ws(int n, int J, int K, int C);
+int dfd_fuse_nll(const float* const* ptrs, int K, const int64_t* targets, int n, int J, const double* cands, int C, void* ws,
+                 size_t ws_bytes, double* out, int64_t* stats, dfd_stream stream);
+int dfd_fuse_agree(const int64_t* const* pred_ptrs, int K, const int64_t* targets, int n, int J, int64_t* pair, int64_t* hist,
+                   int64_t* stats, dfd_stream stream);
+int dfd_fuse_plan(int n, int J, int K, int* out);
 
 /* Input tail on the device (trainers/efficientnet.py:111-234): a uint8 NHWC
  * batch [N][H][W][3] -> RandomHorizontalFlip -> ToTensor (/255) -> Normalize((x-mean)/std) ->
