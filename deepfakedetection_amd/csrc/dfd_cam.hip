@@ -20,7 +20,7 @@
 //   Operation by operation the f32 arithmetic of numpy (tests/_cam_ref.py): contraction is off (here and in build.FLAGS) and
 //   every division is the correctly rounded one.  The cv2 coefficients follow resize(): scale = 1 / (W / w) in double,
 //   fx = (float)((dx + 0.5) * scale - 0.5), sx = floor(fx), f = fx - sx; sx < 0 or sx >= w - 1 clamp with f = 0.
-#include "dfd_common.h"
+#include "dfd_rowred.h"
 
 #pragma clang fp contract(off)
 
@@ -31,11 +31,6 @@
 template <typename T> __device__ __forceinline__ float cam_ld(const T* p, long i);
 template <> __device__ __forceinline__ float cam_ld<float>(const float* p, long i) { return p[i]; }
 template <> __device__ __forceinline__ float cam_ld<bf16>(const bf16* p, long i) { return bf2f(p[i].x); }
-
-__device__ __forceinline__ float cam_wave_sum(float v) {
-    for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off, 64);
-    return v;
-}
 
 template <typename T>
 __global__ void __launch_bounds__(CAM_MAP_THREADS)
@@ -55,7 +50,7 @@ k_gradcam_map(const T* __restrict__ act, const T* __restrict__ grad, int HW, int
         float acc = 0.f;
         const long row = base + (long)p * C;
         for (int c = lane; c < C; c += 64) acc = acc + w_sh[c] * cam_ld(act, row + c);
-        acc = cam_wave_sum(acc);
+        acc = wave_sum(acc);
         if (lane == 0) cam[(long)n * HW + p] = acc < 0.f ? 0.f : acc;
     }
 }

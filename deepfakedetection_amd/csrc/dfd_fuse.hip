@@ -3,45 +3,27 @@
 // coefficient vectors at once, and the right / wrong agreement tables of the members' predictions.
 //
 // Every member's logits are an f32 [n][J] buffer of its own; the K device addresses travel by value in the launch (fuse_ptrs_t).
-// No workgroup ever waits for another one: whatever depends on another workgroup's result is a later launch on the same stream.
-//   dfd_fuse_scores      k_fuse_zero     stats[0] = 0
+// dfd_fuse_scores and dfd_fuse_nll use the row layouts and the launch shape of dfd_rowred.h; dfd_fuse_nll is the two-stage sum
+// described there, with the order of every sum (equal inputs give equal bits):
+//   dfd_fuse_scores      k_rowred_zero   stats[0] = 0
 //                        k_fuse_scores   one row per thread or per wave: f64 throughout, one rounding to f32 on store
 //   dfd_fuse_nll         k_fuse_nll      stage 1: the workgroup's f64 partials of {nll, g[K], H[K(K+1)/2]} per candidate and its two
 //                                        int64 row counts into ws
-//                        k_fuse_sum      stage 2, ONE workgroup: the partials in index order (dfd_calib.hip's k_calib_sum)
-//   dfd_fuse_agree       k_fuse_zero     pair, hist and stats = 0
+//                        k_rowred_sum    stage 2
+//   dfd_fuse_agree       k_rowred_zero   pair, hist and stats = 0
 //                        k_fuse_agree    an LDS histogram of the 2^K right / wrong patterns per workgroup, from which the workgroup
 //                                        adds its share of every table cell with 64-bit integer adds
-// Row layouts (fuse_plan): K J <= DFD_FUSE_THREAD_MAX_KJ gives every thread one row of a chunk of FUSE_ROWS_THREAD rows (in
-// k_fuse_nll the K rows of a sample are read once into LDS and serve every candidate); above it every wave takes FUSE_WAVE_ROWS
-// consecutive rows of a chunk of FUSE_ROWS_WAVE, lane l taking columns l, l + 64, ... and reading them again per candidate.
-// Stage 1 runs min(chunks, DFD_FUSE_MAX_BLOCKS) workgroups, workgroup b taking chunks b, b + blocks, ...  The integer results are
-// sums of integers; the f64 results are summed in an order that (n, J, K) alone fixes: lanes by an xor butterfly, trips and waves
-// in index order, workgroups by k_fuse_sum.  Equal inputs give equal bits.
-#include "dfd_common.h"
+// K J <= DFD_FUSE_THREAD_MAX_KJ takes the thread layout (in k_fuse_nll the K rows of a sample are read once into LDS and serve
+// every candidate), wider inputs the wave layout, a lane reading its columns again per candidate; at most DFD_FUSE_MAX_BLOCKS
+// workgroups.
+#include "dfd_rowred.h"
 
-#define FUSE_THREADS 256
-#define FUSE_WAVES (FUSE_THREADS / 64)
-#define FUSE_ROWS_THREAD FUSE_THREADS                               // rows per chunk, one thread per row
-#define FUSE_WAVE_ROWS 8                                            // consecutive rows per wave and chunk, one wave per row
-#define FUSE_ROWS_WAVE (FUSE_WAVES * FUSE_WAVE_ROWS)
 #define FUSE_K DFD_FUSE_MAX_MODELS
 #define FUSE_TRI (FUSE_K * (FUSE_K + 1) / 2)
 static_assert(DFD_FUSE_MAX_TERMS == 1 + FUSE_K + FUSE_TRI, "nll, the gradient and the upper triangle of the Hessian");
-static_assert(DFD_FUSE_STAGE2_WIDTH == 64, "stage 2 sums one output per wave trip");
-static_assert((1 << FUSE_K) == FUSE_THREADS, "k_fuse_agree keeps one pattern count per thread");
+static_assert((1 << FUSE_K) == ROWRED_THREADS, "k_fuse_agree keeps one pattern count per thread");
 
-struct fuse_plan_t { int layout, rows, blocks, trips; };
-
-static fuse_plan_t fuse_plan(int n, int J, int K) {
-    fuse_plan_t p;
-    p.layout = K * J <= DFD_FUSE_THREAD_MAX_KJ ? DFD_FUSE_LAYOUT_THREAD : DFD_FUSE_LAYOUT_WAVE;
-    p.rows = p.layout == DFD_FUSE_LAYOUT_THREAD ? FUSE_ROWS_THREAD : FUSE_ROWS_WAVE;
-    const long chunks = ((long)n + p.rows - 1) / p.rows;
-    p.blocks = (int)(chunks < 1 ? 1 : (chunks > DFD_FUSE_MAX_BLOCKS ? DFD_FUSE_MAX_BLOCKS : chunks));
-    p.trips = (p.blocks + DFD_FUSE_STAGE2_WIDTH - 1) / DFD_FUSE_STAGE2_WIDTH;
-    return p;
-}
+static rowred_plan_t fuse_plan(int n, int J, int K) { return rowred_plan(n, K * J <= DFD_FUSE_THREAD_MAX_KJ, DFD_FUSE_MAX_BLOCKS); }
 
 static bool fuse_shape_ok(int n, int J, int K) {
     return n >= 0 && n <= DFD_FUSE_MAX_N && J >= 1 && J <= DFD_FUSE_MAX_J && K >= 1 && K <= DFD_FUSE_MAX_MODELS;
@@ -51,31 +33,6 @@ static bool fuse_shape_ok(int n, int J, int K) {
 struct fuse_ptrs_t { const void* p[FUSE_K]; };
 struct fuse_coef_t { double v[FUSE_K]; };
 struct fuse_cands_t { double v[DFD_FUSE_MAX_CANDS][FUSE_K]; };
-
-static __device__ __forceinline__ bool fuse_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
-
-static __device__ __forceinline__ double fuse_wave_sum(double v) {     // every lane ends with the same bits: a + b == b + a
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-static __device__ __forceinline__ double fuse_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-static __device__ __forceinline__ long fuse_wave_sum_i64(long v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__global__ void __launch_bounds__(FUSE_THREADS)
-k_fuse_zero(int64_t* __restrict__ a, int na, int64_t* __restrict__ b, int nb, int64_t* __restrict__ c, int nc) {
-    for (int i = threadIdx.x; i < na; i += FUSE_THREADS) a[i] = 0;
-    for (int i = threadIdx.x; i < nb; i += FUSE_THREADS) b[i] = 0;
-    for (int i = threadIdx.x; i < nc; i += FUSE_THREADS) c[i] = 0;
-}
 
 // ------------------------------------------------------------------ fused scores
 // sum_k a_k z_k[off] in the order k = 0, 1, ...: the one form of the pooled logit in this file
@@ -92,7 +49,7 @@ static __device__ __forceinline__ bool fuse_row_bad(const fuse_ptrs_t& zp, int K
 #pragma unroll
     for (int k = 0; k < FUSE_K; ++k)
         if (k < K)
-            for (int j = j0; j < J; j += step) bad |= fuse_nonfinite(((const float*)zp.p[k])[first + j]);
+            for (int j = j0; j < J; j += step) bad |= f32_nonfinite(((const float*)zp.p[k])[first + j]);
     return bad;
 }
 
@@ -106,9 +63,9 @@ static __device__ __forceinline__ void fuse_row(const fuse_ptrs_t& zp, const fus
     if (MODE == DFD_FUSE_LOGIT) {
         double m = -INFINITY, s = 0.0;
         for (int j = j0; j < J; j += step) m = fmax(m, fuse_pool(zp, coef.v, K, first + j));
-        if (WAVE) m = fuse_wave_max(m);
+        if (WAVE) m = wave_max(m);
         for (int j = j0; j < J; j += step) s += exp(fuse_pool(zp, coef.v, K, first + j) - m);
-        if (WAVE) s = fuse_wave_sum(s);
+        if (WAVE) s = wave_sum(s);
         for (int j = j0; j < J; j += step) {
             const double f = fuse_pool(zp, coef.v, K, first + j);
             const float p = (float)(exp(f - m) / s);
@@ -124,9 +81,9 @@ static __device__ __forceinline__ void fuse_row(const fuse_ptrs_t& zp, const fus
             if (k < K) {
                 const float* __restrict__ z = (const float*)zp.p[k] + first;
                 for (int j = j0; j < J; j += step) mk[k] = fmax(mk[k], beta.v[k] * (double)z[j]);
-                if (WAVE) mk[k] = fuse_wave_max(mk[k]);
+                if (WAVE) mk[k] = wave_max(mk[k]);
                 for (int j = j0; j < J; j += step) sk[k] += exp(beta.v[k] * (double)z[j] - mk[k]);
-                if (WAVE) sk[k] = fuse_wave_sum(sk[k]);
+                if (WAVE) sk[k] = wave_sum(sk[k]);
             }
         }
         for (int j = j0; j < J; j += step) {
@@ -143,14 +100,14 @@ static __device__ __forceinline__ void fuse_row(const fuse_ptrs_t& zp, const fus
 }
 
 template <int LAYOUT, int MODE>
-__global__ void __launch_bounds__(FUSE_THREADS)
+__global__ void __launch_bounds__(ROWRED_THREADS)
 k_fuse_scores(const fuse_ptrs_t zp, int K, int n, int J, const fuse_coef_t coef, const fuse_coef_t beta, float* __restrict__ probs,
               float* __restrict__ logits_out, int64_t* __restrict__ preds, int64_t* __restrict__ stats) {
-    __shared__ long red[FUSE_WAVES];
+    __shared__ long red[ROWRED_WAVES];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     long nonfinite = 0;
     if (LAYOUT == DFD_FUSE_LAYOUT_THREAD) {
-        for (long base = (long)blockIdx.x * FUSE_ROWS_THREAD; base < n; base += (long)gridDim.x * FUSE_ROWS_THREAD) {
+        for (long base = (long)blockIdx.x * ROWRED_ROWS_THREAD; base < n; base += (long)gridDim.x * ROWRED_ROWS_THREAD) {
             const long i = base + t;
             if (i >= n) continue;
             const long first = i * J;
@@ -168,9 +125,9 @@ k_fuse_scores(const fuse_ptrs_t zp, int K, int n, int J, const fuse_coef_t coef,
             preds[i] = arg;
         }
     } else {
-        for (long base = (long)blockIdx.x * FUSE_ROWS_WAVE; base < n; base += (long)gridDim.x * FUSE_ROWS_WAVE) {
-            for (int r = 0; r < FUSE_WAVE_ROWS; ++r) {
-                const long i = base + w * FUSE_WAVE_ROWS + r;               // wave-uniform
+        for (long base = (long)blockIdx.x * ROWRED_ROWS_WAVE; base < n; base += (long)gridDim.x * ROWRED_ROWS_WAVE) {
+            for (int r = 0; r < ROWRED_WAVE_ROWS; ++r) {
+                const long i = base + w * ROWRED_WAVE_ROWS + r;               // wave-uniform
                 if (i >= n) break;
                 const long first = i * J;
                 if (__any(fuse_row_bad(zp, K, first, J, lane, 64))) {
@@ -183,29 +140,24 @@ k_fuse_scores(const fuse_ptrs_t zp, int K, int n, int J, const fuse_coef_t coef,
                 }
                 float best; int arg;
                 fuse_row<MODE, true>(zp, coef, beta, K, first, J, lane, 64, probs, logits_out, best, arg);
-#pragma unroll
-                for (int o = 32; o >= 1; o >>= 1) {
-                    const float ob = __shfl_xor(best, o, 64);
-                    const int oa = __shfl_xor(arg, o, 64);
-                    if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
-                }
+                wave_first_argmax(best, arg);
                 if (lane == 0) preds[i] = arg;
             }
         }
     }
-    nonfinite = fuse_wave_sum_i64(nonfinite);
+    nonfinite = wave_sum(nonfinite);
     if (lane == 0) red[w] = nonfinite;
     __syncthreads();
     if (t == 0) {
         long s = 0;
-        for (int u = 0; u < FUSE_WAVES; ++u) s += red[u];
+        for (int u = 0; u < ROWRED_WAVES; ++u) s += red[u];
         if (s) atomicAdd(reinterpret_cast<unsigned long long*>(stats), (unsigned long long)s);
     }
 }
 
 extern "C" int dfd_fuse_plan(int n, int J, int K, int* out) {
     if (!fuse_shape_ok(n, J, K) || !out) return DFD_EINVAL;
-    const fuse_plan_t p = fuse_plan(n, J, K);
+    const rowred_plan_t p = fuse_plan(n, J, K);
     out[0] = p.layout; out[1] = p.rows; out[2] = p.blocks; out[3] = p.trips;
     return DFD_OK;
 }
@@ -219,7 +171,7 @@ static bool fuse_take_ptrs(const void* const* ptrs, int K, bool may_be_null, fus
 }
 
 #define FUSE_LAUNCH_SCORES(LAYOUT, MODE)                                                                                          \
-    hipLaunchKernelGGL((k_fuse_scores<LAYOUT, MODE>), dim3(p.blocks), dim3(FUSE_THREADS), 0, st, zp, K, n, J, cv, bv, probs, logits_out, \
+    hipLaunchKernelGGL((k_fuse_scores<LAYOUT, MODE>), dim3(p.blocks), dim3(ROWRED_THREADS), 0, st, zp, K, n, J, cv, bv, probs, logits_out, \
                        preds, stats)
 
 extern "C" int dfd_fuse_scores(const float* const* ptrs, int K, int n, int J, int mode, const double* coef, const double* beta,
@@ -239,8 +191,8 @@ extern "C" int dfd_fuse_scores(const float* const* ptrs, int K, int n, int J, in
     }
     if (mode == DFD_FUSE_PROB && !(__builtin_fabs(total - 1.0) <= 1e-12)) return DFD_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const fuse_plan_t p = fuse_plan(n, J, K);
-    hipLaunchKernelGGL(k_fuse_zero, dim3(1), dim3(FUSE_THREADS), 0, st, stats, 1, (int64_t*)nullptr, 0, (int64_t*)nullptr, 0);
+    const rowred_plan_t p = fuse_plan(n, J, K);
+    hipLaunchKernelGGL(k_rowred_zero<ROWRED_THREADS>, dim3(1), dim3(ROWRED_THREADS), 0, st, stats, 1, (int64_t*)nullptr, 0, (int64_t*)nullptr, 0);
     if (n > 0) {
         if (p.layout == DFD_FUSE_LAYOUT_THREAD) {
             if (mode == DFD_FUSE_LOGIT) FUSE_LAUNCH_SCORES(DFD_FUSE_LAYOUT_THREAD, DFD_FUSE_LOGIT);
@@ -275,7 +227,7 @@ static __device__ __forceinline__ void fuse_sums_add(fuse_sums_t& u, const doubl
 
 // Every lane holds a row's term (or 0): their sum over the wave joins the wave's running sum of candidate c, term o
 static __device__ __forceinline__ void fuse_acc(double* __restrict__ acc, int o, double v, int lane) {
-    v = fuse_wave_sum(v);
+    v = wave_sum(v);
     if (lane == 0) acc[o] += v;
 }
 
@@ -306,20 +258,20 @@ static __device__ __forceinline__ void fuse_terms(double* __restrict__ acc, cons
 }
 
 template <int LAYOUT>
-__global__ void __launch_bounds__(FUSE_THREADS)
+__global__ void __launch_bounds__(ROWRED_THREADS)
 k_fuse_nll(const fuse_ptrs_t zp, const int64_t* __restrict__ targets, int n, int J, int K, const fuse_cands_t cands, int C, int terms,
            double* __restrict__ part, int64_t* __restrict__ ipart) {
-    __shared__ double acc[FUSE_WAVES][DFD_FUSE_MAX_CANDS][DFD_FUSE_MAX_TERMS];
+    __shared__ double acc[ROWRED_WAVES][DFD_FUSE_MAX_CANDS][DFD_FUSE_MAX_TERMS];
     __shared__ double sa[DFD_FUSE_MAX_CANDS][FUSE_K];
-    __shared__ float zs[LAYOUT == DFD_FUSE_LAYOUT_THREAD ? DFD_FUSE_THREAD_MAX_KJ : 1][FUSE_THREADS];      // [k J + j][thread]
-    __shared__ long icount[FUSE_WAVES][2];
+    __shared__ float zs[LAYOUT == DFD_FUSE_LAYOUT_THREAD ? DFD_FUSE_THREAD_MAX_KJ : 1][ROWRED_THREADS];      // [k J + j][thread]
+    __shared__ long icount[ROWRED_WAVES][2];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    for (int i = t; i < FUSE_WAVES * DFD_FUSE_MAX_CANDS * DFD_FUSE_MAX_TERMS; i += FUSE_THREADS) (&acc[0][0][0])[i] = 0.0;
+    for (int i = t; i < ROWRED_WAVES * DFD_FUSE_MAX_CANDS * DFD_FUSE_MAX_TERMS; i += ROWRED_THREADS) (&acc[0][0][0])[i] = 0.0;
     if (t < DFD_FUSE_MAX_CANDS * FUSE_K) (&sa[0][0])[t] = cands.v[t / FUSE_K][t % FUSE_K];
     __syncthreads();
     long nonfinite = 0, oob = 0;
     if (LAYOUT == DFD_FUSE_LAYOUT_THREAD) {
-        for (long base = (long)blockIdx.x * FUSE_ROWS_THREAD; base < n; base += (long)gridDim.x * FUSE_ROWS_THREAD) {
+        for (long base = (long)blockIdx.x * ROWRED_ROWS_THREAD; base < n; base += (long)gridDim.x * ROWRED_ROWS_THREAD) {
             const long i = base + t;                                        // the trip count is wave-uniform: base < n for the wave
             bool ok = i < n;
             int y = 0;
@@ -331,7 +283,7 @@ k_fuse_nll(const fuse_ptrs_t zp, const int64_t* __restrict__ targets, int n, int
                         const float* __restrict__ row = (const float*)zp.p[k] + i * J;
                         for (int j = 0; j < J; ++j) {
                             const float v = row[j];
-                            bad |= fuse_nonfinite(v);
+                            bad |= f32_nonfinite(v);
                             zs[k * J + j][t] = v;                           // k J + j < K J <= DFD_FUSE_THREAD_MAX_KJ; read by this thread only
                         }
                     }
@@ -380,9 +332,9 @@ k_fuse_nll(const fuse_ptrs_t zp, const int64_t* __restrict__ targets, int n, int
             }
         }
     } else {
-        for (long base = (long)blockIdx.x * FUSE_ROWS_WAVE; base < n; base += (long)gridDim.x * FUSE_ROWS_WAVE) {
-            for (int r = 0; r < FUSE_WAVE_ROWS; ++r) {
-                const long i = base + w * FUSE_WAVE_ROWS + r;               // wave-uniform
+        for (long base = (long)blockIdx.x * ROWRED_ROWS_WAVE; base < n; base += (long)gridDim.x * ROWRED_ROWS_WAVE) {
+            for (int r = 0; r < ROWRED_WAVE_ROWS; ++r) {
+                const long i = base + w * ROWRED_WAVE_ROWS + r;               // wave-uniform
                 if (i >= n) break;
                 const long first = i * J;
                 const int64_t y = targets[i];
@@ -394,7 +346,7 @@ k_fuse_nll(const fuse_ptrs_t zp, const int64_t* __restrict__ targets, int n, int
                 for (int c = 0; c < C; ++c) {
                     double m = -INFINITY, fy = 0.0;
                     for (int j = lane; j < J; j += 64) m = fmax(m, fuse_pool(zp, sa[c], K, first + j));
-                    m = fuse_wave_max(m);
+                    m = wave_max(m);
 #pragma unroll
                     for (int k = 0; k < FUSE_K; ++k)
                         if (k < K) fy += sa[c][k] * zy[k];                  // fuse_pool's arithmetic at column y
@@ -413,14 +365,14 @@ k_fuse_nll(const fuse_ptrs_t zp, const int64_t* __restrict__ targets, int n, int
                         }
                         fuse_sums_add(u, zk, exp(f - m), K);
                     }
-                    u.s = fuse_wave_sum(u.s);
+                    u.s = wave_sum(u.s);
 #pragma unroll
                     for (int k = 0; k < FUSE_K; ++k) {
                         if (k < K) {
-                            u.s1[k] = fuse_wave_sum(u.s1[k]);
+                            u.s1[k] = wave_sum(u.s1[k]);
 #pragma unroll
                             for (int l = k; l < FUSE_K; ++l)
-                                if (l < K) u.s2[fuse_tri(k, l)] = fuse_wave_sum(u.s2[fuse_tri(k, l)]);
+                                if (l < K) u.s2[fuse_tri(k, l)] = wave_sum(u.s2[fuse_tri(k, l)]);
                         }
                     }
                     fuse_terms<true>(acc[w][c], u, m, fy, zy, K, true, lane);
@@ -428,47 +380,7 @@ k_fuse_nll(const fuse_ptrs_t zp, const int64_t* __restrict__ targets, int n, int
             }
         }
     }
-    nonfinite = fuse_wave_sum_i64(nonfinite); oob = fuse_wave_sum_i64(oob);
-    if (lane == 0) { icount[w][0] = nonfinite; icount[w][1] = oob; }
-    __syncthreads();
-    const int blocks = gridDim.x;
-    for (int o = t; o < C * terms; o += FUSE_THREADS) {
-        const int c = o / terms, q = o - c * terms;
-        double s = acc[0][c][q];
-        for (int u = 1; u < FUSE_WAVES; ++u) s += acc[u][c][q];
-        part[(long)o * blocks + blockIdx.x] = s;
-    }
-    if (t < 2) {
-        long s = 0;
-        for (int u = 0; u < FUSE_WAVES; ++u) s += icount[u][t];
-        ipart[(long)t * blocks + blockIdx.x] = s;
-    }
-}
-
-// Stage 2, one workgroup: out[o] = the sum over b < blocks of part[o * blocks + b], o < nf (f64) — wave w takes o = w, w + 4, ...,
-// its lanes the partials lane, lane + 64, ... in `trips` trips, then the butterfly — and iout[o] likewise over ipart (int64), o < ni.
-__global__ void __launch_bounds__(FUSE_THREADS)
-k_fuse_sum(const double* __restrict__ part, int nf, const int64_t* __restrict__ ipart, int ni, int blocks, int trips,
-           double* __restrict__ out, int64_t* __restrict__ iout) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int o = w; o < nf; o += FUSE_WAVES) {
-        double s = 0.0;
-        for (int trip = 0; trip < trips; ++trip) {
-            const int b = trip * DFD_FUSE_STAGE2_WIDTH + lane;
-            if (b < blocks) s += part[(long)o * blocks + b];
-        }
-        s = fuse_wave_sum(s);
-        if (lane == 0) out[o] = s;
-    }
-    for (int o = w; o < ni; o += FUSE_WAVES) {
-        long s = 0;
-        for (int trip = 0; trip < trips; ++trip) {
-            const int b = trip * DFD_FUSE_STAGE2_WIDTH + lane;
-            if (b < blocks) s += ipart[(long)o * blocks + b];
-        }
-        s = fuse_wave_sum_i64(s);
-        if (lane == 0) iout[o] = s;
-    }
+    rowred_stage1_store(acc, icount, C * terms, terms, nonfinite, oob, part, ipart);
 }
 
 static int fuse_terms_of(int K) { return 1 + K + K * (K + 1) / 2; }
@@ -492,34 +404,34 @@ extern "C" int dfd_fuse_nll(const float* const* ptrs, int K, const int64_t* targ
         }
     if (ws_bytes < dfd_fuse_nll_ws(n, J, K, C)) return DFD_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const fuse_plan_t p = fuse_plan(n, J, K);
+    const rowred_plan_t p = fuse_plan(n, J, K);
     const int terms = fuse_terms_of(K);
     double* part = (double*)ws;
     int64_t* ipart = (int64_t*)(part + (size_t)p.blocks * C * terms);
     if (p.layout == DFD_FUSE_LAYOUT_THREAD)
-        hipLaunchKernelGGL(k_fuse_nll<DFD_FUSE_LAYOUT_THREAD>, dim3(p.blocks), dim3(FUSE_THREADS), 0, st, zp, targets, n, J, K, cv, C, terms,
+        hipLaunchKernelGGL(k_fuse_nll<DFD_FUSE_LAYOUT_THREAD>, dim3(p.blocks), dim3(ROWRED_THREADS), 0, st, zp, targets, n, J, K, cv, C, terms,
                            part, ipart);
     else
-        hipLaunchKernelGGL(k_fuse_nll<DFD_FUSE_LAYOUT_WAVE>, dim3(p.blocks), dim3(FUSE_THREADS), 0, st, zp, targets, n, J, K, cv, C, terms,
+        hipLaunchKernelGGL(k_fuse_nll<DFD_FUSE_LAYOUT_WAVE>, dim3(p.blocks), dim3(ROWRED_THREADS), 0, st, zp, targets, n, J, K, cv, C, terms,
                            part, ipart);
-    hipLaunchKernelGGL(k_fuse_sum, dim3(1), dim3(FUSE_THREADS), 0, st, (const double*)part, C * terms, (const int64_t*)ipart, 2, p.blocks,
-                       p.trips, out, stats);
+    hipLaunchKernelGGL(k_rowred_sum<ROWRED_THREADS>, dim3(1), dim3(ROWRED_THREADS), 0, st, (const double*)part, C * terms, (const int64_t*)ipart,
+                       2, p.blocks, p.trips, out, stats);
     return DFD_CHECK_LAUNCH();
 }
 
 // ------------------------------------------------------------------ agreement of the members' predictions
 // Bit k of a row's pattern: member k predicted the target.  cnt[pattern] per workgroup in LDS; then cell (a, b, q) of pair is the
 // sum of cnt over the patterns whose bits a and b read q = {11, 10, 01, 00}[q], and hist[c] the sum over those with c bits set.
-__global__ void __launch_bounds__(FUSE_THREADS)
+__global__ void __launch_bounds__(ROWRED_THREADS)
 k_fuse_agree(const fuse_ptrs_t pp, const int64_t* __restrict__ targets, int n, int J, int K, int64_t* __restrict__ pair,
              int64_t* __restrict__ hist, int64_t* __restrict__ stats) {
     __shared__ unsigned int cnt[1 << FUSE_K];
-    __shared__ long red[FUSE_WAVES];
+    __shared__ long red[ROWRED_WAVES];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     cnt[t] = 0;
     __syncthreads();
     long oob = 0;
-    for (long i = (long)blockIdx.x * FUSE_THREADS + t; i < n; i += (long)gridDim.x * FUSE_THREADS) {
+    for (long i = (long)blockIdx.x * ROWRED_THREADS + t; i < n; i += (long)gridDim.x * ROWRED_THREADS) {
         const int64_t y = targets[i];
         if (y < 0 || y >= J) { ++oob; continue; }
         unsigned int pattern = 0;
@@ -528,11 +440,11 @@ k_fuse_agree(const fuse_ptrs_t pp, const int64_t* __restrict__ targets, int n, i
             if (k < K) pattern |= (unsigned int)(((const int64_t*)pp.p[k])[i] == y) << k;
         atomicAdd(&cnt[pattern], 1u);                                       // fewer than 2^32 rows in all (DFD_FUSE_MAX_N)
     }
-    oob = fuse_wave_sum_i64(oob);
+    oob = wave_sum(oob);
     if (lane == 0) red[w] = oob;
     __syncthreads();
     const int patterns = 1 << K;
-    for (int o = t; o < K * K * 4; o += FUSE_THREADS) {
+    for (int o = t; o < K * K * 4; o += ROWRED_THREADS) {
         const int q = o & 3, b = (o >> 2) % K, a = (o >> 2) / K;
         const unsigned int want_a = q < 2, want_b = (q & 1) == 0;
         long s = 0;
@@ -546,10 +458,10 @@ k_fuse_agree(const fuse_ptrs_t pp, const int64_t* __restrict__ targets, int n, i
             if (__popc(m) == t) s += cnt[m];
         if (s) atomicAdd(reinterpret_cast<unsigned long long*>(hist + t), (unsigned long long)s);
     }
-    if (t == FUSE_THREADS - 1) {
+    if (t == ROWRED_THREADS - 1) {
         long valid = 0, bad = 0;
         for (int m = 0; m < patterns; ++m) valid += cnt[m];
-        for (int u = 0; u < FUSE_WAVES; ++u) bad += red[u];
+        for (int u = 0; u < ROWRED_WAVES; ++u) bad += red[u];
         if (valid) atomicAdd(reinterpret_cast<unsigned long long*>(stats + 0), (unsigned long long)valid);
         if (bad) atomicAdd(reinterpret_cast<unsigned long long*>(stats + 1), (unsigned long long)bad);
     }
@@ -562,10 +474,10 @@ extern "C" int dfd_fuse_agree(const int64_t* const* pred_ptrs, int K, const int6
     fuse_ptrs_t pp;
     if (!fuse_take_ptrs((const void* const*)pred_ptrs, K, n == 0, pp)) return DFD_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const long chunks = ((long)n + FUSE_THREADS - 1) / FUSE_THREADS;
+    const long chunks = ((long)n + ROWRED_THREADS - 1) / ROWRED_THREADS;
     const int blocks = (int)(chunks > DFD_FUSE_MAX_BLOCKS ? DFD_FUSE_MAX_BLOCKS : chunks);
-    hipLaunchKernelGGL(k_fuse_zero, dim3(1), dim3(FUSE_THREADS), 0, st, pair, K * K * 4, hist, K + 1, stats, 2);
+    hipLaunchKernelGGL(k_rowred_zero<ROWRED_THREADS>, dim3(1), dim3(ROWRED_THREADS), 0, st, pair, K * K * 4, hist, K + 1, stats, 2);
     if (blocks > 0)
-        hipLaunchKernelGGL(k_fuse_agree, dim3(blocks), dim3(FUSE_THREADS), 0, st, pp, targets, n, J, K, pair, hist, stats);
+        hipLaunchKernelGGL(k_fuse_agree, dim3(blocks), dim3(ROWRED_THREADS), 0, st, pp, targets, n, J, K, pair, hist, stats);
     return DFD_CHECK_LAUNCH();
 }

@@ -1,19 +1,11 @@
 // dfd_misc.hip — the small kernels around the conv stack: squeeze-excite MLP, stem
-// convolution, classifier head, label-smoothed cross entropy, softmax/argmax and the
-// fused multi-tensor AdamW step.  All f32 except the stem's output / gradient tensors.
+// convolution, classifier head, label-smoothed cross entropy, softmax/argmax (plain and
+// temperature-scaled: one kernel) and the fused multi-tensor AdamW step.  All f32 except
+// the stem's output / gradient tensors.  Wave and workgroup reductions: dfd_rowred.h.
 #include "dfd_common.h"
+#include "dfd_rowred.h"
 #include "dfd_se.h"
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
 template <int ACT> __device__ __forceinline__ float act_rt(float z) { return act_fwd<ACT>(z); }
 
 // ===========================================================================
@@ -807,17 +799,6 @@ extern "C" int dfd_linear_bwd(const float* dout, const float* x, const float* w,
 // ===========================================================================
 // label-smoothed cross entropy (mean reduction), softmax / argmax
 // ===========================================================================
-__device__ __forceinline__ float block_reduce(float v, float* sm, bool is_max) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    v = is_max ? wave_max(v) : wave_sum(v);
-    __syncthreads();
-    if (lane == 0) sm[wave] = v;
-    __syncthreads();
-    float r = sm[0];
-    for (int i = 1; i < DFD_THREADS / 64; ++i) r = is_max ? fmaxf(r, sm[i]) : r + sm[i];
-    return r;
-}
-
 __global__ void __launch_bounds__(DFD_THREADS)
 k_ce_rows(const float* __restrict__ logits, const int64_t* __restrict__ targets, int N, int J, float eps, float gscale,
           float* __restrict__ row_loss, float* __restrict__ dlogits) {
@@ -1021,8 +1002,13 @@ extern "C" int dfd_ce_loss_w(const float* logits, const void* targets, int soft,
     return DFD_CHECK_LAUNCH();
 }
 
+// SCALED: softmax / arg max of beta * z as exp((z - max) * beta), beta > 0; at beta == 1 the product is exact and both instances
+// return the same bits.  The plain instance never reads beta and has no multiplication.
+template <bool SCALED> __device__ __forceinline__ float softmax_exp(float d, float beta) { return SCALED ? __expf(d * beta) : __expf(d); }
+
+template <bool SCALED>
 __global__ void __launch_bounds__(DFD_THREADS)
-k_softmax_argmax(const float* __restrict__ logits, int J, float* __restrict__ probs, int64_t* __restrict__ preds) {
+k_softmax_argmax(const float* __restrict__ logits, int J, float beta, float* __restrict__ probs, int64_t* __restrict__ preds) {
     __shared__ float sm[4];
     __shared__ int si[4];
     const int n = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -1031,7 +1017,7 @@ k_softmax_argmax(const float* __restrict__ logits, int J, float* __restrict__ pr
     for (int j = t; j < J; j += DFD_THREADS) mx = fmaxf(mx, lr[j]);
     mx = block_reduce(mx, sm, true);
     float se = 0.f;
-    for (int j = t; j < J; j += DFD_THREADS) se += __expf(lr[j] - mx);
+    for (int j = t; j < J; j += DFD_THREADS) se += softmax_exp<SCALED>(lr[j] - mx, beta);
     se = block_reduce(se, sm, false);
     const float inv = 1.f / se;
     // A thread starts from (-1, index 0): any probability, which is >= 0, beats it, so a thread without a column never wins.  A
@@ -1039,17 +1025,11 @@ k_softmax_argmax(const float* __restrict__ logits, int J, float* __restrict__ pr
     // index torch.argmax(torch.softmax(row)) returns, and stays an index into the row.
     float bp = -1.f; int bi = 0;
     for (int j = t; j < J; j += DFD_THREADS) {
-        const float p = __expf(lr[j] - mx) * inv;
+        const float p = softmax_exp<SCALED>(lr[j] - mx, beta) * inv;
         if (probs) probs[(long)n * J + j] = p;
         if (p > bp) { bp = p; bi = j; }
     }
-    // arg max of the probabilities, lowest index on ties
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const float op = __shfl_xor(bp, o);
-        const int oi = __shfl_xor(bi, o);
-        if (op > bp || (op == bp && oi < bi)) { bp = op; bi = oi; }
-    }
+    wave_first_argmax(bp, bi);                                          // arg max of the probabilities, lowest index on ties
     __syncthreads();
     if (lane == 0) { sm[wave] = bp; si[wave] = bi; }
     __syncthreads();
@@ -1061,7 +1041,14 @@ k_softmax_argmax(const float* __restrict__ logits, int J, float* __restrict__ pr
 }
 extern "C" int dfd_softmax_argmax(const float* logits, int N, int J, float* probs, int64_t* preds, dfd_stream stream) {
     if (!logits || !preds || N < 1 || J < 1) return DFD_EINVAL;
-    hipLaunchKernelGGL(k_softmax_argmax, dim3(N), dim3(DFD_THREADS), 0, (hipStream_t)stream, logits, J, probs, preds);
+    hipLaunchKernelGGL(k_softmax_argmax<false>, dim3(N), dim3(DFD_THREADS), 0, (hipStream_t)stream, logits, J, 1.f, probs, preds);
+    return DFD_CHECK_LAUNCH();
+}
+extern "C" int dfd_softmax_argmax_t(const float* logits, int N, int J, float inv_temperature, float* probs, int64_t* preds,
+                                    dfd_stream stream) {
+    if (!logits || !preds || N < 1 || J < 1) return DFD_EINVAL;
+    if (!(inv_temperature > 0.f) || !__builtin_isfinite(inv_temperature)) return DFD_EINVAL;
+    hipLaunchKernelGGL(k_softmax_argmax<true>, dim3(N), dim3(DFD_THREADS), 0, (hipStream_t)stream, logits, J, inv_temperature, probs, preds);
     return DFD_CHECK_LAUNCH();
 }
 

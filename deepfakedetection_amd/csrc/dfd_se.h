@@ -2,13 +2,7 @@
 // backward kernel that can carry it as extra workgroups (dfd_rowpass.hip, dfd_act_bn_bwd_se): the result is read by AdamW only, so it
 // does not have to be a launch of its own on the block's dependency chain (16 launches of ~13 us per EfficientNet-B0 step).
 #pragma once
-#include "dfd_common.h"
-
-__device__ __forceinline__ float se_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
+#include "dfd_rowred.h"
 
 // block (bx, by) of a (ceil(C / 64), R) grid of 256 threads; red: >= 3 * 4 * 64 floats of LDS.  ws = [g: N x C | dh: N x R | h: N x R]
 // (dfd_se_bwd's workspace).  thread (c, nl) sums every 4th image, the four image lanes are combined through LDS in a fixed order.
@@ -58,7 +52,7 @@ __device__ __forceinline__ void se_fc_bwd_w_body(const float* __restrict__ poole
         __syncthreads();
         float s = 0.f;
         for (int n = t; n < N; n += DFD_THREADS) s += ws_dh[(long)n * R + r];
-        s = se_wave_sum(s);
+        s = wave_sum(s);
         if ((t & 63) == 0) red[t >> 6] = s;
         __syncthreads();
         if (t == 0) db1[r] = (accumulate ? db1[r] : 0.f) + red[0] + red[1] + red[2] + red[3];

@@ -1292,9 +1292,9 @@ CALIB_LAYOUT_THREAD, CALIB_LAYOUT_WAVE = _lib.CALIB_LAYOUT_THREAD, _lib.CALIB_LA
 
 
 @dataclass(frozen=True)
-class CalibPlan:
-    """dfd_calib_plan's answer: the row layout, the rows a workgroup takes per trip, the stage-1 workgroups and the trips of the
-    stage-2 loop of calib_bins / calib_nll at (n, J)."""
+class RowPlan:
+    """dfd_calib_plan's and dfd_fuse_plan's answer (csrc/dfd_rowred.h): the row layout, the rows a workgroup takes per trip, the
+    stage-1 workgroups and the trips of the stage-2 loop."""
 
     layout: int
     rows: int
@@ -1302,17 +1302,11 @@ class CalibPlan:
     trips: int
 
 
-def _calib_rows(op: str, rows: torch.Tensor, targets: torch.Tensor) -> tuple[int, int]:
-    if rows.dim() != 2 or rows.dtype != torch.float32 or targets.dtype != torch.int64 or tuple(targets.shape) != (rows.shape[0],):
-        raise ValueError(f"{op}: expected f32 [n, J] rows and int64 [n] targets, got {rows.dtype} {tuple(rows.shape)} and "
-                         f"{targets.dtype} {tuple(targets.shape)}")
-    n, J = rows.shape
-    if not 0 <= n <= CALIB_MAX_N or not 1 <= J <= CALIB_MAX_J:
-        raise ValueError(f"{op}: takes 0..{CALIB_MAX_N} rows of 1..{CALIB_MAX_J} classes, got [{n}, {J}]")
-    return n, J
+CalibPlan = FusePlan = RowPlan
 
 
-def _calib_ws(op: str, ws: torch.Tensor | None, need: int, device) -> torch.Tensor:
+def _f64_ws(op: str, ws: torch.Tensor | None, need: int, device) -> torch.Tensor:
+    """The caller's workspace if it is an 8-byte aligned uint8 tensor of `need` bytes (it holds f64 and int64 partials), or a new one."""
     if ws is None:
         return torch.empty(max(need // 8, 1), dtype=torch.float64, device=device).view(torch.uint8)
     if ws.dtype != torch.uint8 or ws.numel() < need or ws.device != device or ws.data_ptr() % 8:
@@ -1320,25 +1314,38 @@ def _calib_ws(op: str, ws: torch.Tensor | None, need: int, device) -> torch.Tens
     return ws
 
 
+def _calib_shape(op: str, n: int, J: int, K: int | None = None) -> None:
+    if not 0 <= n <= CALIB_MAX_N or not 1 <= J <= CALIB_MAX_J:
+        raise ValueError(f"{op}: takes 0..{CALIB_MAX_N} rows of 1..{CALIB_MAX_J} classes, got [{n}, {J}]")
+    if K is not None and not 1 <= K <= CALIB_MAX_BETAS:
+        raise ValueError(f"{op}: takes 1..{CALIB_MAX_BETAS} betas, got {K}")
+
+
+def _calib_rows(op: str, rows: torch.Tensor, targets: torch.Tensor) -> tuple[int, int]:
+    if rows.dim() != 2 or rows.dtype != torch.float32 or targets.dtype != torch.int64 or tuple(targets.shape) != (rows.shape[0],):
+        raise ValueError(f"{op}: expected f32 [n, J] rows and int64 [n] targets, got {rows.dtype} {tuple(rows.shape)} and "
+                         f"{targets.dtype} {tuple(targets.shape)}")
+    _calib_shape(op, *rows.shape)
+    return rows.shape
+
+
 def calib_bins_ws(n: int, J: int) -> int:
     """Bytes of workspace calib_bins needs for n rows of J classes."""
-    if not 0 <= n <= CALIB_MAX_N or not 1 <= J <= CALIB_MAX_J:
-        raise ValueError(f"calib_bins takes 0..{CALIB_MAX_N} rows of 1..{CALIB_MAX_J} classes, got [{n}, {J}]")
+    _calib_shape("calib_bins", n, J)
     return _L().dfd_calib_bins_ws(n, J)
 
 
 def calib_nll_ws(n: int, J: int, K: int) -> int:
     """Bytes of workspace calib_nll needs for n rows of J classes at K betas; it covers calib_bins_ws(n, J) too."""
-    if not 0 <= n <= CALIB_MAX_N or not 1 <= J <= CALIB_MAX_J or not 1 <= K <= CALIB_MAX_BETAS:
-        raise ValueError(f"calib_nll takes 0..{CALIB_MAX_N} rows of 1..{CALIB_MAX_J} classes at 1..{CALIB_MAX_BETAS} betas, got [{n}, {J}], {K}")
+    _calib_shape("calib_nll", n, J, K)
     return _L().dfd_calib_nll_ws(n, J, K)
 
 
-def calib_plan(n: int, J: int) -> CalibPlan:
+def calib_plan(n: int, J: int) -> RowPlan:
     """Which layout and launch shape calib_bins / calib_nll use for n rows of J classes (host code)."""
     out = (ctypes.c_int * 4)()
     check(_L().dfd_calib_plan(int(n), int(J), out), "dfd_calib_plan", f"n={n} J={J}")
-    return CalibPlan(*out)
+    return RowPlan(*out)
 
 
 def calib_bins(probs: torch.Tensor, targets: torch.Tensor, bins: int = 15, ws: torch.Tensor | None = None, out=None):
@@ -1350,7 +1357,7 @@ def calib_bins(probs: torch.Tensor, targets: torch.Tensor, bins: int = 15, ws: t
     if not 1 <= M <= CALIB_MAX_BINS:
         raise ValueError(f"calib_bins: bins must be 1..{CALIB_MAX_BINS}, got {M}")
     device = probs.device
-    ws = _calib_ws("calib_bins", ws, calib_bins_ws(n, J), device)
+    ws = _f64_ws("calib_bins", ws, calib_bins_ws(n, J), device)
     o_bins, o_stats, o_brier = out if out is not None else (None, None, None)
     table = _dst(o_bins, (M, 3), device, torch.int64)
     stats = _dst(o_stats, (4,), device, torch.int64)
@@ -1371,7 +1378,7 @@ def calib_nll(logits: torch.Tensor, targets: torch.Tensor, betas, ws: torch.Tens
     if not 1 <= K <= CALIB_MAX_BETAS or not all(math.isfinite(b) and b > 0.0 for b in values):
         raise ValueError(f"calib_nll: expected 1..{CALIB_MAX_BETAS} finite betas > 0, got {values}")
     device = logits.device
-    ws = _calib_ws("calib_nll", ws, calib_nll_ws(n, J, K), device)
+    ws = _f64_ws("calib_nll", ws, calib_nll_ws(n, J, K), device)
     o_out, o_stats = out if out is not None else (None, None)
     sums = _dst(o_out, (K, 3), device, torch.float64)
     stats = _dst(o_stats, (2,), device, torch.int64)
@@ -1400,20 +1407,15 @@ FUSE_THREAD_MAX_KJ, FUSE_MAX_BLOCKS, FUSE_STAGE2_WIDTH = _lib.FUSE_THREAD_MAX_KJ
 FUSE_LAYOUT_THREAD, FUSE_LAYOUT_WAVE, FUSE_LOGIT, FUSE_PROB = _lib.FUSE_LAYOUT_THREAD, _lib.FUSE_LAYOUT_WAVE, _lib.FUSE_LOGIT, _lib.FUSE_PROB
 
 
-@dataclass(frozen=True)
-class FusePlan:
-    """dfd_fuse_plan's answer: the row layout, the rows a workgroup takes per trip, the stage-1 workgroups and the trips of
-    fuse_nll's stage-2 loop at (n, J, K)."""
-
-    layout: int
-    rows: int
-    blocks: int
-    trips: int
-
-
 def fuse_terms(K: int) -> int:
     """The f64 results per candidate of fuse_nll: the NLL, K gradient entries and the upper triangle of the Hessian."""
     return 1 + K + K * (K + 1) // 2
+
+
+def _fuse_shape(op: str, n: int, J: int, K: int, C: int = 1) -> None:
+    if not 0 <= n <= FUSE_MAX_N or not 1 <= J <= FUSE_MAX_J or not 1 <= K <= FUSE_MAX_MODELS or not 1 <= C <= FUSE_MAX_CANDS:
+        raise ValueError(f"{op}: takes 0..{FUSE_MAX_N} rows of 1..{FUSE_MAX_J} classes from 1..{FUSE_MAX_MODELS} members at "
+                         f"1..{FUSE_MAX_CANDS} candidates, got [{n}, {J}], {K}, {C}")
 
 
 def _fuse_members(op: str, members, dtype: torch.dtype, dim: int):
@@ -1427,9 +1429,7 @@ def _fuse_members(op: str, members, dtype: torch.dtype, dim: int):
         if m.dim() != dim or m.dtype != dtype or m.shape != first.shape or m.device != first.device:
             raise ValueError(f"{op}: every member must be {dtype} with {dim} dimensions, one shape and one device, got "
                              f"{[(m.dtype, tuple(m.shape)) for m in members]}")
-    n = first.shape[0]
-    if not 0 <= n <= FUSE_MAX_N or (dim == 2 and not 1 <= first.shape[1] <= FUSE_MAX_J):
-        raise ValueError(f"{op}: takes 0..{FUSE_MAX_N} rows of 1..{FUSE_MAX_J} classes, got {tuple(first.shape)}")
+    _fuse_shape(op, first.shape[0], first.shape[1] if dim == 2 else 1, K)
     return members, (ctypes.c_void_p * K)(*[_p(m) for m in members])
 
 
@@ -1438,18 +1438,16 @@ def _fuse_targets(op: str, targets: torch.Tensor, n: int) -> None:
         raise ValueError(f"{op}: expected int64 [{n}] targets, got {targets.dtype} {tuple(targets.shape)}")
 
 
-def fuse_plan(n: int, J: int, K: int) -> FusePlan:
+def fuse_plan(n: int, J: int, K: int) -> RowPlan:
     """Which layout and launch shape fuse_scores / fuse_nll use for n rows of J classes from K members (host code)."""
     out = (ctypes.c_int * 4)()
     check(_L().dfd_fuse_plan(int(n), int(J), int(K), out), "dfd_fuse_plan", f"n={n} J={J} K={K}")
-    return FusePlan(*out)
+    return RowPlan(*out)
 
 
 def fuse_nll_ws(n: int, J: int, K: int, C: int) -> int:
     """Bytes of workspace fuse_nll needs for n rows of J classes from K members at C candidates."""
-    if not 0 <= n <= FUSE_MAX_N or not 1 <= J <= FUSE_MAX_J or not 1 <= K <= FUSE_MAX_MODELS or not 1 <= C <= FUSE_MAX_CANDS:
-        raise ValueError(f"fuse_nll takes 0..{FUSE_MAX_N} rows of 1..{FUSE_MAX_J} classes from 1..{FUSE_MAX_MODELS} members at "
-                         f"1..{FUSE_MAX_CANDS} candidates, got [{n}, {J}], {K}, {C}")
+    _fuse_shape("fuse_nll", n, J, K, C)
     return _L().dfd_fuse_nll_ws(n, J, K, C)
 
 
@@ -1493,7 +1491,7 @@ def fuse_nll(logits_list, targets: torch.Tensor, cands, ws: torch.Tensor | None 
     if not 1 <= C <= FUSE_MAX_CANDS or any(len(r) != K or not all(math.isfinite(v) for v in r) for r in rows):
         raise ValueError(f"fuse_nll: expected 1..{FUSE_MAX_CANDS} candidates of {K} finite coefficients, got {rows}")
     device = members[0].device
-    ws = _calib_ws("fuse_nll", ws, fuse_nll_ws(n, J, K, C), device)
+    ws = _f64_ws("fuse_nll", ws, fuse_nll_ws(n, J, K, C), device)
     o_out, o_stats = out if out is not None else (None, None)
     sums = _dst(o_out, (C, fuse_terms(K)), device, torch.float64)
     stats = _dst(o_stats, (2,), device, torch.int64)
@@ -1510,8 +1508,7 @@ def fuse_agree(preds_list, targets: torch.Tensor, num_classes: int, out=None):
     members, ptrs = _fuse_members("fuse_agree", preds_list, torch.int64, 1)
     K, n, J = len(members), members[0].shape[0], int(num_classes)
     _fuse_targets("fuse_agree", targets, n)
-    if not 1 <= J <= FUSE_MAX_J:
-        raise ValueError(f"fuse_agree: num_classes must be 1..{FUSE_MAX_J}, got {J}")
+    _fuse_shape("fuse_agree", n, J, K)
     device = members[0].device
     o_pair, o_hist, o_stats = out if out is not None else (None, None, None)
     pair = _dst(o_pair, (K, K, 4), device, torch.int64)

@@ -615,8 +615,9 @@ int dfd_confusion(const int64_t* truth, const int64_t* pred, int n, int J, int64
  * DFD_CALIB_MAX_BLOCKS; a workgroup strides over the rest), trips of the stage-2 loop (DFD_CALIB_STAGE2_WIDTH partials per
  * trip)} of both entry points above: host code, for the tests that name a tier.
  *
- * dfd_softmax_argmax_t: dfd_softmax_argmax of beta * z: p_j = exp((z_j - max_j z) * beta) / sum, beta = inv_temperature finite
- * and > 0 (else DFD_EINVAL); the same rules for non-finite rows and ties; at beta == 1.0f the same bits as dfd_softmax_argmax. */
+ * dfd_softmax_argmax_t (csrc/dfd_misc.hip, dfd_softmax_argmax's kernel): dfd_softmax_argmax of beta * z:
+ * p_j = exp((z_j - max_j z) * beta) / sum, beta = inv_temperature finite and > 0 (else DFD_EINVAL); the same rules for non-finite
+ * rows and ties; at beta == 1.0f the same bits as dfd_softmax_argmax. */
 #define DFD_CALIB_MAX_N (1 << 28)
 #define DFD_CALIB_MAX_J 1024
 #define DFD_CALIB_MAX_BINS 64
