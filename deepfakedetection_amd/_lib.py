@@ -181,6 +181,9 @@ SIGNATURES: dict[str, tuple] = {
     "dfd_fuse_nll": (c_int, [P, c_int, P, c_int, c_int, POINTER(c_double), c_int, P, c_size_t, P, P, P]),
     "dfd_fuse_agree": (c_int, [P, c_int, P, c_int, c_int, P, P, P, P]),
     "dfd_fuse_plan": (c_int, [c_int, c_int, c_int, _PI]),
+    # ---- ABI 152
+    "dfd_stem_bwd_fused_ok": (c_int, [c_int, POINTER(StemShape), P]),
+    "dfd_stem_bwd_fused": (c_int, [c_int, P, P, P, P, c_int, P, P, POINTER(StemShape), c_int, P, c_size_t, c_int, P]),
     # ---- ABI 111
     "dfd_bn_eval_coeffs_multi": (c_int, [P, c_int, P]),
     "dfd_sum_batch_begin": (c_int, []),

@@ -193,7 +193,7 @@ k_act_bn_bwd(const T* __restrict__ D, const T* __restrict__ y, const float* __re
                 acc[j] += d;
                 acc[V + j] += d * (yv[j] - mean[j]) * rstd[j];
             }
-            Vec<T>::store(dz + r * C + c0, dv);
+            if (dz) Vec<T>::store(dz + r * C + c0, dv);     // (uniform) NULL: the sums only
         }
     }
     reduce_rowlanes<2 * V>(acc, red, cm.cvb, cm.rpb, vl, rl, active);
@@ -583,7 +583,7 @@ static int act_bn_bwd_t(const void* D, const void* y, const float* gate, const f
 extern "C" int dfd_act_bn_bwd(int dtype, const void* D, const void* y, const float* gate, const float* dpool,
                               const float* bnstate, int act, void* dz, int N, int HW, int C, float* partials, int pcap,
                               int* nparts, dfd_stream stream) {
-    if (!shape_ok(dtype, N, HW, C) || !y || !bnstate || !dz || !partials || !nparts || pcap < 1) return DFD_EINVAL;
+    if (!shape_ok(dtype, N, HW, C) || !y || !bnstate || !partials || !nparts || pcap < 1) return DFD_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     return dtype == DFD_BF16
                ? act_bn_bwd_t<bf16>(D, y, gate, dpool, bnstate, act, dz, N, HW, C, partials, pcap, nparts, st)
@@ -757,4 +757,4 @@ extern "C" int dfd_bn_bwd_finalize(const float* partials, int nparts, int C, dou
                                   nullptr, accumulate, coef, stream);
 }
 
-extern "C" int dfd_version(void) { return 151; }   // see include/dfd_hip.h
+extern "C" int dfd_version(void) { return 152; }   // see include/dfd_hip.h

@@ -14,6 +14,8 @@
 // k = 24 + kh for r = 8 (forward: one 16-byte run per lane) / k = 9 kh + r (backward: per-pixel gathers).
 // Same products as the f32 kernels (bf16 operands, f32 accumulation), another summation order.
 // Shapes outside (bf16, k 3, stride 2, Cout % 16 == 0, Cout <= 64, W % 4 == 0) keep the dfd_misc.hip kernels.
+// Cout <= 32 (EfficientNet-B0..B2): k_stem_wgrad_fused makes the weight gradient straight from the incoming gradient g, so the
+// stage's dz tensor is never stored (same bits as the pair of kernels it replaces).
 #include "dfd_common.h"
 #include "dfd_pw.h"
 
@@ -292,6 +294,189 @@ k_stem_wgrad_mfma(const float* __restrict__ x, const unsigned short* __restrict_
     }
 }
 
+// ---------------------------------------------------------------- weight gradient straight from g (no stored dz, ABI 152)
+// k_stem_wgrad_mfma<CT, true> with its dz operand recomputed: dz = act'(scale y + shift) g, rounded to bf16 operation for operation
+// as k_act_bn_bwd stores it, then the BatchNorm-backward map gm = a dz + b y + c and its rounding as in k_stem_wgrad_mfma.  The LDS
+// image, the MFMA order, the grid and the slab are that kernel's, so dw has the bits of dfd_act_bn_bwd + dfd_stem_conv_wgrad; the
+// dz tensor (205 MB at batch 256 x 224^2) is neither written nor read: the sums come from dfd_act_bn_bwd with dz = NULL.
+// What the one-buffer kernel leaves on the table is taken here: the next step's g, y and x vectors are loaded into registers
+// (clamped coordinates, no divergent branch around a load) before the current step's MFMA phase and are in flight while it runs.
+template <int CT, int ACT>
+__global__ void __launch_bounds__(DFD_THREADS)
+k_stem_wgrad_fused(const float* __restrict__ x, const unsigned short* __restrict__ gr, const unsigned short* __restrict__ yraw,
+                   const float* __restrict__ bnstate, const float* __restrict__ coef, dfd_stem_shape s, int RP, int WoP,
+                   float* __restrict__ ws) {
+    extern __shared__ __attribute__((aligned(16))) unsigned short smem_s[];
+    constexpr int RS = 2 * (STM_BROWS - 1) + 3;
+    constexpr int Co = 16 * CT, PITCH = Co + 16, CV = Co / 8;
+    constexpr int DV = 4, XV = 4;                         // prefetched 16-byte vectors per lane: g, y (each DV) and x (XV)
+    static_assert(DFD_THREADS % CV == 0, "a lane keeps one channel vector");
+    unsigned short* xrow = smem_s;                        // [RS][RP]
+    unsigned short* dzt = smem_s + ((RS * RP + 7) & ~7);  // [STM_BROWS][WoP][PITCH]
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c16 = lane & 15, g = lane >> 4, q = c16 >> 2, p = c16 & 3;
+    const int row = wave >> 1, half = wave & 1;
+    for (int i = threadIdx.x; i < RS * RP; i += DFD_THREADS) xrow[i] = 0;
+    for (int i = threadIdx.x; i < STM_BROWS * WoP * PITCH / 2; i += DFD_THREADS) reinterpret_cast<unsigned*>(dzt)[i] = 0u;   // pixels >= Wo stay zero
+    f32x4_t acc[CT][2];
+#pragma unroll
+    for (int t = 0; t < CT; ++t) { acc[t][0] = (f32x4_t){0.f, 0.f, 0.f, 0.f}; acc[t][1] = (f32x4_t){0.f, 0.f, 0.f, 0.f}; }
+    const int v = threadIdx.x % CV;                       // the lane's channel vector (fixed: 256 % CV == 0)
+    float sc[8], sh[8], ka[8], kb[8], kc[8];
+    load_f32<8>(bnstate + v * 8, sc); load_f32<8>(bnstate + Co + v * 8, sh);
+    load_f32<8>(coef + v * 8, ka); load_f32<8>(coef + Co + v * 8, kb); load_f32<8>(coef + 2 * Co + v * 8, kc);
+    const int groups = (s.Ho + STM_BROWS - 1) / STM_BROWS;
+    const long nsteps = (long)s.N * groups;
+    const int ksteps = WoP >> 5;
+    int boff[2];
+    bool bon[2];
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+        const int k = c16 + 16 * nt, kh = k / 9, r = k - 9 * kh;
+        bon[nt] = k < 27;
+        boff[nt] = bon[nt] ? (2 * row + kh) * RP + r : 0;
+    }
+    // the lane's items do not depend on the step: (row, column) of its g / y vectors and of its x vectors, clamped into the step
+    const int dtotal = STM_BROWS * s.Wo * CV, vpr = (s.W * 3) >> 2, xtotal = RS * vpr;
+    int drow_[DV], dcol[DV], ddst[DV], xr_[XV], xcol[XV], xdst[XV];
+#pragma unroll
+    for (int u = 0; u < DV; ++u) {
+        const int i = threadIdx.x + u * DFD_THREADS, ic = i < dtotal ? i : dtotal - 1;
+        const int pix = ic / CV, r = pix / s.Wo, ox = pix - r * s.Wo;
+        drow_[u] = r; dcol[u] = ox * Co + v * 8;
+        ddst[u] = i < dtotal ? (r * WoP + ox) * PITCH + v * 8 : -1;
+    }
+#pragma unroll
+    for (int u = 0; u < XV; ++u) {
+        const int i = threadIdx.x + u * DFD_THREADS, ic = i < xtotal ? i : xtotal - 1;
+        const int r = ic / vpr, c = ic - r * vpr;
+        xr_[u] = r; xcol[u] = 4 * c;
+        xdst[u] = i < xtotal ? r * RP + 3 * s.pad_left + 4 * c : -1;
+    }
+    uint4 dg[DV], dy[DV];
+    float4 xv[XV];
+    auto fetch = [&](long step) {
+        const long n = step / groups;
+        const int oy0 = (int)(step - n * groups) * STM_BROWS, iy0 = oy0 * 2 - s.pad_top;
+#pragma unroll
+        for (int u = 0; u < DV; ++u) {
+            int oy = oy0 + drow_[u];
+            oy = oy < s.Ho ? oy : s.Ho - 1;
+            const long off = ((n * s.Ho + oy) * (long)s.Wo) * Co + dcol[u];
+            dg[u] = *reinterpret_cast<const uint4*>(gr + off);
+            dy[u] = *reinterpret_cast<const uint4*>(yraw + off);
+        }
+#pragma unroll
+        for (int u = 0; u < XV; ++u) {
+            int iy = iy0 + xr_[u];
+            iy = iy < 0 ? 0 : (iy < s.H ? iy : s.H - 1);
+            xv[u] = *reinterpret_cast<const float4*>(x + ((n * s.H + iy) * (long)s.W) * 3 + xcol[u]);
+        }
+    };
+    // gm of one (g, y) vector pair -> the image: k_act_bn_bwd's dz (MODE 0), then k_stem_wgrad_mfma's map, rounding for rounding
+    auto put = [&](int dst, bool on, const uint4& a, const uint4& b) {
+        uint4 o = make_uint4(0, 0, 0, 0);
+        if (on) {
+            float f[8], f2[8];
+            Vec<bf16>::unpack(a, f);
+            Vec<bf16>::unpack(b, f2);
+#pragma unroll
+            for (int j = 0; j < 8; j += 2) {
+                const dfd_f2 z2 = __builtin_elementwise_fma((dfd_f2){sc[j], sc[j + 1]}, (dfd_f2){f2[j], f2[j + 1]}, (dfd_f2){sh[j], sh[j + 1]});
+                const dfd_f2 g2 = act_grad2<ACT>(z2);
+                f[j] = round_to<bf16>(f[j] * g2.x); f[j + 1] = round_to<bf16>(f[j + 1] * g2.y);
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) f[j] = fmaf(ka[j], f[j], fmaf(kb[j], f2[j], kc[j]));
+            o = Vec<bf16>::pack(f);
+        }
+        *reinterpret_cast<uint4*>(dzt + dst) = o;
+    };
+    long step = blockIdx.x;
+    fetch(step);
+    for (; step < nsteps; step += gridDim.x) {
+        const long n = step / groups;
+        const int oy0 = (int)(step - n * groups) * STM_BROWS, iy0 = oy0 * 2 - s.pad_top;
+        __syncthreads();                                  // the previous step's MFMA phase has read the image and the rows
+#pragma unroll
+        for (int u = 0; u < DV; ++u)
+            if (ddst[u] >= 0) put(ddst[u], oy0 + drow_[u] < s.Ho, dg[u], dy[u]);
+#pragma unroll
+        for (int u = 0; u < XV; ++u)
+            if (xdst[u] >= 0) {
+                const int iy = iy0 + xr_[u];
+                const bool on = iy >= 0 && iy < s.H;
+                unsigned short* d = xrow + xdst[u];
+                d[0] = on ? st_f2bf(xv[u].x) : (unsigned short)0; d[1] = on ? st_f2bf(xv[u].y) : (unsigned short)0;
+                d[2] = on ? st_f2bf(xv[u].z) : (unsigned short)0; d[3] = on ? st_f2bf(xv[u].w) : (unsigned short)0;
+            }
+        for (int i = threadIdx.x + DV * DFD_THREADS; i < dtotal; i += DFD_THREADS) {       // wider images than DV covers (not prefetched)
+            const int pix = i / CV, r = pix / s.Wo, ox = pix - r * s.Wo;
+            const bool on = oy0 + r < s.Ho;
+            uint4 a = make_uint4(0, 0, 0, 0), b = a;
+            if (on) {
+                const long off = ((n * s.Ho + oy0 + r) * (long)s.Wo + ox) * Co + v * 8;
+                a = *reinterpret_cast<const uint4*>(gr + off);
+                b = *reinterpret_cast<const uint4*>(yraw + off);
+            }
+            put((r * WoP + ox) * PITCH + v * 8, on, a, b);
+        }
+        for (int i = threadIdx.x + XV * DFD_THREADS; i < xtotal; i += DFD_THREADS) {
+            const int r = i / vpr, c = i - r * vpr, iy = iy0 + r;
+            float4 w4 = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (iy >= 0 && iy < s.H) w4 = *reinterpret_cast<const float4*>(x + ((n * s.H + iy) * (long)s.W) * 3 + 4 * c);
+            unsigned short* d = xrow + r * RP + 3 * s.pad_left + 4 * c;
+            d[0] = st_f2bf(w4.x); d[1] = st_f2bf(w4.y); d[2] = st_f2bf(w4.z); d[3] = st_f2bf(w4.w);
+        }
+        if (step + gridDim.x < nsteps) fetch(step + gridDim.x);  // (uniform) in flight during the MFMA phase below
+        __syncthreads();
+        // ---- k-step = 32 pixels of the wave's row; slot (g, j) = pixel 32 ks + 16 (j >> 2) + 4 g + (j & 3)
+        const unsigned short* drow = dzt + row * WoP * PITCH;
+        for (int ks = half; ks < ksteps; ks += 2) {
+            bf16x8_t bfr[2];
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) {
+                unsigned short e[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int px = 32 * ks + 16 * (j >> 2) + 4 * g + (j & 3);
+                    e[j] = xrow[boff[nt] + 6 * px];
+                }
+                uint4 qq = make_uint4((unsigned)e[0] | ((unsigned)e[1] << 16), (unsigned)e[2] | ((unsigned)e[3] << 16),
+                                      (unsigned)e[4] | ((unsigned)e[5] << 16), (unsigned)e[6] | ((unsigned)e[7] << 16));
+                if (!bon[nt]) qq = make_uint4(0, 0, 0, 0);
+                bfr[nt] = __builtin_bit_cast(bf16x8_t, qq);
+            }
+#pragma unroll
+            for (int t = 0; t < CT; ++t) {
+                const unsigned short* a = drow + (32 * ks + 4 * g + q) * PITCH + 16 * t + 4 * p;
+                const short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((st_lds_short4*)(a));
+                const short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((st_lds_short4*)(a + 16 * PITCH));
+                const bf16x8_t af = __builtin_bit_cast(bf16x8_t, (short8_t){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
+                acc[t][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bfr[0], acc[t][0], 0, 0, 0);
+                acc[t][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bfr[1], acc[t][1], 0, 0, 0);
+            }
+        }
+    }
+    // ---- the four waves' partial sums through LDS (fixed order), written in torch's tap order (ci, kh, kw): as k_stem_wgrad_mfma
+    __syncthreads();
+    float* red = reinterpret_cast<float*>(dzt);           // [4][Co][32]
+#pragma unroll
+    for (int t = 0; t < CT; ++t)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) red[(wave * Co + 16 * t + 4 * g + r) * 32 + 16 * nt + c16] = acc[t][nt][r];
+    __syncthreads();
+    float* o = ws + (long)blockIdx.x * Co * 27;
+    for (int i = threadIdx.x; i < Co * 27; i += DFD_THREADS) {
+        const int co = i / 27, k = i - co * 27, kh = k / 9, r = k - 9 * kh, kw = r / 3, ci = r - 3 * kw;
+        float sum = 0.f;
+#pragma unroll
+        for (int wv = 0; wv < 4; ++wv) sum += red[(wv * Co + co) * 32 + k];
+        o[co * 27 + (ci * 3 + kh) * 3 + kw] = sum;
+    }
+}
+
 // ----------------------------------------------------------------------------------------------------------------- host
 static bool stem_mfma_ok(const dfd_stem_shape* s, const void* x) {
     return s->k == 3 && s->stride == 2 && s->Cout % 16 == 0 && s->Cout <= 64 && s->W % 4 == 0 && ((size_t)x & 15) == 0 &&
@@ -350,4 +535,44 @@ int dfd_stem_wgrad_mfma(const float* x, const void* dz, const void* yraw, const 
     switch (Co / 16) { case 1: STW(1); break; case 2: STW(2); break; case 3: STW(3); break; default: STW(4); break; }
 #undef STW
     return DFD_CHECK_LAUNCH();
+}
+
+// ---- the weight gradient straight from g (include/dfd_hip.h, ABI 152): dfd_stem_wgrad_mfma's plan, so the same bits
+static bool stem_fused_ok(int dtype, const dfd_stem_shape* s, const void* x) {
+    if (dtype != DFD_BF16 || !s || s->N < 1 || s->H < 1 || s->W < 1 || s->Ho < 1 || s->Wo < 1 || s->pad_top < 0 || s->pad_left < 0) return false;
+    return stem_mfma_ok(s, x) && s->Cout <= 32;
+}
+extern "C" int dfd_stem_bwd_fused_ok(int dtype, const dfd_stem_shape* s, const float* x) {
+    if (!stem_fused_ok(dtype, s, x)) return 0;
+    const int RP = stem_row_pitch(s, 32), WoP = ((s->Wo + 31) / 32) * 32;
+    size_t dzt = (size_t)STM_BROWS * WoP * (s->Cout + 16) * 2;
+    if (dzt < (size_t)4 * s->Cout * 32 * 4) dzt = (size_t)4 * s->Cout * 32 * 4;
+    return ((((size_t)(2 * (STM_BROWS - 1) + 3) * RP + 7) & ~(size_t)7) * 2 + dzt <= 64 * 1024) ? 1 : 0;
+}
+extern "C" int dfd_stem_bwd_fused(int dtype, const float* x, const void* g, const void* y, const float* bnstate, int act,
+                                  const float* coef, float* dw, const dfd_stem_shape* s, int accumulate, float* ws, size_t ws_bytes,
+                                  int max_rows, dfd_stream stream) {
+    if (!x || !g || !y || !bnstate || !coef || !dw || !s || !ws) return DFD_EINVAL;
+    if (!dfd_stem_bwd_fused_ok(dtype, s, x) || (((size_t)g | (size_t)y) & 15)) return DFD_EUNSUPPORTED;
+    if (act != DFD_ACT_NONE && act != DFD_ACT_SILU && act != DFD_ACT_RELU && act != DFD_ACT_GELU) return DFD_EUNSUPPORTED;
+    const int RP = stem_row_pitch(s, 32), WoP = ((s->Wo + 31) / 32) * 32, Co = s->Cout;
+    constexpr int RS = 2 * (STM_BROWS - 1) + 3;
+    size_t dzt = (size_t)STM_BROWS * WoP * (Co + 16) * 2;
+    if (dzt < (size_t)4 * Co * 32 * 4) dzt = (size_t)4 * Co * 32 * 4;
+    const size_t lds = (((size_t)RS * RP + 7) & ~(size_t)7) * 2 + dzt;
+    const long nsteps = (long)s->N * ((s->Ho + STM_BROWS - 1) / STM_BROWS);
+    long P = 768;                                         // dfd_stem_wgrad_mfma's grid: the slab rows, and so the bits, are its own
+    if (max_rows > 0 && P > max_rows) P = max_rows;
+    if (P > nsteps) P = nsteps;
+    if ((size_t)(P + P / 32 + 2) * Co * 27 * 4 > ws_bytes) return DFD_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+#define STB(CT) hipLaunchKernelGGL((k_stem_wgrad_fused<CT, ACT>), dim3((unsigned)P), dim3(DFD_THREADS), lds, st, x, (const unsigned short*)g, \
+                                   (const unsigned short*)y, bnstate, coef, *s, RP, WoP, ws)
+    DISPATCH_ACT(act, {
+        if (Co == 16) STB(1);
+        else STB(2);
+    });
+#undef STB
+    if (hipGetLastError() != hipSuccess) return DFD_ELAUNCH;
+    return dfd_launch_sum_partials(ws, (int)P, (long)Co * 27, dw, accumulate, st);
 }

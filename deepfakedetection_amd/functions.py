@@ -232,6 +232,14 @@ class StemFunction(torch.autograd.Function):
         x, y, st, *t = ctx.saved_tensors
         L = cut_layers(("conv",), t, ctx.needs_input_grad[1:], 0, None, bias=False)["conv"]
         geom = cfg.geom
+        pads = (geom.kernel, geom.stride, geom.pad_lead, geom.pad_lead)
+        if L.need_w and K.stem_bwd_fused_ok(x, y, *pads):
+            # dz has one consumer, the weight gradient, which recomputes it from g and y: the sums only, no dz tensor (same bits)
+            g = _c(g)
+            _, parts, n = K.act_bn_bwd(g, y, None, None, st, ACT_SILU, want_dz=False)
+            coef = bn_backward(L, parts, n, _rows(y), st, cfg.training)
+            L.dw = K.stem_bwd_fused(x, g, y, st, ACT_SILU, coef, *pads, _slot(L.w, True, tuple(L.w.shape)))
+            return (None, *L.grads(bias=False), None)
         dz, parts, n = K.act_bn_bwd(_c(g), y, None, None, st, ACT_SILU)
         coef = bn_backward(L, parts, n, _rows(y), st, cfg.training)
         if L.need_w:

@@ -464,14 +464,15 @@ def bias_grad(g: torch.Tensor, row_scale: torch.Tensor | None = None, out: torch
 
 
 def act_bn_bwd(D: torch.Tensor | None, y: torch.Tensor, gate: torch.Tensor | None, dpool: torch.Tensor | None,
-               state: torch.Tensor, act: int, se_job: tuple | None = None):
+               state: torch.Tensor, act: int, se_job: tuple | None = None, want_dz: bool = True):
     """se_job: what se_bwd(defer_wgrad=True) returned — the block's squeeze-excite FC weight gradients then ride along as extra
-    workgroups of this launch (dfd_act_bn_bwd_se) instead of being a launch of their own."""
+    workgroups of this launch (dfd_act_bn_bwd_se) instead of being a launch of their own.
+    want_dz=False (not with se_job): the partial sums only, dz is None and is not written (its consumer recomputes it: stem_bwd_fused)."""
     _chk_nhwc(y)
     N, H, W, C = y.shape
     if _passenger_task is not None and torch._C._current_graph_task_id() != _passenger_task:
         drop_passengers()               # parked by a backward pass that never reached its flush: this launch must not carry them
-    dz = torch.empty_like(y)
+    dz = torch.empty_like(y) if want_dz or se_job is not None else None
     parts = partials_buf(y.device, C)
     n = ctypes.c_int(0)
     if se_job is not None:
@@ -1113,6 +1114,32 @@ def stem_conv_wgrad(x: torch.Tensor, dz: torch.Tensor, y: torch.Tensor | None, c
     dw = _dst(out, (Cout, 3, k, k), dz.device)
     check(_L().dfd_stem_conv_wgrad(_dt(dz), _p(x), _p(dz), _p(y), _p(coef), _p(dw), ctypes.byref(shp), 0, _p(ws),
                                    ws.numel() * 4, _stream()), "dfd_stem_conv_wgrad")
+    return dw
+
+
+def stem_bwd_fused_ok(x: torch.Tensor, y: torch.Tensor, k: int, stride: int, pad_top: int, pad_left: int) -> bool:
+    """Whether stem_bwd_fused serves this stem (bf16, 16 or 32 output channels, the matrix-core weight-gradient shapes)."""
+    if y.dtype != torch.bfloat16 or y.dim() != 4 or not y.is_contiguous():
+        return False
+    shp = _stem_shape(x.shape, y.shape[3], y.shape[1], y.shape[2], k, stride, pad_top, pad_left)
+    return bool(_L().dfd_stem_bwd_fused_ok(_dt(y), ctypes.byref(shp), _p(x)))
+
+
+def stem_bwd_fused(x: torch.Tensor, g: torch.Tensor, y: torch.Tensor, state: torch.Tensor, act: int, coef: torch.Tensor, k: int,
+                   stride: int, pad_top: int, pad_left: int, out: torch.Tensor | None = None, max_rows: int = 0) -> torch.Tensor:
+    """The stem's weight gradient straight from the incoming gradient g (dfd_stem_bwd_fused): the kernel recomputes the dz that
+    act_bn_bwd(g, y, state, act) would have stored, so that tensor never exists; same bits as act_bn_bwd + stem_conv_wgrad.
+    coef: bn_bwd_finalize over the partial rows of act_bn_bwd(..., want_dz=False).  Only where stem_bwd_fused_ok says so."""
+    _chk_nhwc(y)
+    if g.shape != y.shape or g.dtype != y.dtype or not g.is_contiguous():
+        raise ValueError("stem_bwd_fused: g must be a contiguous tensor of y's shape and dtype")
+    Cout, Ho, Wo = y.shape[3], y.shape[1], y.shape[2]
+    shp = _stem_shape(x.shape, Cout, Ho, Wo, k, stride, pad_top, pad_left)
+    nbytes = _L().dfd_stem_conv_wgrad_ws(ctypes.byref(shp))
+    ws = scratch(y.device, "wgrad_ws", nbytes)
+    dw = _dst(out, (Cout, 3, k, k), y.device)
+    check(_L().dfd_stem_bwd_fused(_dt(y), _p(x), _p(g), _p(y), _p(state), act, _p(coef), _p(dw), ctypes.byref(shp), 0, _p(ws),
+                                  ws.numel() * 4, max_rows, _stream()), "dfd_stem_bwd_fused", str(tuple(y.shape)))
     return dw
 
 
@@ -2109,7 +2136,7 @@ class DeviceRng:
 _profile_sink: list | None = None
 _TIMED = ("bn_act_apply", "bn_bwd_reduce", "act_bn_bwd", "pool_act", "pool_bwd_reduce", "scale_rows", "dwconv_fwd",
           "dwconv_bwd_data", "dwconv_bwd_weight", "pwconv", "pwconv_wgrad", "pwconv_bwd_fused", "stem_conv_fwd", "stem_conv_wgrad",
-          "se_fc_fwd", "se_fc_bwd", "linear_fwd", "linear_bwd", "ce_loss", "adamw_step", "prep_weights", "bn_finalize",
+          "stem_bwd_fused", "se_fc_fwd", "se_fc_bwd", "linear_fwd", "linear_bwd", "ce_loss", "adamw_step", "prep_weights", "bn_finalize",
           "bn_bwd_finalize", "dropout", "bgemm", "attn_scores", "attn_apply", "attn_softmax_fwd", "attn_softmax_bwd", "im2col", "col2im",
           "wattn_fwd", "wattn_bwd", "mx_quant_rows", "mx_gemm",
           "bn_add_act", "bn_add_act_bwd", "affine2_apply", "up2_act_fwd", "up2_act_bwd", "layernorm_fwd", "layernorm_bwd",

@@ -101,7 +101,9 @@ typedef void* dfd_stream;          /* a hipStream_t */
  * 150 = dfd_calib_bins / _ws, dfd_calib_nll / _ws, dfd_calib_plan, dfd_softmax_argmax_t (reliability bins, Brier sum, NLL of
  * temperature-scaled logits with two derivatives, softmax / arg max at a temperature); dfd_softmax_argmax itself is unchanged;
  * 151 = dfd_fuse_scores, dfd_fuse_nll / _ws, dfd_fuse_agree, dfd_fuse_plan (the ensemble of K models: fused scores of a logit or a
- * probability pool, the pool's NLL with gradient and Hessian in its coefficients, right / wrong agreement tables). */
+ * probability pool, the pool's NLL with gradient and Hessian in its coefficients, right / wrong agreement tables);
+ * 152 = dfd_stem_bwd_fused / _ok (the stem's weight gradient straight from the incoming gradient, without a stored dz; same bits as
+ * dfd_act_bn_bwd + dfd_stem_conv_wgrad); dfd_act_bn_bwd takes dz = NULL: the partial sums only. */
 int dfd_version(void);
 
 /* Planner knobs: the tier switches and grid sizes by which tests and per-layer scripts reach a kernel tier.  Process-wide plain ints:
@@ -218,7 +220,8 @@ int dfd_bias_grad(int dtype, const void* g, const float* row_scale, int N, int H
                   float* ws, size_t ws_bytes, dfd_stream stream);
 /* dz = (D*gate[n,c] + dpool[n,c]/HW) * act'(scale*y+shift); writes dz and the partial
  * sums (dz, dz*xhat).  D, gate, dpool are each optional (NULL): D==NULL means the
- * incoming gradient is dpool/HW only (global-average-pool backward).             */
+ * incoming gradient is dpool/HW only (global-average-pool backward).  dz == NULL
+ * (ABI 152): the same partial sums, dz is not written.                           */
 int dfd_act_bn_bwd(int dtype, const void* D, const void* y, const float* gate,
                    const float* dpool, const float* bnstate, int act, void* dz,
                    int N, int HW, int C, float* partials, int pcap, int* nparts,
@@ -400,6 +403,17 @@ int dfd_stem_conv_wgrad(int dtype, const float* x, const void* dz, const void* y
                         const float* coef, float* dw, const dfd_stem_shape* s,
                         int accumulate, float* ws, size_t ws_bytes, dfd_stream stream);
 size_t dfd_stem_conv_wgrad_ws(const dfd_stem_shape* s);
+/* The stem's weight gradient straight from g (ABI 152; bf16, Cout 16 or 32, the shapes of dfd_stem_conv_wgrad's matrix-core kernel:
+ * dfd_stem_bwd_fused_ok says 1; everything else: DFD_EUNSUPPORTED, nothing launched).  g = d loss / d act(BN(y)), y the raw convolution
+ * output, bnstate the forward's (scale, shift, mean, rstd), coef the (a, b, c) of dfd_bn_bwd_finalize_ex.  The kernel recomputes
+ * dz = act'(scale y + shift) g as dfd_act_bn_bwd (D = g, no gate, no dpool) rounds and stores it, and applies a dz + b y + c as
+ * dfd_stem_conv_wgrad does: dw has the bits of that pair of calls, and the dz tensor does not exist.  The sums for coef come from
+ * dfd_act_bn_bwd with dz = NULL (ABI 152: the sums only, same partial rows).  ws: dfd_stem_conv_wgrad_ws bytes; the final
+ * summation joins an open dfd_sum_batch like dfd_stem_conv_wgrad's.  max_rows > 0 caps the grid (tests; another summation order). */
+int dfd_stem_bwd_fused_ok(int dtype, const dfd_stem_shape* s, const float* x);
+int dfd_stem_bwd_fused(int dtype, const float* x, const void* g, const void* y, const float* bnstate, int act,
+                       const float* coef, float* dw, const dfd_stem_shape* s, int accumulate, float* ws,
+                       size_t ws_bytes, int max_rows, dfd_stream stream);
 
 /* ------------------------------------------------- classifier, loss, optimizer --- */
 /* out = u >= p ? x/(1-p) : 0   (forward and, with x = grad, backward)              */
