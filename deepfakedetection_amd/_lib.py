@@ -7,7 +7,7 @@ symbol cannot be resolved, importing/using the kernels raises immediately.
 from __future__ import annotations
 
 import ctypes
-from ctypes import POINTER, Structure, c_double, c_float, c_int, c_int64, c_long, c_size_t, c_uint32, c_void_p
+from ctypes import POINTER, Structure, c_double, c_float, c_int, c_int64, c_long, c_size_t, c_uint32, c_uint64, c_void_p
 from pathlib import Path
 
 import os as _os
@@ -66,6 +66,17 @@ FUSE_MAX_BLOCKS = 1024              # stage-1 workgroups at most
 FUSE_STAGE2_WIDTH = 64              # partials the stage-2 loop takes per trip
 FUSE_LAYOUT_THREAD, FUSE_LAYOUT_WAVE = 0, 1
 FUSE_LOGIT, FUSE_PROB = 0, 1
+# csrc/dfd_boot.hip (the DFD_BOOT_* constants of include/dfd_hip.h)
+BOOT_STREAM = 0x626F6F74            # "boot": the last counter word of every bootstrap draw
+BOOT_MAX_N = 1 << 24
+BOOT_MAX_REPLICATES = 65536
+BOOT_MAX_MEMBERS = 8
+BOOT_STATS_LEN = 10
+(BOOT_P, BOOT_N, BOOT_TWO_U, BOOT_TP, BOOT_FP, BOOT_HITS, BOOT_F0, BOOT_T0, BOOT_F1, BOOT_T1) = range(10)
+BOOT_SCRATCH_BYTES = 512            # reduction scratch in front of the LDS tier's counts
+BOOT_LDS_MAX_N = (160 * 1024 - BOOT_SCRATCH_BYTES) // 4       # largest n whose uint32 counts stay in one workgroup's LDS
+BOOT_DRAW_TILE = 4096               # draws per workgroup of the global tier's draw kernel
+BOOT_TIER_LDS, BOOT_TIER_GLOBAL = 0, 1
 
 
 class DwShape(Structure):
@@ -184,6 +195,11 @@ SIGNATURES: dict[str, tuple] = {
     # ---- ABI 152
     "dfd_stem_bwd_fused_ok": (c_int, [c_int, POINTER(StemShape), P]),
     "dfd_stem_bwd_fused": (c_int, [c_int, P, P, P, P, c_int, P, P, POINTER(StemShape), c_int, P, c_size_t, c_int, P]),
+    # ---- ABI 153
+    "dfd_boot_ws": (c_size_t, [c_int, c_int]),
+    "dfd_boot_plan": (c_int, [c_int, c_int, c_int, c_size_t, _PI]),
+    "dfd_boot_counts": (c_int, [c_int, c_int, c_int, c_uint64, P, P]),
+    "dfd_boot_stats": (c_int, [P, P, c_int, P, P, POINTER(c_double), c_int, c_int, c_uint64, P, c_size_t, P, P]),
     # ---- ABI 111
     "dfd_bn_eval_coeffs_multi": (c_int, [P, c_int, P]),
     "dfd_sum_batch_begin": (c_int, []),

@@ -9,6 +9,7 @@
 //   * bookkeeping kernels that keep ATen off the model path: Philox uniforms, counter bumps, axpby.
 // Layout conventions: see dfd_common.h (NHWC activations, 16 bytes per lane, f32 statistics).
 #include "dfd_common.h"
+#include "dfd_philox.h"
 
 // ===========================================================================
 // bookkeeping
@@ -53,17 +54,7 @@ extern "C" int dfd_add(int dtype, const void* a, const void* b, void* out, long 
     return DFD_CHECK_LAUNCH();
 }
 
-// Philox4x32-10 (Salmon et al., SC'11): key = seed, counter = (offset lo, offset hi, stream id, block index)
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
+// Philox4x32-10 (dfd_philox.h): key = seed, counter = (offset lo, offset hi, stream id, block index)
 // keep <= 0: out[i] = U[0,1); keep > 0: out[i] = floor(keep + u) / keep (drop-path row scale)
 __global__ void k_rand(const uint64_t* __restrict__ state, uint32_t stream_id, float keep, float* __restrict__ out, long n) {
     const uint64_t seed = state[0], off = state[1];

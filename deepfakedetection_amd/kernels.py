@@ -1545,6 +1545,106 @@ def fuse_agree(preds_list, targets: torch.Tensor, num_classes: int, out=None):
     return pair, hist, stats
 
 
+# ------------------------------------------------------------------ the bootstrap (ABI 153, csrc/dfd_boot.hip)
+BOOT_STREAM, BOOT_MAX_N, BOOT_MAX_REPLICATES, BOOT_MAX_MEMBERS = _lib.BOOT_STREAM, _lib.BOOT_MAX_N, _lib.BOOT_MAX_REPLICATES, _lib.BOOT_MAX_MEMBERS
+BOOT_STATS_LEN, BOOT_LDS_MAX_N, BOOT_DRAW_TILE = _lib.BOOT_STATS_LEN, _lib.BOOT_LDS_MAX_N, _lib.BOOT_DRAW_TILE
+BOOT_TIER_LDS, BOOT_TIER_GLOBAL = _lib.BOOT_TIER_LDS, _lib.BOOT_TIER_GLOBAL
+(BOOT_P, BOOT_N, BOOT_TWO_U, BOOT_TP, BOOT_FP, BOOT_HITS, BOOT_F0, BOOT_T0, BOOT_F1, BOOT_T1) = range(BOOT_STATS_LEN)
+BOOT_WS_CAP = 1 << 30               # the largest workspace boot_stats allocates by itself: more resamples mean more passes
+
+
+@dataclass(frozen=True)
+class BootPlan:
+    """dfd_boot_plan's answer: the tier, the resamples per pass, the passes and the draw tiles per resample."""
+
+    tier: int
+    per_pass: int
+    passes: int
+    draw_tiles: int
+
+
+def _boot_shape(op: str, n: int, B: int, M: int = 1) -> None:
+    if not 0 <= n <= BOOT_MAX_N or not 1 <= B <= BOOT_MAX_REPLICATES or not 1 <= M <= BOOT_MAX_MEMBERS:
+        raise ValueError(f"{op}: takes 0..{BOOT_MAX_N} samples, 1..{BOOT_MAX_REPLICATES} resamples and 1..{BOOT_MAX_MEMBERS} members, "
+                         f"got {n}, {B}, {M}")
+
+
+def _boot_seed(op: str, seed: int) -> int:
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"{op}: the seed is an unsigned 64-bit integer, got {seed}")
+    return seed
+
+
+def boot_ws(n: int, B: int) -> int:
+    """Bytes of workspace with which boot_stats runs B resamples of n samples in one pass (0 in the LDS tier)."""
+    _boot_shape("boot_ws", n, B)
+    return _L().dfd_boot_ws(int(n), int(B))
+
+
+def boot_plan(n: int, B: int, M: int = 1, ws_bytes: int | None = None) -> BootPlan:
+    """Which tier boot_stats runs for B resamples of n samples from M members in a workspace of ws_bytes (default: what boot_stats
+    allocates by itself), and in how many passes (host code)."""
+    _boot_shape("boot_plan", n, B, M)
+    if ws_bytes is None:
+        ws_bytes = _boot_default_ws(n, B)
+    out = (ctypes.c_int * 4)()
+    check(_L().dfd_boot_plan(int(n), int(B), int(M), int(ws_bytes), out), "dfd_boot_plan", f"n={n} B={B} M={M} ws={ws_bytes}")
+    return BootPlan(*out)
+
+
+def _boot_default_ws(n: int, B: int) -> int:
+    need = boot_ws(n, B)
+    return need if need <= BOOT_WS_CAP else max(BOOT_WS_CAP // (4 * n), 1) * 4 * n
+
+
+def boot_counts(n: int, b0: int, R: int, seed: int, device, out: torch.Tensor | None = None) -> torch.Tensor:
+    """int32 [R, n] (the bits of the kernel's uint32): how often each of n samples is drawn in resamples b0 .. b0 + R - 1 under
+    `seed` (the resampling rule of include/dfd_hip.h), by the global tier's zero and draw launches."""
+    n, b0, R = int(n), int(b0), int(R)
+    if not 0 <= n <= BOOT_MAX_N or b0 < 0 or R < 1 or b0 + R > BOOT_MAX_REPLICATES:
+        raise ValueError(f"boot_counts: takes 0..{BOOT_MAX_N} samples and resamples inside 0..{BOOT_MAX_REPLICATES}, got {n}, {b0}, {R}")
+    counts = _dst(out, (R, n), torch.device(device), torch.int32)
+    check(_L().dfd_boot_counts(n, b0, R, _boot_seed("boot_counts", seed), _p(counts), _stream()), "dfd_boot_counts", f"n={n} b0={b0} R={R}")
+    return counts
+
+
+def boot_stats(sorted_scores, perms, is_positive: torch.Tensor, replicates: int, seed: int = 0, cuts=None, hit: torch.Tensor | None = None,
+               ws: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """M members' f32 [n] scores sorted ascending and the int32 [n] permutations that sorted them, uint8 [n] is_positive (and
+    optionally uint8 [n] hit) in sample order -> int64 [M, B, BOOT_STATS_LEN] = P, N, two_u, tp, fp, hits, f0, t0, f1, t1 of
+    every bootstrap resample (include/dfd_hip.h).  cuts: one float or None per member (None: no cut).  `ws`: uint8 scratch for the
+    global tier, at least 4 n bytes (one resample per pass); by default boot_ws(n, B) bytes capped at BOOT_WS_CAP.  No host sync."""
+    members, perm_list = list(sorted_scores), list(perms)
+    M, B = len(members), int(replicates)
+    if not 1 <= M <= BOOT_MAX_MEMBERS or len(perm_list) != M:
+        raise ValueError(f"boot_stats: takes 1..{BOOT_MAX_MEMBERS} members with one permutation each, got {M} and {len(perm_list)}")
+    n, device = members[0].numel(), members[0].device
+    _boot_shape("boot_stats", n, B, M)
+    seed = _boot_seed("boot_stats", seed)
+    for group, dtype in ((members, torch.float32), (perm_list, torch.int32)):
+        for t in group:
+            if t.dtype != dtype or tuple(t.shape) != (n,) or t.device != device:
+                raise ValueError(f"boot_stats: expected f32 [{n}] scores and int32 [{n}] permutations on {device}, got {t.dtype} {tuple(t.shape)}")
+    for name, t in (("is_positive", is_positive), ("hit", hit)):
+        if t is not None and (t.dtype != torch.uint8 or tuple(t.shape) != (n,) or t.device != device):
+            raise ValueError(f"boot_stats: {name} must be uint8 [{n}] on {device}, got {t.dtype} {tuple(t.shape)}")
+    values = [float("nan")] * M if cuts is None else [float("nan") if c is None else float(c) for c in cuts]
+    if len(values) != M:
+        raise ValueError(f"boot_stats: {M} members need {M} cuts, got {len(values)}")
+    if ws is None:
+        ws = torch.empty(_boot_default_ws(n, B), dtype=torch.uint8, device=device)
+    elif ws.dtype != torch.uint8 or ws.device != device or (n > BOOT_LDS_MAX_N and ws.numel() < 4 * n):
+        raise ValueError(f"boot_stats: ws must be a uint8 tensor of at least {4 * n} bytes on {device}")
+    stats = _dst(out, (M, B, BOOT_STATS_LEN), device, torch.int64)
+    score_ptrs = (ctypes.c_void_p * M)(*[_p(t) for t in members])
+    perm_ptrs = (ctypes.c_void_p * M)(*[_p(t) for t in perm_list])
+    check(_L().dfd_boot_stats(score_ptrs, perm_ptrs, M, _p(is_positive), _p(hit), (ctypes.c_double * M)(*values), n, B,
+                              seed, _p(ws) if ws.numel() else None, ws.numel(), _p(stats), _stream()),
+          "dfd_boot_stats", f"n={n} B={B} M={M}")
+    return stats
+
+
 # ------------------------------------------------------------------ Grad-CAM (ABI 136)
 def gradcam_map(act: torch.Tensor, grad: torch.Tensor) -> torch.Tensor:
     """Target-layer activation and its gradient, NHWC [N, h, w, C] (f32 or bf16) -> the ReLU'd Grad-CAM map f32 [N, h, w]:

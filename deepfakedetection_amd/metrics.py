@@ -32,9 +32,9 @@ import torch
 
 from . import kernels as K
 
-__all__ = ["CalibrationResult", "DiversityResult", "FusionFit", "RocResult", "ScoreBook", "TemperatureFit", "apply_temperature", "binary_roc",
-           "calibration", "confusion", "diversity", "eer_from_curve", "fit_fusion", "fit_temperature", "fuse", "gather_scores", "mean_nll",
-           "ovr_auc"]
+__all__ = ["BootstrapResult", "CalibrationResult", "DeltaResult", "DiversityResult", "FusionFit", "RocResult", "ScoreBook", "TemperatureFit",
+           "apply_temperature", "binary_roc", "boot_values", "bootstrap", "calibration", "confusion", "diversity", "eer_from_curve",
+           "fit_fusion", "fit_temperature", "fuse", "gather_scores", "mean_nll", "ovr_auc", "paired_delta", "percentile_interval"]
 
 
 class ScoreBook:
@@ -170,7 +170,12 @@ def binary_roc(scores: torch.Tensor, labels: torch.Tensor, positive: int = 1, cu
     if scores.numel() != labels.numel():
         raise ValueError(f"binary_roc: {scores.numel()} scores for {labels.numel()} labels")
     ordered, order = torch.sort(scores)
-    thr, cum_pos, cum_neg, stats = K.roc_curve(ordered.contiguous(), labels[order].contiguous(), positive)
+    return _roc_of_sorted(ordered.contiguous(), labels[order].contiguous(), positive, cuts, strict)
+
+
+def _roc_of_sorted(scores: torch.Tensor, labels: torch.Tensor, positive: int, cuts, strict: bool) -> RocResult:
+    """binary_roc behind its sort: f32 [n] scores ascending and their int64 labels in that order."""
+    thr, cum_pos, cum_neg, stats = K.roc_curve(scores, labels, positive)
     sweep = None
     if cuts is not None:
         cuts_np = np.ascontiguousarray(np.asarray(cuts, dtype=np.float64).reshape(-1))
@@ -192,6 +197,160 @@ def binary_roc(scores: torch.Tensor, labels: torch.Tensor, positive: int = 1, cu
     if sweep is not None:
         res.cuts, res.tp, res.fp = cuts_np, sweep[0].cpu().numpy(), sweep[1].cpu().numpy()
     return res
+
+
+BOOT_METRICS = ("auc", "eer", "accuracy", "balanced_accuracy", "tpr", "fpr", "hit_rate")
+
+
+def boot_values(stats: np.ndarray, metric: str) -> np.ndarray:
+    """One metric of every resample from kernels.boot_stats' integers [..., BOOT_STATS_LEN]: f64 of the leading shape.  Every
+    value is one division of integers below 2^53 (the equal error rate: eer_from_curve's arithmetic on the segment's two ends);
+    a resample with a class absent gives NaN for every metric but hit_rate (hits / n; NaN only for n == 0)."""
+    if metric not in BOOT_METRICS:
+        raise ValueError(f"bootstrap: metric must be one of {', '.join(BOOT_METRICS)}, got {metric!r}")
+    s = np.asarray(stats, dtype=np.int64)
+    P, N, two_u, tp, fp, hits, f0, t0, f1, t1 = (s[..., k] for k in range(K.BOOT_STATS_LEN))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        if metric == "hit_rate":
+            return np.where(P + N > 0, hits / np.maximum(P + N, 1), np.nan)
+        both = (P > 0) & (N > 0)
+        Ps, Ns = np.maximum(P, 1), np.maximum(N, 1)
+        if metric == "auc":
+            value = two_u / (2 * Ps * Ns)
+        elif metric == "accuracy":
+            value = (tp + N - fp) / (Ps + Ns)
+        elif metric == "balanced_accuracy":
+            value = (tp * N + (N - fp) * P) / (2 * Ps * Ns)
+        elif metric == "tpr":
+            value = tp / Ps
+        elif metric == "fpr":
+            value = fp / Ns
+        else:
+            a0, a1 = f0 * P + t0 * N - P * N, f1 * P + t1 * N - P * N        # a0 < 0 <= a1 on the segment
+            t = -a0 / np.where(a1 - a0 != 0, a1 - a0, 1)
+            value = np.where(a1 == 0, f1 / Ns, (f0 + t * (f1 - f0)) / Ns)
+        return np.where(both, value, np.nan)
+
+
+def percentile_interval(values: np.ndarray, level: float) -> tuple[float, float] | None:
+    """np.quantile(valid, [(1 - level) / 2, (1 + level) / 2]) over the values that are not NaN; None when there is none."""
+    v = np.asarray(values, dtype=np.float64).reshape(-1)
+    v = v[~np.isnan(v)]
+    if v.size == 0:
+        return None
+    lo, hi = np.quantile(v, [(1.0 - level) / 2.0, (1.0 + level) / 2.0])
+    return float(lo), float(hi)
+
+
+@dataclass
+class DeltaResult:
+    """A paired comparison of two members (BootstrapResult.delta): the difference of the point figures, the percentile interval of
+    the per-resample differences (None without a valid resample), the two-sided p value and the resamples it rests on."""
+
+    metric: str
+    point: float | None
+    lo: float | None
+    hi: float | None
+    p: float
+    valid: int
+
+
+def paired_delta(metric: str, point_a: float | None, point_b: float | None, values_a: np.ndarray, values_b: np.ndarray,
+                 level: float) -> DeltaResult:
+    """DeltaResult of two members' per-resample values over the same resamples: d = a - b where neither is NaN, and
+    p = min(1, 2 min(#{d <= 0} + 1, #{d >= 0} + 1) / (valid + 1))."""
+    d = np.asarray(values_a, dtype=np.float64) - np.asarray(values_b, dtype=np.float64)
+    d = d[~np.isnan(d)]
+    interval = percentile_interval(d, level)
+    lo, hi = interval if interval is not None else (None, None)
+    p = min(1.0, 2 * min(int((d <= 0).sum()) + 1, int((d >= 0).sum()) + 1) / (d.size + 1))
+    point = None if point_a is None or point_b is None else point_a - point_b
+    return DeltaResult(metric, point, lo, hi, p, int(d.size))
+
+
+@dataclass
+class BootstrapResult:
+    """What bootstrap found: kernels.boot_stats' integers of every member and resample (numpy int64 [M, B, BOOT_STATS_LEN]), the
+    settings, and per member the point figures of the full sample (a dict over BOOT_METRICS; None where a figure does not exist)."""
+
+    stats: np.ndarray
+    replicates: int
+    seed: int
+    level: float
+    point: list
+
+    def values(self, metric: str) -> np.ndarray:
+        """f64 [M, B]: the metric of every member in every resample (boot_values)."""
+        return boot_values(self.stats, metric)
+
+    def degenerate(self, member: int = 0) -> int:
+        """The resamples that lost a class."""
+        s = self.stats[member]
+        return int(((s[:, K.BOOT_P] == 0) | (s[:, K.BOOT_N] == 0)).sum())
+
+    def interval(self, metric: str, member: int = 0) -> tuple[float, float] | None:
+        """The percentile interval of `level` over the resamples where the metric exists; None when there is none."""
+        return percentile_interval(self.values(metric)[member], self.level)
+
+    def delta(self, metric: str, a: int, b: int) -> DeltaResult:
+        """Member a minus member b, paired by resample (paired_delta)."""
+        values = self.values(metric)
+        return paired_delta(metric, self.point[a][metric], self.point[b][metric], values[a], values[b], self.level)
+
+
+def _point_figures(roc: RocResult, hits: int | None, n: int) -> dict:
+    """The full sample's figures in boot_values' arithmetic; roc carries one cut or none."""
+    P, N = roc.n_pos, roc.n_neg
+    out = dict.fromkeys(BOOT_METRICS)
+    if hits is not None and n:
+        out["hit_rate"] = hits / n
+    if P and N:
+        out["auc"], out["eer"] = roc.auc, roc.eer
+        if roc.cuts is not None:
+            tp, fp = int(roc.tp[0]), int(roc.fp[0])
+            out.update(accuracy=(tp + N - fp) / (P + N), balanced_accuracy=(tp * N + (N - fp) * P) / (2 * P * N), tpr=tp / P, fpr=fp / N)
+    return out
+
+
+def bootstrap(scores, labels: torch.Tensor, *, positive: int = 1, cut=None, hits: torch.Tensor | None = None, replicates: int = 2000,
+              seed: int = 0, level: float = 0.95) -> BootstrapResult:
+    """The nonparametric bootstrap of the ROC figures: `replicates` resamples of the n samples, drawn on the device by the rule of
+    include/dfd_hip.h (Philox4x32-10 keyed by `seed`), each judged by kernels.boot_stats.  scores: one float tensor [n] on the
+    device or a list of M <= kernels.BOOT_MAX_MEMBERS over the same samples, which then share every resample (BootstrapResult.delta
+    compares them pairwise).  cut: the threshold of accuracy / balanced_accuracy / tpr / fpr (score >= cut predicts `positive`,
+    compared in f64), one number or one per member; it is held fixed, not chosen again per resample.  hits: optional [n] flags
+    (nonzero = this sample was judged right) behind hit_rate.  Each member is sorted once; the resamples are multiplicities over
+    that order, so none of them sorts.  Non-finite scores raise ValueError.  One read-back after the last launch."""
+    members = [scores] if isinstance(scores, torch.Tensor) else list(scores)
+    if not 1 <= len(members) <= K.BOOT_MAX_MEMBERS:
+        raise ValueError(f"bootstrap: takes 1..{K.BOOT_MAX_MEMBERS} score vectors, got {len(members)}")
+    members = [m.detach().reshape(-1).float() for m in members]
+    labels = labels.detach().reshape(-1).to(torch.int64)
+    n, count, B = labels.numel(), len(members), int(replicates)
+    if any(m.numel() != n for m in members):
+        raise ValueError(f"bootstrap: {[m.numel() for m in members]} scores for {n} labels")
+    if not 1 <= n <= K.BOOT_MAX_N or not 1 <= B <= K.BOOT_MAX_REPLICATES or not 0.0 < float(level) < 1.0:
+        raise ValueError(f"bootstrap: takes 1..{K.BOOT_MAX_N} samples, 1..{K.BOOT_MAX_REPLICATES} replicates and 0 < level < 1, got "
+                         f"{n}, {B}, {level!r}")
+    cuts = list(cut) if isinstance(cut, (list, tuple)) else [cut] * count
+    if len(cuts) != count or any(c is not None and not np.isfinite(float(c)) for c in cuts):
+        raise ValueError(f"bootstrap: cut must be one finite number or one per member ({count}), got {cut!r}")
+    if hits is not None and hits.numel() != n:
+        raise ValueError(f"bootstrap: {hits.numel()} hits for {n} labels")
+    is_positive = (labels == int(positive)).to(torch.uint8)
+    hit = (hits.detach().reshape(-1) != 0).to(torch.uint8) if hits is not None else None
+    ordered, perms, rocs = [], [], []
+    for m, c in zip(members, cuts):
+        s, order = torch.sort(m)
+        ordered.append(s.contiguous())
+        perms.append(order.to(torch.int32).contiguous())
+        rocs.append(_roc_of_sorted(ordered[-1], labels[order].contiguous(), int(positive), None if c is None else [float(c)], True))
+    stats_d = K.boot_stats(ordered, perms, is_positive, B, seed, cuts, hit)
+    total_hits = hit.sum(dtype=torch.int64).reshape(1) if hit is not None else stats_d.new_zeros(1)
+    packed = torch.cat([stats_d.reshape(-1), total_hits]).cpu().numpy()   # the one read-back of the resamples
+    stats = packed[:-1].reshape(count, B, K.BOOT_STATS_LEN).copy()
+    n_hits = int(packed[-1]) if hit is not None else None
+    return BootstrapResult(stats, B, int(seed), float(level), [_point_figures(r, n_hits, n) for r in rocs])
 
 
 def ovr_auc(probs: torch.Tensor, targets: torch.Tensor, num_classes: int, strict: bool = True) -> float | None:

@@ -48,7 +48,7 @@ from torch.utils.data import DataLoader
 
 from .. import data as D
 from .. import metrics as M
-from .._lib import BLUR_MAX_PIXELS, CALIB_MAX_BINS, FUSE_MAX_MODELS
+from .._lib import BLUR_MAX_PIXELS, BOOT_MAX_MEMBERS, BOOT_MAX_REPLICATES, CALIB_MAX_BINS, FUSE_MAX_MODELS
 from .config_schema import OrchestratorConfig
 from .model_registry import get_model_spec
 from .train_env import apply_seed, as_bool, require_num_classes
@@ -355,6 +355,32 @@ def calibration_settings(infer_cfg: dict[str, Any]) -> tuple[int, str | float] |
     return bins, value
 
 
+def bootstrap_settings(raw: Any, where: str = "inference.bootstrap") -> tuple[int, float, int] | None:
+    """Extra key `inference.bootstrap: {replicates: 2000, level: 0.95, seed: 0}` (and `ensemble.bootstrap`): (replicates, level,
+    seed) of the percentile intervals metrics.bootstrap adds to every judged pass, or None without the key.  ValueError for another
+    key, replicates outside 1..65536, a level outside (0, 1) or a seed that is no unsigned 64-bit integer."""
+    if raw is None or raw is False:
+        return None
+    if raw is True:
+        raw = {}
+    if not isinstance(raw, dict):
+        raise ValueError(f"{where} must be a mapping like {{replicates: 2000, level: 0.95, seed: 0}}, got {raw!r}")
+    unknown = sorted(set(map(str, raw)) - {"replicates", "level", "seed"})
+    if unknown:
+        raise ValueError(f"{where} takes replicates, level and seed; not {', '.join(unknown)}")
+    try:
+        replicates, level, seed = int(raw.get("replicates", 2000)), float(raw.get("level", 0.95)), int(raw.get("seed", 0))
+    except (TypeError, ValueError):
+        raise ValueError(f"{where} takes numbers, got {raw!r}") from None
+    if not 1 <= replicates <= BOOT_MAX_REPLICATES:
+        raise ValueError(f"{where}.replicates must be 1..{BOOT_MAX_REPLICATES}, got {raw.get('replicates')!r}")
+    if not 0.0 < level < 1.0:
+        raise ValueError(f"{where}.level must lie inside (0, 1), got {raw.get('level')!r}")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"{where}.seed must be an unsigned 64-bit integer, got {raw.get('seed')!r}")
+    return replicates, level, seed
+
+
 @dataclass(frozen=True)
 class EnsembleSettings:
     """The top-level `ensemble:` key, every default applied (ensemble_settings)."""
@@ -363,6 +389,7 @@ class EnsembleSettings:
     weights: str | tuple[float, ...]                # "equal" | "fit" | one weight per member
     l2: float
     output_dir: Path
+    bootstrap: tuple[int, float, int] | None = None     # bootstrap_settings of `ensemble.bootstrap`
 
 
 def ensemble_settings(config: dict[str, Any], out: Console) -> EnsembleSettings | None:
@@ -411,7 +438,8 @@ def ensemble_settings(config: dict[str, Any], out: Console) -> EnsembleSettings 
         raise ValueError(f"ensemble.l2 must be a number >= 0, got {raw.get('l2')!r}")
     if len(members) == 1:
         out.print("[bold yellow]ensemble[/]: one member only; its scores are fused with nothing")
-    return EnsembleSettings(members, mode, weights, l2, Path(str(raw.get("output_dir") or "runs/ensemble")))
+    return EnsembleSettings(members, mode, weights, l2, Path(str(raw.get("output_dir") or "runs/ensemble")),
+                            bootstrap_settings(raw.get("bootstrap"), "ensemble.bootstrap"))
 
 
 def robustness_levels(infer_cfg: dict[str, Any]) -> list[tuple[str, float | int]]:
@@ -730,7 +758,28 @@ def _judge(s: InferenceSettings, book, threshold: float, calib: _Calibration | N
         probs, targets, roc = book.probs.clone(), book.targets.clone(), None        # the book is filled again by the next level
         record, preds, cm = _split_metrics(s.name, s.split, probs, book.preds.clone(), targets, s.num_classes, threshold)
     record.update(figures)
+    if s.bootstrap is not None and roc is not None:
+        record.update(_bootstrap_keys(book, threshold, s.bootstrap, roc))
     return PassResult(record, probs, preds, targets, cm, roc, reliability)
+
+
+BOOT_RECORD_METRICS = (("roc_auc", "auc"), ("eer", "eer"), ("accuracy", "accuracy"), ("balanced_accuracy", "balanced_accuracy"))
+
+
+def _bootstrap_keys(book, threshold: float, settings: tuple[int, float, int], roc) -> dict[str, Any]:
+    """The `ci` and `bootstrap` keys of a binary pass kept on the device: percentile intervals at the threshold in force, which is
+    held fixed (its own uncertainty is not resampled).  Scores that are not finite leave ci None."""
+    replicates, level, seed = settings
+    about: dict[str, Any] = {"replicates": replicates, "seed": seed, "level": level, "degenerate": None}
+    if roc.nonfinite:
+        return {"ci": None, "bootstrap": about}
+    res = M.bootstrap(book.probs[:, 1], book.targets, cut=threshold, replicates=replicates, seed=seed, level=level)
+    about["degenerate"] = res.degenerate()
+    ci = {}
+    for key, metric in BOOT_RECORD_METRICS:
+        interval = res.interval(metric)
+        ci[key] = list(interval) if interval is not None else None
+    return {"ci": ci, "bootstrap": about}
 
 
 def _emit(record: dict[str, Any], run_paths: RunPaths, out: Console, head: str) -> None:
@@ -808,6 +857,7 @@ class InferenceSettings:
     calibration: tuple[int, str | float] | None     # extra key (calibration_settings): the passes keep their logits, T rescales them
     robustness: tuple[tuple[str, float | int], ...]         # the robustness_levels that can run (the device pipeline's batch is perturbed)
     cam_limit: int | None                           # None also where Grad-CAM cannot run
+    bootstrap: tuple[int, float, int] | None = None     # extra key (bootstrap_settings): every judged pass gains `ci` and `bootstrap`
 
 
 def inference_settings(config: dict[str, Any], model_cfg: dict[str, Any], out: Console) -> InferenceSettings:
@@ -845,6 +895,11 @@ def inference_settings(config: dict[str, Any], model_cfg: dict[str, Any], out: C
     if calibration is not None and not device_metrics:
         out.print("[bold yellow]inference.calibration ignored[/]: needs inference.device_metrics on a CUDA device")
         calibration = None
+    num_classes = int(model_cfg.get("num_classes", data_cfg.get("num_classes", 2)))
+    bootstrap = bootstrap_settings(infer_cfg.get("bootstrap"))
+    if bootstrap is not None and not (device_metrics and num_classes == 2):
+        out.print("[bold yellow]inference.bootstrap ignored[/]: needs inference.device_metrics on a CUDA device and a binary problem")
+        bootstrap = None
     levels = robustness_levels(infer_cfg)
     if levels and not gpu_resize:           # the perturbation is applied to the cropped uint8 batch of the device pipeline
         out.print("[bold yellow]inference.robustness skipped[/]: needs inference.gpu_resize on a CUDA device")
@@ -858,11 +913,11 @@ def inference_settings(config: dict[str, Any], model_cfg: dict[str, Any], out: C
         limit = None
     return InferenceSettings(
         name=name, root=root if root.is_absolute() else (Path.cwd() / root).resolve(), split=split,
-        val_split=str(data_cfg.get("val_split", "val")), num_classes=int(model_cfg.get("num_classes", data_cfg.get("num_classes", 2))),
+        val_split=str(data_cfg.get("val_split", "val")), num_classes=num_classes,
         image_size=image_size, batch_size=batch_size, num_workers=int(infer_cfg.get("num_workers", 4)),
         amp=str(infer_cfg.get("amp", "")).lower() in ("bf16", "bfloat16", "true", "1"), device=device,
         fp8_weights=str(infer_cfg.get("fp8_weights", "")).lower() in on, transform=transform,
-        device_metrics=device_metrics, calibration=calibration, robustness=tuple(levels), cam_limit=limit)
+        device_metrics=device_metrics, calibration=calibration, bootstrap=bootstrap, robustness=tuple(levels), cam_limit=limit)
 
 
 @dataclass
@@ -957,6 +1012,24 @@ def _ensemble_figures(book) -> dict[str, Any]:
     return {"ece": res.ece, "mce": res.mce, "brier": res.brier, "nll": M.mean_nll(book.logits, book.targets)}
 
 
+def _ensemble_vs_members(book, threshold: float, names: list[str], members: list[MemberScores], settings: tuple[int, float, int]) -> dict[str, Any]:
+    """ensemble.json's `vs_members`: per member the paired bootstrap of ensemble minus member on the clean pass, in AUC and in
+    accuracy, each side at its own record's threshold and temperature.  One metrics.bootstrap call scores the ensemble beside up to
+    BOOT_MAX_MEMBERS - 1 members; a larger ensemble takes a second call, which draws the same resamples from the same seed."""
+    replicates, level, seed = settings
+    targets = book.targets
+    out: dict[str, Any] = {}
+    for start in range(0, len(members), BOOT_MAX_MEMBERS - 1):
+        part = list(zip(names, members))[start:start + BOOT_MAX_MEMBERS - 1]
+        scores = [book.probs[:, 1]] + [M.apply_temperature(m.clean[0], m.temperature if m.temperature is not None else 1.0)[0][:, 1]
+                                       for _, m in part]
+        cuts = [float(threshold)] + [float(m.record.get("threshold", 0.5)) for _, m in part]
+        res = M.bootstrap(scores, targets, cut=cuts, replicates=replicates, seed=seed, level=level)
+        for k, (name, _) in enumerate(part, start=1):
+            out[name] = {"auc": asdict(res.delta("auc", 0, k)), "accuracy": asdict(res.delta("accuracy", 0, k))}
+    return out
+
+
 def run_ensemble_job(ens: EnsembleSettings, names: list[str], members: list[MemberScores], run_paths: RunPaths) -> None:
     """Fuse the members' kept logits (metrics.fuse), judge the fused passes as a member's are judged and write ensemble.json."""
     console.print(f"[bold]→ ensemble of {', '.join(names)}[/]")
@@ -976,7 +1049,11 @@ def _run_ensemble_job(ens: EnsembleSettings, names: list[str], members: list[Mem
         if (m.val is None) != (first.val is None) or m.val_paths != first.val_paths or \
                 (m.val is not None and not torch.equal(m.val[1], first.val[1])):
             raise ValueError(f"ensemble: {name} scored other samples or targets of split {first.settings.val_split!r} than {names[0]}")
-    s = replace(first.settings, name="ensemble", calibration=None)
+    boot = ens.bootstrap
+    if boot is not None and first.settings.num_classes != 2:
+        out.print("[bold yellow]ensemble.bootstrap ignored[/]: needs a binary problem")
+        boot = None
+    s = replace(first.settings, name="ensemble", calibration=None, bootstrap=boot)
     temperatures = [m.temperature for m in members]
     doc: dict[str, Any] = {"members": list(names), "mode": ens.mode, "weights": ens.weights if isinstance(ens.weights, str) else "given",
                            "temperatures": temperatures, "fit": None}
@@ -1004,7 +1081,7 @@ def _run_ensemble_job(ens: EnsembleSettings, names: list[str], members: list[Mem
         val_book = _fused_book(pooled, [m.val[0] for m in members], first.val[1], ens, weights)
         threshold = _first_set(_validation_threshold(val_book), threshold)
         del val_book
-    book = _fused_book(pooled, [m.clean[0] for m in members], first.clean[1], ens, weights)
+    book = book_clean = _fused_book(pooled, [m.clean[0] for m in members], first.clean[1], ens, weights)
     clean = _judge(s, book, threshold, None, clean=True)
     clean.record.update(_ensemble_figures(book))
     scores = clean.probs[:, 1].numpy() if s.num_classes == 2 and torch.unique(clean.targets).numel() > 1 else None
@@ -1025,6 +1102,8 @@ def _run_ensemble_job(ens: EnsembleSettings, names: list[str], members: list[Mem
     doc["clean"] = {name: {"accuracy": rec.get("accuracy"), "roc_auc": rec.get("roc_auc")}
                     for name, rec in [*zip(names, (m.record for m in members)), ("ensemble", clean.record)]}
     doc["threshold"] = float(threshold)
+    if boot is not None and not clean.roc.nonfinite:
+        doc["vs_members"] = _ensemble_vs_members(book_clean, threshold, names, members, boot)
     (run_paths.run_dir / "ensemble.json").write_text(json.dumps(doc, indent=2) + "\n", encoding="utf-8")
     out.print(f"[bold]Ensemble[/]: coefficients {doc['coefficients']} | oracle accuracy {div.oracle_accuracy} | {run_paths.run_dir / 'ensemble.json'}")
 

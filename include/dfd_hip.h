@@ -103,7 +103,9 @@ typedef void* dfd_stream;          /* a hipStream_t */
  * 151 = dfd_fuse_scores, dfd_fuse_nll / _ws, dfd_fuse_agree, dfd_fuse_plan (the ensemble of K models: fused scores of a logit or a
  * probability pool, the pool's NLL with gradient and Hessian in its coefficients, right / wrong agreement tables);
  * 152 = dfd_stem_bwd_fused / _ok (the stem's weight gradient straight from the incoming gradient, without a stored dz; same bits as
- * dfd_act_bn_bwd + dfd_stem_conv_wgrad); dfd_act_bn_bwd takes dz = NULL: the partial sums only. */
+ * dfd_act_bn_bwd + dfd_stem_conv_wgrad); dfd_act_bn_bwd takes dz = NULL: the partial sums only;
+ * 153 = dfd_boot_stats, dfd_boot_counts, dfd_boot_plan, dfd_boot_ws (bootstrap resamples of the ROC statistics: Philox draws into
+ * integer counts, weighted sweeps of the sorted scores; all outputs integers). */
 int dfd_version(void);
 
 /* Planner knobs: the tier switches and grid sizes by which tests and per-layer scripts reach a kernel tier.  Process-wide plain ints:
@@ -704,6 +706,56 @@ int dfd_fuse_nll(const float* const* ptrs, int K, const int64_t* targets, int n,
 int dfd_fuse_agree(const int64_t* const* pred_ptrs, int K, const int64_t* targets, int n, int J, int64_t* pair, int64_t* hist,
                    int64_t* stats, dfd_stream stream);
 int dfd_fuse_plan(int n, int J, int K, int* out);
+
+/* The nonparametric bootstrap of the ROC statistics on the device (csrc/dfd_boot.hip, ABI 153).  B <= DFD_BOOT_MAX_REPLICATES
+ * resamples of n <= DFD_BOOT_MAX_N samples, M <= DFD_BOOT_MAX_MEMBERS score vectors ("members") over the same samples.
+ *
+ * The resampling rule: draw t (0 <= t < n) of resample b (0 <= b < B) runs Philox4x32-10 (csrc/dfd_philox.h) with the key
+ * (seed & 0xffffffff, seed >> 32) and the counter (t >> 2, b, 0, DFD_BOOT_STREAM); u = output word t & 3; the drawn sample is
+ * idx = ((uint64_t)u * n) >> 32.  c_b[i] is how often sample i was drawn, i in the CALLER'S order (not the sorted one), so that
+ * every member sees the same resamples.  The multiply-shift gives each index either floor(2^32 / n) or that plus one of the 2^32
+ * values of u: the index probabilities differ by at most n / 2^32 relative (0.4 % at n = 2^24, 2.3e-5 at n = 10^5).
+ *
+ * dfd_boot_stats: score_ptrs / perm_ptrs = M device addresses each IN HOST MEMORY (they travel by value in the launch): member
+ * m's n f32 scores sorted ASCENDING and the int32 permutation that sorted them (score_ptrs[m][i] is the score of sample
+ * perm_ptrs[m][i]; an entry outside [0, n) counts for nothing).  is_positive uint8 [n] and hit uint8 [n] (or NULL) are in sample
+ * order and shared; cuts = M doubles in host memory (NULL or a NaN: no cut).  Scores must be finite.  Every sample i counts
+ * c_b[i] times:
+ *   stats int64 [M][B][DFD_BOOT_STATS_LEN] = {P, N, two_u, tp, fp, hits, f0, t0, f1, t1}
+ *   P, N    weighted positives (is_positive != 0) / negatives; two_u as dfd_roc_curve defines it over the tie groups of the scores
+ *   tp, fp  positives / negatives with (double)score >= cut, 0 without a cut; hits = sum c_b[i] * (hit[i] != 0), 0 without hit
+ *   f0, t0, f1, t1  (fps, tps) at the two ends of the segment of the resample's ROC curve (thresholds descending) on which the
+ *           equal error rate is interpolated: the segment ends at the first tie-group end where fps P + tps N - P N >= 0 and starts
+ *           at the group end before it, or at (0, 0); all four are 0 when P == 0 or N == 0.  Tie groups that a resample leaves
+ *           empty stay in as repeated points, which changes none of the four.
+ * Two tiers; dfd_boot_plan tells which one runs.  n <= DFD_BOOT_LDS_MAX_N: one workgroup per resample keeps its uint32 counts in
+ * LDS (4 n bytes behind DFD_BOOT_SCRATCH_BYTES of reduction scratch: together the 160 KiB one workgroup may declare), draws with LDS
+ * integer adds and sweeps every member; ws is not read.  Above: counts are uint32 [R][n] in ws, R = min(B, ws_bytes / (4 n))
+ * resamples per pass, and the call loops over ceil(B / R) passes of three launches: zero, draw (one workgroup per (resample,
+ * tile of DFD_BOOT_DRAW_TILE draws), global integer adds without return), statistics (one workgroup per (resample, member)).
+ * The atomics add integers only: counts and statistics do not depend on arrival order or launch geometry.
+ *
+ * dfd_boot_ws(n, B): the bytes for R = B in the global tier, 0 in the LDS tier or for arguments out of range.
+ * dfd_boot_plan: plan[4] = {tier (DFD_BOOT_TIER_LDS / _GLOBAL), R, passes, draw tiles per resample}.
+ * dfd_boot_counts: the global tier's zero and draw alone: counts uint32 [R][n] of resamples b0 .. b0 + R - 1 (any n).
+ * n == 0 is valid (zeros).  n, B, M, b0 or R out of range, a NULL pointer, or a global-tier ws too small for one resample:
+ * DFD_EINVAL, nothing is launched. */
+#define DFD_BOOT_STREAM 0x626f6f74u
+#define DFD_BOOT_MAX_N (1 << 24)
+#define DFD_BOOT_MAX_REPLICATES 65536
+#define DFD_BOOT_MAX_MEMBERS 8
+#define DFD_BOOT_STATS_LEN 10
+#define DFD_BOOT_SCRATCH_BYTES 512
+#define DFD_BOOT_LDS_MAX_N ((160 * 1024 - DFD_BOOT_SCRATCH_BYTES) / 4)
+#define DFD_BOOT_DRAW_TILE 4096
+#define DFD_BOOT_TIER_LDS 0
+#define DFD_BOOT_TIER_GLOBAL 1
+size_t dfd_boot_ws(int n, int B);
+int dfd_boot_plan(int n, int B, int M, size_t ws_bytes, int* plan);
+int dfd_boot_counts(int n, int b0, int R, uint64_t seed, uint32_t* counts, dfd_stream stream);
+int dfd_boot_stats(const float* const* score_ptrs, const int* const* perm_ptrs, int M, const unsigned char* is_positive,
+                   const unsigned char* hit, const double* cuts, int n, int B, uint64_t seed, void* ws, size_t ws_bytes, int64_t* stats,
+                   dfd_stream stream);
 
 /* Input tail on the device (trainers/efficientnet.py:111-234): a uint8 NHWC
  * batch [N][H][W][3] -> RandomHorizontalFlip -> ToTensor (/255) -> Normalize((x-mean)/std) ->
