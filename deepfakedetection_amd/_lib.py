@@ -77,6 +77,16 @@ BOOT_SCRATCH_BYTES = 512            # reduction scratch in front of the LDS tier
 BOOT_LDS_MAX_N = (160 * 1024 - BOOT_SCRATCH_BYTES) // 4       # largest n whose uint32 counts stay in one workgroup's LDS
 BOOT_DRAW_TILE = 4096               # draws per workgroup of the global tier's draw kernel
 BOOT_TIER_LDS, BOOT_TIER_GLOBAL = 0, 1
+BOOT_GROUPED_MAX_WEIGHT = (1 << 31) - 1     # the cluster bootstrap: groups times the largest group at most
+# csrc/dfd_group.hip (the DFD_GROUP_* constants of include/dfd_hip.h)
+GROUP_MEAN, GROUP_VOTE, GROUP_MAX = 0, 1, 2
+GROUP_MAX_N = 1 << 24
+GROUP_MAX_J = 1024
+GROUP_LDS_BYTES = 65536             # the workspace size up to which every workgroup keeps a private copy of the cells in LDS
+GROUP_LDS_MAX_BLOCKS = 256
+GROUP_GLOBAL_MAX_BLOCKS = 2048
+GROUP_TIER_LDS, GROUP_TIER_GLOBAL = 0, 1
+(GROUP_INVALID, GROUP_OOB, GROUP_MIXED, GROUP_EMPTY) = range(4)
 
 
 class DwShape(Structure):
@@ -200,6 +210,13 @@ SIGNATURES: dict[str, tuple] = {
     "dfd_boot_plan": (c_int, [c_int, c_int, c_int, c_size_t, _PI]),
     "dfd_boot_counts": (c_int, [c_int, c_int, c_int, c_uint64, P, P]),
     "dfd_boot_stats": (c_int, [P, P, c_int, P, P, POINTER(c_double), c_int, c_int, c_uint64, P, c_size_t, P, P]),
+    # ---- ABI 154
+    "dfd_boot_ws_grouped": (c_size_t, [c_int, c_int, c_int]),
+    "dfd_boot_plan_grouped": (c_int, [c_int, c_int, c_int, c_int, c_int, c_size_t, _PI]),
+    "dfd_boot_stats_grouped": (c_int, [P, P, c_int, P, P, POINTER(c_double), P, c_int, c_int, c_int, c_int, c_uint64, P, c_size_t, P, P]),
+    "dfd_group_ws": (c_size_t, [c_int, c_int, c_int]),
+    "dfd_group_plan": (c_int, [c_int, c_int, c_int, _PI]),
+    "dfd_group_pool": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P, P, P, P, P, P]),
     # ---- ABI 111
     "dfd_bn_eval_coeffs_multi": (c_int, [P, c_int, P]),
     "dfd_sum_batch_begin": (c_int, []),

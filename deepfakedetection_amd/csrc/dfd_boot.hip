@@ -1,4 +1,5 @@
-// dfd_boot.hip — bootstrap resamples of the ROC statistics on the device (ABI 153; the contract is in include/dfd_hip.h).
+// dfd_boot.hip — bootstrap resamples of the ROC statistics on the device (ABI 153, the cluster bootstrap ABI 154; the contract is in
+// include/dfd_hip.h).
 //
 // A resample is a vector of multiplicities c[i] over the samples in the caller's order; the scores stay sorted as they are, so no
 // resample sorts.  Everything is integer counting: the draws add 1 to uint32 counts, the sweep adds the counts up, and the only
@@ -13,6 +14,9 @@
 // at a group's two ends the thread adds the group's term of two_u and tests whether the equal-error segment ends there.  P and N do
 // not depend on the member (the labels are shared), so a pass over the counts in sample order supplies them before the sweep, and
 // the sweep is one pass.  The tie-group ends are a comparison of neighbouring scores the sweep has loaded anyway.
+// The cluster bootstrap (dfd_boot_stats_grouped) draws G groups instead of n samples: the counts have G entries, and the totals and
+// the sweep read a sample's weight as counts[group[i]] (BootGrouped) where the plain bootstrap reads counts[i] (BootDirect).  The
+// kernels k_boot_lds_g / k_boot_glb_g differ from k_boot_lds / k_boot_glb in that alone; zero and draw run over G unchanged.
 #include "dfd_common.h"
 #include "dfd_philox.h"
 
@@ -108,12 +112,28 @@ static __device__ __forceinline__ void boot_draw4(uint32_t* counts, int n, uint3
     }
 }
 
-// P, N and hits of the resample whose counts are c[0..n), in sample order
-static __device__ __forceinline__ void boot_totals(const uint32_t* c, const unsigned char* __restrict__ is_positive,
+// how often sample i counts in a resample: its own count, or the count of its group (an id outside [0, G) counts for nothing)
+struct BootDirect {
+    const uint32_t* c;
+    __device__ __forceinline__ uint32_t operator()(int i) const { return c[i]; }
+};
+struct BootGrouped {
+    const uint32_t* c;
+    const int* __restrict__ group;
+    int G;
+    __device__ __forceinline__ uint32_t operator()(int i) const {
+        const int g = group[i];
+        return (unsigned)g < (unsigned)G ? c[g] : 0u;
+    }
+};
+
+// P, N and hits of the resample in which sample i counts c(i) times, in sample order
+template <typename W>
+static __device__ __forceinline__ void boot_totals(const W c, const unsigned char* __restrict__ is_positive,
                                                    const unsigned char* __restrict__ hit, int n, BootScratch* sc, int& P, int& N, int& hits) {
     unsigned long long v[2] = {0, 0};                                   // P | N << 32, hits
     for (int i = threadIdx.x; i < n; i += BOOT_THREADS) {
-        const unsigned long long w = c[i];
+        const unsigned long long w = c(i);
         v[0] += is_positive[i] ? w : (w << 32);
         if (hit && hit[i]) v[1] += w;
     }
@@ -123,8 +143,9 @@ static __device__ __forceinline__ void boot_totals(const uint32_t* c, const unsi
     hits = (int)v[1];
 }
 
-// one member's statistics of the resample whose counts are c[0..n): out[DFD_BOOT_STATS_LEN]
-static __device__ __forceinline__ void boot_sweep(const uint32_t* c, const float* __restrict__ score, const int* __restrict__ perm,
+// one member's statistics of the resample in which sample i counts c(i) times: out[DFD_BOOT_STATS_LEN]
+template <typename W>
+static __device__ __forceinline__ void boot_sweep(const W c, const float* __restrict__ score, const int* __restrict__ perm,
                                                   const unsigned char* __restrict__ is_positive, double cut, int n, int P, int N, int hits,
                                                   BootScratch* sc, int64_t* __restrict__ out) {
     const int t = threadIdx.x;
@@ -150,7 +171,7 @@ static __device__ __forceinline__ void boot_sweep(const uint32_t* c, const float
                 const float s_next = i + 1 < n ? score[i + 1] : 0.f;
                 const int idx = perm[i];
                 const bool ok = (unsigned)idx < (unsigned)n;
-                const int wt = ok ? (int)c[idx] : 0;
+                const int wt = ok ? (int)c(idx) : 0;
                 unsigned fl = ok && is_positive[idx] ? BOOT_F_POS : 0u;
                 if (i == n - 1 || !(s == s_next)) fl |= BOOT_F_END;     // dfd_roc_curve's tie groups: float comparison
                 if ((double)s >= cut) fl |= BOOT_F_CUT;                 // false for a NaN cut
@@ -212,9 +233,10 @@ k_boot_lds(BootMembers mem, int M, const unsigned char* __restrict__ is_positive
     for (int q = t; q < nq; q += BOOT_THREADS) boot_draw4(c, n, (uint32_t)q, (uint32_t)b, k0, k1);
     __syncthreads();
     int P, N, hits;
-    boot_totals(c, is_positive, hit, n, sc, P, N, hits);
+    const BootDirect w = {c};
+    boot_totals(w, is_positive, hit, n, sc, P, N, hits);
     for (int m = 0; m < M; ++m)
-        boot_sweep(c, mem.score[m], mem.perm[m], is_positive, mem.cut[m], n, P, N, hits, sc,
+        boot_sweep(w, mem.score[m], mem.perm[m], is_positive, mem.cut[m], n, P, N, hits, sc,
                    stats + ((size_t)m * B + b) * DFD_BOOT_STATS_LEN);
 }
 
@@ -243,8 +265,43 @@ k_boot_glb(BootMembers mem, const uint32_t* __restrict__ counts, const unsigned 
     const uint32_t* c = counts + (size_t)blockIdx.x * n;
     const int m = blockIdx.y, b = b0 + blockIdx.x;
     int P, N, hits;
-    boot_totals(c, is_positive, hit, n, &sc, P, N, hits);
-    boot_sweep(c, mem.score[m], mem.perm[m], is_positive, mem.cut[m], n, P, N, hits, &sc, stats + ((size_t)m * B + b) * DFD_BOOT_STATS_LEN);
+    const BootDirect w = {c};
+    boot_totals(w, is_positive, hit, n, &sc, P, N, hits);
+    boot_sweep(w, mem.score[m], mem.perm[m], is_positive, mem.cut[m], n, P, N, hits, &sc, stats + ((size_t)m * B + b) * DFD_BOOT_STATS_LEN);
+}
+
+// k_boot_lds with the G group counts in LDS: resample b draws G groups
+__global__ void __launch_bounds__(BOOT_THREADS)
+k_boot_lds_g(BootMembers mem, int M, const unsigned char* __restrict__ is_positive, const unsigned char* __restrict__ hit,
+             const int* __restrict__ group, int n, int G, int B, uint32_t k0, uint32_t k1, int64_t* __restrict__ stats) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t boot_lds[];
+    BootScratch* sc = reinterpret_cast<BootScratch*>(boot_lds);
+    uint32_t* c = boot_lds + DFD_BOOT_SCRATCH_BYTES / 4;
+    const int t = threadIdx.x, b = blockIdx.x;
+    for (int i = t; i < G; i += BOOT_THREADS) c[i] = 0;
+    __syncthreads();
+    const int nq = (G + 3) / 4;
+    for (int q = t; q < nq; q += BOOT_THREADS) boot_draw4(c, G, (uint32_t)q, (uint32_t)b, k0, k1);
+    __syncthreads();
+    int P, N, hits;
+    const BootGrouped w = {c, group, G};
+    boot_totals(w, is_positive, hit, n, sc, P, N, hits);
+    for (int m = 0; m < M; ++m)
+        boot_sweep(w, mem.score[m], mem.perm[m], is_positive, mem.cut[m], n, P, N, hits, sc,
+                   stats + ((size_t)m * B + b) * DFD_BOOT_STATS_LEN);
+}
+
+// k_boot_glb over counts uint32 [R][G]
+__global__ void __launch_bounds__(BOOT_THREADS)
+k_boot_glb_g(BootMembers mem, const uint32_t* __restrict__ counts, const unsigned char* __restrict__ is_positive,
+             const unsigned char* __restrict__ hit, const int* __restrict__ group, int n, int G, int B, int b0,
+             int64_t* __restrict__ stats) {
+    __shared__ BootScratch sc;
+    const int m = blockIdx.y, b = b0 + blockIdx.x;
+    int P, N, hits;
+    const BootGrouped w = {counts + (size_t)blockIdx.x * G, group, G};
+    boot_totals(w, is_positive, hit, n, &sc, P, N, hits);
+    boot_sweep(w, mem.score[m], mem.perm[m], is_positive, mem.cut[m], n, P, N, hits, &sc, stats + ((size_t)m * B + b) * DFD_BOOT_STATS_LEN);
 }
 
 static bool boot_shape_ok(int n, int B) { return n >= 0 && n <= DFD_BOOT_MAX_N && B >= 1 && B <= DFD_BOOT_MAX_REPLICATES; }
@@ -286,6 +343,16 @@ extern "C" int dfd_boot_counts(int n, int b0, int R, uint64_t seed, uint32_t* co
     return DFD_CHECK_LAUNCH();
 }
 
+static bool boot_members(const float* const* score_ptrs, const int* const* perm_ptrs, const double* cuts, int M, int n, BootMembers& mem) {
+    for (int m = 0; m < M; ++m) {
+        if (n > 0 && (!score_ptrs[m] || !perm_ptrs[m])) return false;
+        mem.score[m] = n > 0 ? score_ptrs[m] : nullptr;
+        mem.perm[m] = n > 0 ? perm_ptrs[m] : nullptr;
+        mem.cut[m] = cuts ? cuts[m] : __builtin_nan("");
+    }
+    return true;
+}
+
 extern "C" int dfd_boot_stats(const float* const* score_ptrs, const int* const* perm_ptrs, int M, const unsigned char* is_positive,
                               const unsigned char* hit, const double* cuts, int n, int B, uint64_t seed, void* ws, size_t ws_bytes,
                               int64_t* stats, dfd_stream stream) {
@@ -293,12 +360,7 @@ extern "C" int dfd_boot_stats(const float* const* score_ptrs, const int* const* 
     if (dfd_boot_plan(n, B, M, ws_bytes, plan) != DFD_OK || !stats) return DFD_EINVAL;
     if (n > 0 && (!score_ptrs || !perm_ptrs || !is_positive)) return DFD_EINVAL;
     BootMembers mem = {};
-    for (int m = 0; m < M; ++m) {
-        if (n > 0 && (!score_ptrs[m] || !perm_ptrs[m])) return DFD_EINVAL;
-        mem.score[m] = n > 0 ? score_ptrs[m] : nullptr;
-        mem.perm[m] = n > 0 ? perm_ptrs[m] : nullptr;
-        mem.cut[m] = cuts ? cuts[m] : __builtin_nan("");
-    }
+    if (!boot_members(score_ptrs, perm_ptrs, cuts, M, n, mem)) return DFD_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     if (plan[0] == DFD_BOOT_TIER_LDS) {
         dfd_allow_lds_once<k_boot_lds>(160 * 1024);
@@ -312,6 +374,48 @@ extern "C" int dfd_boot_stats(const float* const* score_ptrs, const int* const* 
         const int r = B - b0 < R ? B - b0 : R;
         boot_launch_counts(n, b0, r, seed, (uint32_t*)ws, st);
         hipLaunchKernelGGL(k_boot_glb, dim3(r, M), dim3(BOOT_THREADS), 0, st, mem, (const uint32_t*)ws, is_positive, hit, n, B, b0, stats);
+    }
+    return DFD_CHECK_LAUNCH();
+}
+
+// ---------------------------------------------------------------------------------------------------------------- cluster bootstrap
+static bool boot_grouped_ok(int n, int G, int max_size, int B) {
+    return boot_shape_ok(n, B) && G >= 1 && G <= n && max_size >= 1 && max_size <= n &&
+           (uint64_t)G * (uint64_t)max_size <= DFD_BOOT_GROUPED_MAX_WEIGHT;
+}
+
+extern "C" size_t dfd_boot_ws_grouped(int n, int G, int B) {
+    if (!boot_shape_ok(n, B) || G < 1 || G > n || G <= DFD_BOOT_LDS_MAX_N) return 0;
+    return (size_t)B * (size_t)G * sizeof(uint32_t);
+}
+
+extern "C" int dfd_boot_plan_grouped(int n, int G, int max_size, int B, int M, size_t ws_bytes, int* plan) {
+    if (!boot_grouped_ok(n, G, max_size, B)) return DFD_EINVAL;
+    return dfd_boot_plan(G, B, M, ws_bytes, plan);                      // the tiers, passes and draw tiles of G counts
+}
+
+extern "C" int dfd_boot_stats_grouped(const float* const* score_ptrs, const int* const* perm_ptrs, int M, const unsigned char* is_positive,
+                                      const unsigned char* hit, const double* cuts, const int* group, int n, int G, int max_size, int B,
+                                      uint64_t seed, void* ws, size_t ws_bytes, int64_t* stats, dfd_stream stream) {
+    int plan[4];
+    if (dfd_boot_plan_grouped(n, G, max_size, B, M, ws_bytes, plan) != DFD_OK || !stats) return DFD_EINVAL;
+    if (!score_ptrs || !perm_ptrs || !is_positive || !group) return DFD_EINVAL;
+    BootMembers mem = {};
+    if (!boot_members(score_ptrs, perm_ptrs, cuts, M, n, mem)) return DFD_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (plan[0] == DFD_BOOT_TIER_LDS) {
+        dfd_allow_lds_once<k_boot_lds_g>(160 * 1024);
+        hipLaunchKernelGGL(k_boot_lds_g, dim3(B), dim3(BOOT_THREADS), DFD_BOOT_SCRATCH_BYTES + (size_t)G * sizeof(uint32_t), st, mem, M,
+                           is_positive, hit, group, n, G, B, (uint32_t)seed, (uint32_t)(seed >> 32), stats);
+        return DFD_CHECK_LAUNCH();
+    }
+    if (!ws) return DFD_EINVAL;
+    const int R = plan[1];
+    for (int b0 = 0; b0 < B; b0 += R) {
+        const int r = B - b0 < R ? B - b0 : R;
+        boot_launch_counts(G, b0, r, seed, (uint32_t*)ws, st);
+        hipLaunchKernelGGL(k_boot_glb_g, dim3(r, M), dim3(BOOT_THREADS), 0, st, mem, (const uint32_t*)ws, is_positive, hit, group, n, G, B,
+                           b0, stats);
     }
     return DFD_CHECK_LAUNCH();
 }

@@ -1609,29 +1609,37 @@ def boot_counts(n: int, b0: int, R: int, seed: int, device, out: torch.Tensor | 
     return counts
 
 
+def _boot_inputs(op: str, sorted_scores, perms, is_positive: torch.Tensor, hit, cuts, groups: torch.Tensor | None = None):
+    """What boot_stats and boot_stats_grouped check alike -> (the members, their permutations, one cut or NaN per member)."""
+    members, perm_list = list(sorted_scores), list(perms)
+    M = len(members)
+    if not 1 <= M <= BOOT_MAX_MEMBERS or len(perm_list) != M:
+        raise ValueError(f"{op}: takes 1..{BOOT_MAX_MEMBERS} members with one permutation each, got {M} and {len(perm_list)}")
+    n, device = members[0].numel(), members[0].device
+    for many, dtype in ((members, torch.float32), (perm_list, torch.int32), ([groups] if groups is not None else [], torch.int32)):
+        for t in many:
+            if t.dtype != dtype or tuple(t.shape) != (n,) or t.device != device:
+                raise ValueError(f"{op}: expected f32 [{n}] scores and int32 [{n}] permutations (and group ids) on {device}, got {t.dtype} "
+                                 f"{tuple(t.shape)}")
+    for name, t in (("is_positive", is_positive), ("hit", hit)):
+        if t is not None and (t.dtype != torch.uint8 or tuple(t.shape) != (n,) or t.device != device):
+            raise ValueError(f"{op}: {name} must be uint8 [{n}] on {device}, got {t.dtype} {tuple(t.shape)}")
+    values = [float("nan")] * M if cuts is None else [float("nan") if c is None else float(c) for c in cuts]
+    if len(values) != M:
+        raise ValueError(f"{op}: {M} members need {M} cuts, got {len(values)}")
+    return members, perm_list, values
+
+
 def boot_stats(sorted_scores, perms, is_positive: torch.Tensor, replicates: int, seed: int = 0, cuts=None, hit: torch.Tensor | None = None,
                ws: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
     """M members' f32 [n] scores sorted ascending and the int32 [n] permutations that sorted them, uint8 [n] is_positive (and
     optionally uint8 [n] hit) in sample order -> int64 [M, B, BOOT_STATS_LEN] = P, N, two_u, tp, fp, hits, f0, t0, f1, t1 of
     every bootstrap resample (include/dfd_hip.h).  cuts: one float or None per member (None: no cut).  `ws`: uint8 scratch for the
     global tier, at least 4 n bytes (one resample per pass); by default boot_ws(n, B) bytes capped at BOOT_WS_CAP.  No host sync."""
-    members, perm_list = list(sorted_scores), list(perms)
-    M, B = len(members), int(replicates)
-    if not 1 <= M <= BOOT_MAX_MEMBERS or len(perm_list) != M:
-        raise ValueError(f"boot_stats: takes 1..{BOOT_MAX_MEMBERS} members with one permutation each, got {M} and {len(perm_list)}")
-    n, device = members[0].numel(), members[0].device
+    members, perm_list, values = _boot_inputs("boot_stats", sorted_scores, perms, is_positive, hit, cuts)
+    M, B, n, device = len(members), int(replicates), members[0].numel(), members[0].device
     _boot_shape("boot_stats", n, B, M)
     seed = _boot_seed("boot_stats", seed)
-    for group, dtype in ((members, torch.float32), (perm_list, torch.int32)):
-        for t in group:
-            if t.dtype != dtype or tuple(t.shape) != (n,) or t.device != device:
-                raise ValueError(f"boot_stats: expected f32 [{n}] scores and int32 [{n}] permutations on {device}, got {t.dtype} {tuple(t.shape)}")
-    for name, t in (("is_positive", is_positive), ("hit", hit)):
-        if t is not None and (t.dtype != torch.uint8 or tuple(t.shape) != (n,) or t.device != device):
-            raise ValueError(f"boot_stats: {name} must be uint8 [{n}] on {device}, got {t.dtype} {tuple(t.shape)}")
-    values = [float("nan")] * M if cuts is None else [float("nan") if c is None else float(c) for c in cuts]
-    if len(values) != M:
-        raise ValueError(f"boot_stats: {M} members need {M} cuts, got {len(values)}")
     if ws is None:
         ws = torch.empty(_boot_default_ws(n, B), dtype=torch.uint8, device=device)
     elif ws.dtype != torch.uint8 or ws.device != device or (n > BOOT_LDS_MAX_N and ws.numel() < 4 * n):
@@ -1643,6 +1651,132 @@ def boot_stats(sorted_scores, perms, is_positive: torch.Tensor, replicates: int,
                               seed, _p(ws) if ws.numel() else None, ws.numel(), _p(stats), _stream()),
           "dfd_boot_stats", f"n={n} B={B} M={M}")
     return stats
+
+
+# ------------------------------------------------------------------ the cluster bootstrap (ABI 154, csrc/dfd_boot.hip)
+BOOT_GROUPED_MAX_WEIGHT = _lib.BOOT_GROUPED_MAX_WEIGHT
+
+
+def _boot_grouped_shape(op: str, n: int, G: int, max_size: int, B: int, M: int = 1) -> None:
+    _boot_shape(op, n, B, M)
+    if not 1 <= G <= n or not 1 <= max_size <= n or G * max_size > BOOT_GROUPED_MAX_WEIGHT:
+        raise ValueError(f"{op}: takes 1..n groups of at most max_size <= n samples with groups * max_size <= {BOOT_GROUPED_MAX_WEIGHT}, "
+                         f"got n={n}, groups={G}, max_size={max_size}")
+
+
+def boot_ws_grouped(n: int, num_groups: int, B: int) -> int:
+    """Bytes of workspace with which boot_stats_grouped runs B resamples of num_groups groups in one pass (0 in the LDS tier)."""
+    _boot_grouped_shape("boot_ws_grouped", n, num_groups, 1, B)
+    return _L().dfd_boot_ws_grouped(int(n), int(num_groups), int(B))
+
+
+def _boot_grouped_default_ws(n: int, G: int, B: int) -> int:
+    need = boot_ws_grouped(n, G, B)
+    return need if need <= BOOT_WS_CAP else max(BOOT_WS_CAP // (4 * G), 1) * 4 * G
+
+
+def boot_plan_grouped(n: int, num_groups: int, max_size: int, B: int, M: int = 1, ws_bytes: int | None = None) -> BootPlan:
+    """boot_plan of the cluster bootstrap: the tier boundary is on num_groups (host code)."""
+    n, G, max_size = int(n), int(num_groups), int(max_size)
+    _boot_grouped_shape("boot_plan_grouped", n, G, max_size, B, M)
+    if ws_bytes is None:
+        ws_bytes = _boot_grouped_default_ws(n, G, B)
+    out = (ctypes.c_int * 4)()
+    check(_L().dfd_boot_plan_grouped(n, G, max_size, int(B), int(M), int(ws_bytes), out), "dfd_boot_plan_grouped",
+          f"n={n} G={G} max_size={max_size} B={B} M={M} ws={ws_bytes}")
+    return BootPlan(*out)
+
+
+def boot_stats_grouped(sorted_scores, perms, is_positive: torch.Tensor, groups: torch.Tensor, num_groups: int, max_size: int,
+                       replicates: int, seed: int = 0, cuts=None, hit: torch.Tensor | None = None, ws: torch.Tensor | None = None,
+                       out: torch.Tensor | None = None) -> torch.Tensor:
+    """boot_stats of the cluster bootstrap (include/dfd_hip.h): a resample draws num_groups whole groups, and sample i counts as
+    often as its group groups[i] (int32 [n], sample order; an id outside [0, num_groups) counts for nothing) was drawn.  max_size:
+    the caller's bound on the largest group; num_groups * max_size <= BOOT_GROUPED_MAX_WEIGHT.  `ws`: uint8 scratch for the global
+    tier (num_groups > BOOT_LDS_MAX_N), at least 4 num_groups bytes.  No host sync."""
+    members, perm_list, values = _boot_inputs("boot_stats_grouped", sorted_scores, perms, is_positive, hit, cuts, groups)
+    M, B, G, max_size, n, device = len(members), int(replicates), int(num_groups), int(max_size), members[0].numel(), members[0].device
+    _boot_grouped_shape("boot_stats_grouped", n, G, max_size, B, M)
+    seed = _boot_seed("boot_stats_grouped", seed)
+    if ws is None:
+        ws = torch.empty(_boot_grouped_default_ws(n, G, B), dtype=torch.uint8, device=device)
+    elif ws.dtype != torch.uint8 or ws.device != device or (G > BOOT_LDS_MAX_N and ws.numel() < 4 * G):
+        raise ValueError(f"boot_stats_grouped: ws must be a uint8 tensor of at least {4 * G} bytes on {device}")
+    stats = _dst(out, (M, B, BOOT_STATS_LEN), device, torch.int64)
+    score_ptrs = (ctypes.c_void_p * M)(*[_p(t) for t in members])
+    perm_ptrs = (ctypes.c_void_p * M)(*[_p(t) for t in perm_list])
+    check(_L().dfd_boot_stats_grouped(score_ptrs, perm_ptrs, M, _p(is_positive), _p(hit), (ctypes.c_double * M)(*values), _p(groups), n, G,
+                                      max_size, B, seed, _p(ws) if ws.numel() else None, ws.numel(), _p(stats), _stream()),
+          "dfd_boot_stats_grouped", f"n={n} G={G} max_size={max_size} B={B} M={M}")
+    return stats
+
+
+# ------------------------------------------------------------------ group pooling (ABI 154, csrc/dfd_group.hip)
+GROUP_MEAN, GROUP_VOTE, GROUP_MAX = _lib.GROUP_MEAN, _lib.GROUP_VOTE, _lib.GROUP_MAX
+GROUP_MAX_N, GROUP_MAX_J, GROUP_LDS_BYTES = _lib.GROUP_MAX_N, _lib.GROUP_MAX_J, _lib.GROUP_LDS_BYTES
+GROUP_TIER_LDS, GROUP_TIER_GLOBAL = _lib.GROUP_TIER_LDS, _lib.GROUP_TIER_GLOBAL
+(GROUP_INVALID, GROUP_OOB, GROUP_MIXED, GROUP_EMPTY) = range(4)
+
+
+@dataclass(frozen=True)
+class GroupPlan:
+    """dfd_group_plan's answer: the tier, the accumulate workgroups, the LDS bytes of each (0 in the global tier) and the finish
+    workgroups."""
+
+    tier: int
+    workgroups: int
+    lds_bytes: int
+    finish_workgroups: int
+
+
+def _group_shape(op: str, n: int, G: int, J: int) -> None:
+    if not 1 <= G <= n <= GROUP_MAX_N or not 1 <= J <= GROUP_MAX_J:
+        raise ValueError(f"{op}: takes 1 <= groups <= rows <= {GROUP_MAX_N} and 1..{GROUP_MAX_J} classes, got rows={n}, groups={G}, J={J}")
+
+
+def group_ws(n: int, num_groups: int, J: int) -> int:
+    """Bytes of workspace group_pool needs."""
+    _group_shape("group_ws", n, num_groups, J)
+    return _L().dfd_group_ws(int(n), int(num_groups), int(J))
+
+
+def group_plan(n: int, num_groups: int, J: int) -> GroupPlan:
+    """Which tier group_pool runs for n rows of J classes in num_groups groups, and its launch shape (host code)."""
+    _group_shape("group_plan", n, num_groups, J)
+    out = (ctypes.c_int * 4)()
+    check(_L().dfd_group_plan(int(n), int(num_groups), int(J), out), "dfd_group_plan", f"n={n} G={num_groups} J={J}")
+    return GroupPlan(*out)
+
+
+def group_pool(probs: torch.Tensor, groups: torch.Tensor, targets: torch.Tensor, num_groups: int, mode: int = GROUP_MEAN,
+               positive: int = 1, ws: torch.Tensor | None = None, out=None):
+    """f32 [n, J] probabilities, int32 [n] group ids in [0, num_groups) and int64 [n] targets -> (probs f32 [G, J], preds int64 [G],
+    targets int64 [G], sizes int32 [G], info int64 [4] = invalid rows / ids out of range / groups with mixed targets / empty
+    groups): include/dfd_hip.h.  GROUP_MEAN and GROUP_VOTE sum integers, GROUP_MAX copies the member row with the largest
+    probs[:, positive]; the bits do not depend on the order of the rows.  Three launches, no host sync.  `ws`: uint8 scratch of
+    group_ws bytes; `out`: the five destinations."""
+    if probs.dim() != 2 or probs.dtype != torch.float32 or targets.dtype != torch.int64 or groups.dtype != torch.int32 or \
+            tuple(targets.shape) != (probs.shape[0],) or tuple(groups.shape) != (probs.shape[0],):
+        raise ValueError(f"group_pool: expected f32 [n, J] rows, int32 [n] groups and int64 [n] targets, got {probs.dtype} "
+                         f"{tuple(probs.shape)}, {groups.dtype} {tuple(groups.shape)} and {targets.dtype} {tuple(targets.shape)}")
+    n, J = probs.shape
+    G, mode, positive = int(num_groups), int(mode), int(positive)
+    _group_shape("group_pool", n, G, J)
+    if mode not in (GROUP_MEAN, GROUP_VOTE, GROUP_MAX) or not 0 <= positive < J:
+        raise ValueError(f"group_pool: mode must be 0..2 and positive a class below {J}, got {mode}, {positive}")
+    device = probs.device
+    need = group_ws(n, G, J)                                            # G (8 J + 12): not always a multiple of 8
+    ws = _f64_ws("group_pool", ws, need, device) if ws is not None else \
+        torch.empty((need + 7) // 8, dtype=torch.float64, device=device).view(torch.uint8)
+    o = out if out is not None else (None,) * 5
+    pooled = _dst(o[0], (G, J), device)
+    preds = _dst(o[1], (G,), device, torch.int64)
+    tgt = _dst(o[2], (G,), device, torch.int64)
+    sizes = _dst(o[3], (G,), device, torch.int32)
+    info = _dst(o[4], (4,), device, torch.int64)
+    check(_L().dfd_group_pool(_p(probs), _p(groups), _p(targets), n, G, J, mode, positive, _p(ws), ws.numel(), _p(pooled), _p(preds),
+                              _p(tgt), _p(sizes), _p(info), _stream()), "dfd_group_pool", f"n={n} G={G} J={J} mode={mode}")
+    return pooled, preds, tgt, sizes, info
 
 
 # ------------------------------------------------------------------ Grad-CAM (ABI 136)

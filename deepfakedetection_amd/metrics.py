@@ -19,12 +19,19 @@ returns it with its gradient and Hessian for eight step lengths at once, so the 
 per iteration.  `diversity` counts how the members' right and wrong predictions coincide; every figure it returns is one division
 of Python integers.
 
-`ScoreBook` and `gather_scores` are plain torch (they run on the CPU and under gloo as well); the metrics themselves need a
+`group_ids` turns the sample paths of a split into group ids on the host (the video a frame was cut from), `group_pool` pools the
+rows of every group into one row with csrc/dfd_group.hip (exact integer sums, or the member row with the largest positive score),
+and `bootstrap(groups=...)` resamples whole groups instead of samples: the cluster bootstrap, for samples that are correlated
+inside a group.
+
+`ScoreBook`, `group_ids` and `gather_scores` are plain torch / numpy (they run on the CPU and under gloo as well); the metrics themselves need a
 HIP device, like every kernel front end.
 """
 
 from __future__ import annotations
 
+import os
+import re
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -32,9 +39,10 @@ import torch
 
 from . import kernels as K
 
-__all__ = ["BootstrapResult", "CalibrationResult", "DeltaResult", "DiversityResult", "FusionFit", "RocResult", "ScoreBook", "TemperatureFit",
-           "apply_temperature", "binary_roc", "boot_values", "bootstrap", "calibration", "confusion", "diversity", "eer_from_curve",
-           "fit_fusion", "fit_temperature", "fuse", "gather_scores", "mean_nll", "ovr_auc", "paired_delta", "percentile_interval"]
+__all__ = ["BootstrapResult", "CalibrationResult", "DeltaResult", "DiversityResult", "FusionFit", "GroupScores", "RocResult", "ScoreBook",
+           "TemperatureFit", "apply_temperature", "binary_roc", "boot_values", "bootstrap", "calibration", "confusion", "diversity",
+           "eer_from_curve", "fit_fusion", "fit_temperature", "fuse", "gather_scores", "group_ids", "group_pool", "mean_nll", "ovr_auc",
+           "paired_delta", "percentile_interval"]
 
 
 class ScoreBook:
@@ -278,6 +286,7 @@ class BootstrapResult:
     seed: int
     level: float
     point: list
+    clusters: int | None = None                     # the groups a resample draws (the cluster bootstrap); None: it draws samples
 
     def values(self, metric: str) -> np.ndarray:
         """f64 [M, B]: the metric of every member in every resample (boot_values)."""
@@ -313,14 +322,17 @@ def _point_figures(roc: RocResult, hits: int | None, n: int) -> dict:
 
 
 def bootstrap(scores, labels: torch.Tensor, *, positive: int = 1, cut=None, hits: torch.Tensor | None = None, replicates: int = 2000,
-              seed: int = 0, level: float = 0.95) -> BootstrapResult:
+              seed: int = 0, level: float = 0.95, groups: torch.Tensor | None = None) -> BootstrapResult:
     """The nonparametric bootstrap of the ROC figures: `replicates` resamples of the n samples, drawn on the device by the rule of
     include/dfd_hip.h (Philox4x32-10 keyed by `seed`), each judged by kernels.boot_stats.  scores: one float tensor [n] on the
     device or a list of M <= kernels.BOOT_MAX_MEMBERS over the same samples, which then share every resample (BootstrapResult.delta
     compares them pairwise).  cut: the threshold of accuracy / balanced_accuracy / tpr / fpr (score >= cut predicts `positive`,
     compared in f64), one number or one per member; it is held fixed, not chosen again per resample.  hits: optional [n] flags
     (nonzero = this sample was judged right) behind hit_rate.  Each member is sorted once; the resamples are multiplicities over
-    that order, so none of them sorts.  Non-finite scores raise ValueError.  One read-back after the last launch."""
+    that order, so none of them sorts.  Non-finite scores raise ValueError.  One read-back after the last launch.
+    groups: integer group ids [n] (the video of each frame, ids >= 0) turn this into the cluster bootstrap: a resample draws
+    G = max id + 1 whole groups by the same rule and every sample counts as often as its group was drawn, which is the right unit
+    when the samples of a group are correlated.  G and the largest group are read back once before the launches."""
     members = [scores] if isinstance(scores, torch.Tensor) else list(scores)
     if not 1 <= len(members) <= K.BOOT_MAX_MEMBERS:
         raise ValueError(f"bootstrap: takes 1..{K.BOOT_MAX_MEMBERS} score vectors, got {len(members)}")
@@ -345,12 +357,93 @@ def bootstrap(scores, labels: torch.Tensor, *, positive: int = 1, cut=None, hits
         ordered.append(s.contiguous())
         perms.append(order.to(torch.int32).contiguous())
         rocs.append(_roc_of_sorted(ordered[-1], labels[order].contiguous(), int(positive), None if c is None else [float(c)], True))
-    stats_d = K.boot_stats(ordered, perms, is_positive, B, seed, cuts, hit)
+    clusters = None
+    if groups is not None:
+        ids = groups.detach().reshape(-1).to(device=labels.device, dtype=torch.int32).contiguous()
+        if ids.numel() != n:
+            raise ValueError(f"bootstrap: {ids.numel()} group ids for {n} labels")
+        uniq, sizes = torch.unique(ids, return_counts=True)
+        low, high, largest = (int(v) for v in torch.stack([uniq.min().long(), uniq.max().long(), sizes.max()]).tolist())   # the extra read-back
+        if low < 0:
+            raise ValueError(f"bootstrap: group ids must be >= 0, got {low}")
+        clusters = high + 1
+        stats_d = K.boot_stats_grouped(ordered, perms, is_positive, ids, clusters, largest, B, seed, cuts, hit)
+    else:
+        stats_d = K.boot_stats(ordered, perms, is_positive, B, seed, cuts, hit)
     total_hits = hit.sum(dtype=torch.int64).reshape(1) if hit is not None else stats_d.new_zeros(1)
     packed = torch.cat([stats_d.reshape(-1), total_hits]).cpu().numpy()   # the one read-back of the resamples
     stats = packed[:-1].reshape(count, B, K.BOOT_STATS_LEN).copy()
     n_hits = int(packed[-1]) if hit is not None else None
-    return BootstrapResult(stats, B, int(seed), float(level), [_point_figures(r, n_hits, n) for r in rocs])
+    return BootstrapResult(stats, B, int(seed), float(level), [_point_figures(r, n_hits, n) for r in rocs], clusters)
+
+
+GROUP_POOLS = {"mean": K.GROUP_MEAN, "vote": K.GROUP_VOTE, "max": K.GROUP_MAX}
+
+
+@dataclass
+class GroupScores:
+    """What group_pool found, on the device: one row per group (probs f32 [G, J], preds / targets int64 [G], sizes int32 [G]; an
+    empty group holds zeros, pred 0, target -1, size 0) and info = the rows left out as invalid, the rows left out for an id out of
+    range, the groups with mixed targets (always 0: they raise) and the empty groups, as Python integers."""
+
+    probs: torch.Tensor
+    preds: torch.Tensor
+    targets: torch.Tensor
+    sizes: torch.Tensor
+    info: tuple
+
+
+def group_pool(probs: torch.Tensor, groups: torch.Tensor, targets: torch.Tensor, mode: str = "mean", positive: int = 1,
+               num_groups: int | None = None) -> GroupScores:
+    """Pool the rows of every group (the frames of a video) into one row with kernels.group_pool: `mean` of the probabilities,
+    `vote` = the share of rows whose arg max is each class, `max` = the member row with the largest probs[:, positive].  mean and
+    vote are sums of integers (multiples of 2^-32), so the pooled bits do not depend on the order of the rows.  groups: integer ids
+    [n]; num_groups: G (default: the largest id + 1, one more read-back).  A group is judged against its smallest member target; a
+    group whose members disagree raises ValueError.  One read-back of `info` after the last launch."""
+    if mode not in GROUP_POOLS:
+        raise ValueError(f"group_pool: mode must be one of {', '.join(GROUP_POOLS)}, got {mode!r}")
+    probs = probs.detach().float().contiguous()
+    targets = targets.detach().reshape(-1).to(torch.int64).contiguous()
+    ids = groups.detach().reshape(-1).to(device=probs.device, dtype=torch.int32).contiguous()
+    G = int(ids.max().item()) + 1 if num_groups is None else int(num_groups)
+    pooled, preds, tgt, sizes, info_d = K.group_pool(probs, ids, targets, G, GROUP_POOLS[mode], positive)
+    info = tuple(int(v) for v in info_d.tolist())
+    if info[K.GROUP_MIXED]:
+        raise ValueError(f"group_pool: {info[K.GROUP_MIXED]} of {G} groups hold rows with different targets")
+    return GroupScores(pooled, preds, tgt, sizes, info)
+
+
+def group_ids(paths, root, key: str = "parent", pattern: str | None = None) -> tuple[np.ndarray, int, list[str]]:
+    """The group (video) of every file of a split, on the host: (int32 ids [n], G, the groups' names).  Ids are dense, in order of
+    first appearance.  The class directory is part of every key, so a video name under two classes gives two groups.
+    key="parent": the file's directory relative to `root`; a file lying directly in a class directory is a group of its own.
+    key="regex": (that directory, group 1 of re.fullmatch(pattern, stem)); a stem that does not match is a group of its own."""
+    if key not in ("parent", "regex"):
+        raise ValueError(f"group_ids: key must be 'parent' or 'regex', got {key!r}")
+    if key == "regex":
+        if not pattern:
+            raise ValueError("group_ids: key='regex' needs a pattern")
+        rx = re.compile(pattern)
+        if rx.groups < 1:
+            raise ValueError(f"group_ids: the pattern {pattern!r} has no capture group")
+    root = os.path.normpath(os.fspath(root))
+    table: dict = {}
+    ids = np.empty(len(paths), dtype=np.int32)
+    for i, path in enumerate(paths):
+        rel = os.path.relpath(os.path.normpath(os.fspath(path)), root).replace(os.sep, "/")
+        folder, _, name = rel.rpartition("/")
+        video = None
+        if key == "parent":
+            if "/" in folder:                                           # below the class directory: the directory is the video
+                video = folder
+        else:
+            m = rx.fullmatch(os.path.splitext(name)[0])
+            if m is not None and m.group(1) is not None:
+                video = f"{folder}/{m.group(1)}"
+        ident = ("group", video) if video is not None else ("file", rel)       # a file of its own never merges with a video's key
+        ids[i] = table.setdefault(ident, len(table))
+    names = [k[1] for k in table]
+    return ids, len(table), names
 
 
 def ovr_auc(probs: torch.Tensor, targets: torch.Tensor, num_classes: int, strict: bool = True) -> float | None:

@@ -30,6 +30,7 @@ import io
 import json
 import math
 import os
+import re
 import sys
 from collections.abc import Iterator
 from dataclasses import asdict, dataclass, replace
@@ -379,6 +380,38 @@ def bootstrap_settings(raw: Any, where: str = "inference.bootstrap") -> tuple[in
     if not 0 <= seed < 1 << 64:
         raise ValueError(f"{where}.seed must be an unsigned 64-bit integer, got {raw.get('seed')!r}")
     return replicates, level, seed
+
+
+GROUP_KEYS, GROUP_POOLS = ("parent", "regex"), ("mean", "vote", "max")
+
+
+def group_settings(raw: Any, where: str = "inference.group_by") -> tuple[str, str | None, str] | None:
+    """Extra key `inference.group_by: {key: parent, pool: mean}` or `{key: regex, pattern: '^(.+)_\\d+$', pool: vote}`: (key,
+    pattern, pool) by which the frames of a split are grouped into videos (metrics.group_ids) and a video's frames pooled into one
+    score (metrics.group_pool), or None without the key.  pool: mean (the default), vote or max.  ValueError for another key, an
+    unknown value, `regex` without a pattern that compiles and has a capture group, or a pattern without `regex`."""
+    if raw is None or raw is False:
+        return None
+    if not isinstance(raw, dict):
+        raise ValueError(f"{where} must be a mapping like {{key: parent, pool: mean}}, got {raw!r}")
+    unknown = sorted(set(map(str, raw)) - {"key", "pattern", "pool"})
+    if unknown:
+        raise ValueError(f"{where} takes key, pattern and pool; not {', '.join(unknown)}")
+    key, pool, pattern = str(raw.get("key", "parent")).strip().lower(), str(raw.get("pool", "mean")).strip().lower(), raw.get("pattern")
+    if key not in GROUP_KEYS:
+        raise ValueError(f"{where}.key must be one of {', '.join(GROUP_KEYS)}, got {raw.get('key')!r}")
+    if pool not in GROUP_POOLS:
+        raise ValueError(f"{where}.pool must be one of {', '.join(GROUP_POOLS)}, got {raw.get('pool')!r}")
+    if key == "regex":
+        try:
+            groups = re.compile(str(pattern)).groups if isinstance(pattern, str) and pattern else 0
+        except re.error as exc:
+            raise ValueError(f"{where}.pattern does not compile: {exc}") from None
+        if groups < 1:
+            raise ValueError(f"{where}.pattern must be a regular expression with a capture group, got {pattern!r}")
+    elif pattern is not None:
+        raise ValueError(f"{where}.pattern needs key: regex")
+    return key, (str(pattern) if key == "regex" else None), pool
 
 
 @dataclass(frozen=True)
@@ -747,10 +780,55 @@ class PassResult:
     cm: np.ndarray
     roc: Any                        # the binary metrics.RocResult of a device book, else None
     reliability: Any                # (temperature, CalibrationResult at T = 1, at T) of a clean pass under calibration, else None
+    group_record: dict[str, Any] | None = None      # the second record of the pass under inference.group_by, else None
 
 
-def _judge(s: InferenceSettings, book, threshold: float, calib: _Calibration | None, clean: bool = False) -> PassResult:
-    """A filled book -> the pass's result: rescaled first under inference.calibration, then judged where the book lives."""
+@dataclass
+class _Groups:
+    """inference.group_by of one split: every sample's group id beside the book's rows (int32 on the book's device), the groups,
+    those of one sample, the pooling mode and the threshold the pooled scores are judged at (the balanced-accuracy threshold of
+    the pooled validation pass, else the frame path's default), held fixed for every level."""
+    ids: torch.Tensor
+    count: int
+    singletons: int
+    pool: str
+    threshold: float = 0.5
+
+
+def _split_groups(s: "InferenceSettings", paths: list[str], split: str, device) -> _Groups:
+    key, pattern, pool = s.group_by
+    ids, count, _ = M.group_ids(paths, s.root / split, key, pattern)
+    sizes = np.bincount(ids, minlength=count)
+    return _Groups(torch.from_numpy(ids).to(device), count, int((sizes == 1).sum()), pool)
+
+
+def _pooled_book(book, groups: _Groups) -> M.ScoreBook:
+    """The book of the groups' pooled scores.  group_ids keeps the class directory in every key, so no group mixes targets; a row
+    that cannot be pooled (a probability that is NaN or outside [0, 1]) is an error here."""
+    pooled = M.group_pool(book.probs, groups.ids, book.targets, groups.pool, positive=1 if book.num_classes > 1 else 0, num_groups=groups.count)
+    if any(pooled.info):
+        raise ValueError(f"inference.group_by: {pooled.info[0]} rows are not probabilities, {pooled.info[1]} ids are out of range and "
+                         f"{pooled.info[3]} of {groups.count} groups are empty")
+    out = M.ScoreBook(groups.count, book.num_classes, book.probs.device)
+    out.append(pooled.probs, pooled.preds, pooled.targets)
+    return out
+
+
+def _group_record(s: "InferenceSettings", book, groups: _Groups) -> dict[str, Any]:
+    """The pass judged per group: the pooled scores through the frame path's own record function, at the groups' threshold; under
+    inference.bootstrap the ordinary bootstrap over the G pooled scores."""
+    pooled = _pooled_book(book, groups)
+    record, _, _, _, _, roc = _split_metrics_device(s.name, s.split, pooled, s.num_classes, groups.threshold)
+    record.update(unit="group", pool=groups.pool, groups=groups.count, singletons=groups.singletons)
+    if s.bootstrap is not None and roc is not None:
+        record.update(_bootstrap_keys(pooled, groups.threshold, s.bootstrap, roc))
+    return record
+
+
+def _judge(s: InferenceSettings, book, threshold: float, calib: _Calibration | None, clean: bool = False,
+           groups: _Groups | None = None) -> PassResult:
+    """A filled book -> the pass's result: rescaled first under inference.calibration, then judged where the book lives.  groups
+    (inference.group_by): the pass is judged per group too, and the frame record's intervals come from the cluster bootstrap."""
     figures, reliability = calib.apply(book, clean) if calib is not None else ({}, None)
     if book.probs.is_cuda:
         record, probs, preds, targets, cm, roc = _split_metrics_device(s.name, s.split, book, s.num_classes, threshold)
@@ -759,21 +837,26 @@ def _judge(s: InferenceSettings, book, threshold: float, calib: _Calibration | N
         record, preds, cm = _split_metrics(s.name, s.split, probs, book.preds.clone(), targets, s.num_classes, threshold)
     record.update(figures)
     if s.bootstrap is not None and roc is not None:
-        record.update(_bootstrap_keys(book, threshold, s.bootstrap, roc))
-    return PassResult(record, probs, preds, targets, cm, roc, reliability)
+        record.update(_bootstrap_keys(book, threshold, s.bootstrap, roc, groups))
+    group_record = _group_record(s, book, groups) if groups is not None else None
+    return PassResult(record, probs, preds, targets, cm, roc, reliability, group_record)
 
 
 BOOT_RECORD_METRICS = (("roc_auc", "auc"), ("eer", "eer"), ("accuracy", "accuracy"), ("balanced_accuracy", "balanced_accuracy"))
 
 
-def _bootstrap_keys(book, threshold: float, settings: tuple[int, float, int], roc) -> dict[str, Any]:
+def _bootstrap_keys(book, threshold: float, settings: tuple[int, float, int], roc, groups: _Groups | None = None) -> dict[str, Any]:
     """The `ci` and `bootstrap` keys of a binary pass kept on the device: percentile intervals at the threshold in force, which is
-    held fixed (its own uncertainty is not resampled).  Scores that are not finite leave ci None."""
+    held fixed (its own uncertainty is not resampled).  Scores that are not finite leave ci None.  groups: the resamples draw
+    whole groups (the cluster bootstrap), and `bootstrap` says so."""
     replicates, level, seed = settings
     about: dict[str, Any] = {"replicates": replicates, "seed": seed, "level": level, "degenerate": None}
+    if groups is not None:
+        about.update(cluster=True, groups=groups.count)
     if roc.nonfinite:
         return {"ci": None, "bootstrap": about}
-    res = M.bootstrap(book.probs[:, 1], book.targets, cut=threshold, replicates=replicates, seed=seed, level=level)
+    res = M.bootstrap(book.probs[:, 1], book.targets, cut=threshold, replicates=replicates, seed=seed, level=level,
+                      groups=groups.ids if groups is not None else None)
     about["degenerate"] = res.degenerate()
     ci = {}
     for key, metric in BOOT_RECORD_METRICS:
@@ -858,6 +941,7 @@ class InferenceSettings:
     robustness: tuple[tuple[str, float | int], ...]         # the robustness_levels that can run (the device pipeline's batch is perturbed)
     cam_limit: int | None                           # None also where Grad-CAM cannot run
     bootstrap: tuple[int, float, int] | None = None     # extra key (bootstrap_settings): every judged pass gains `ci` and `bootstrap`
+    group_by: tuple[str, str | None, str] | None = None     # extra key (group_settings): every judged pass gains a record per group
 
 
 def inference_settings(config: dict[str, Any], model_cfg: dict[str, Any], out: Console) -> InferenceSettings:
@@ -900,6 +984,10 @@ def inference_settings(config: dict[str, Any], model_cfg: dict[str, Any], out: C
     if bootstrap is not None and not (device_metrics and num_classes == 2):
         out.print("[bold yellow]inference.bootstrap ignored[/]: needs inference.device_metrics on a CUDA device and a binary problem")
         bootstrap = None
+    group_by = group_settings(infer_cfg.get("group_by"))
+    if group_by is not None and not device_metrics:
+        out.print("[bold yellow]inference.group_by ignored[/]: needs inference.device_metrics on a CUDA device")
+        group_by = None
     levels = robustness_levels(infer_cfg)
     if levels and not gpu_resize:           # the perturbation is applied to the cropped uint8 batch of the device pipeline
         out.print("[bold yellow]inference.robustness skipped[/]: needs inference.gpu_resize on a CUDA device")
@@ -917,7 +1005,7 @@ def inference_settings(config: dict[str, Any], model_cfg: dict[str, Any], out: C
         image_size=image_size, batch_size=batch_size, num_workers=int(infer_cfg.get("num_workers", 4)),
         amp=str(infer_cfg.get("amp", "")).lower() in ("bf16", "bfloat16", "true", "1"), device=device,
         fp8_weights=str(infer_cfg.get("fp8_weights", "")).lower() in on, transform=transform,
-        device_metrics=device_metrics, calibration=calibration, bootstrap=bootstrap, robustness=tuple(levels), cam_limit=limit)
+        device_metrics=device_metrics, calibration=calibration, bootstrap=bootstrap, group_by=group_by, robustness=tuple(levels), cam_limit=limit)
 
 
 @dataclass
@@ -946,7 +1034,7 @@ def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: 
         model.fp8_weights = True
     calib = _Calibration(*s.calibration) if s.calibration is not None else None
     capture = capture and s.device_metrics          # the ensemble fuses logits kept on the device
-    threshold = 0.5
+    threshold = group_threshold = 0.5
     val_scores, val_paths = None, []
     if s.num_classes == 2 or (calib is not None and calib.mode == "fit") or capture:
         val_dir = s.root / s.val_split
@@ -958,6 +1046,9 @@ def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: 
             calib.fit(val_book, s.val_split, out)
         if val_book is not None and s.num_classes == 2:
             threshold = _first_set(_validation_threshold(val_book), threshold)
+            if s.group_by is not None:
+                val_groups = _split_groups(s, [str(path) for path, _ in val_set.samples], s.val_split, s.device)
+                group_threshold = _first_set(_validation_threshold(_pooled_book(val_book, val_groups)), group_threshold)
         del val_book                                    # its device buffers go before the split's own book is made
 
     split_dir = s.root / s.split
@@ -973,21 +1064,28 @@ def _run_inference_job(*, config_path: Path, config: dict[str, Any], model_cfg: 
                         TimeElapsedColumn(), TimeRemainingColumn(), TextColumn("{task.fields[speed]}"), console=out)
     book = _score_pass(model, dataset, s, progress=progress, keep_logits=capture)   # one book for this pass and every level below
     clean_scores = (book.logits.clone(), book.targets.clone()) if capture else None
-    clean = _judge(s, book, threshold, calib, clean=True)
+    groups = None
+    if s.group_by is not None:
+        groups = replace(_split_groups(s, [str(path) for path, _ in dataset.samples], s.split, s.device), threshold=group_threshold)
+    clean = _judge(s, book, threshold, calib, clean=True, groups=groups)
     if calib is not None:
         calib.write(run_paths.run_dir)
     scores = clean.probs[:, 1].numpy() if s.num_classes == 2 and torch.unique(clean.targets).numel() > 1 else None
     _save_plots(clean.cm, list(dataset.classes), clean.targets.numpy(), scores, run_paths.plots, roc=clean.roc,
                 reliability=clean.reliability)
     _emit(clean.record, run_paths, out, "[bold]Accuracy[/]:")
+    if clean.group_record is not None:
+        _emit(clean.group_record, run_paths, out, f"[bold]Accuracy per group[/] ({groups.count} groups, {groups.pool}):")
     levels = {}
     for kind, level in s.robustness:
         _score_pass(model, dataset, s, book, tail=robustness_tail(kind, level), keep_logits=capture)
         if capture:
             levels[(kind, level)] = book.logits.clone()
-        perturbed = _judge(s, book, threshold, calib).record        # at the clean pass's threshold and temperature
-        perturbed["perturbation"] = {kind: level}
-        _emit(perturbed, run_paths, out, f"[bold]Robustness[/] {kind}={level:g}: accuracy")
+        judged = _judge(s, book, threshold, calib, groups=groups)   # at the clean pass's thresholds and temperature
+        for perturbed, unit in ((judged.record, ""), (judged.group_record, " per group")):
+            if perturbed is not None:
+                perturbed["perturbation"] = {kind: level}
+                _emit(perturbed, run_paths, out, f"[bold]Robustness[/] {kind}={level:g}: accuracy{unit}")
     if s.cam_limit is not None:
         count = write_cam_overlays(model, dataset, clean.probs, clean.preds, s.cam_limit, run_paths.run_dir / "cam",
                                    batch_size=s.batch_size, num_workers=s.num_workers)
@@ -1076,25 +1174,35 @@ def _run_ensemble_job(ens: EnsembleSettings, names: list[str], members: list[Mem
     doc["coefficients"] = [w / (t if fold and t is not None else 1.0) for w, t in zip(weights, temperatures)]
     pooled = [replace(m, temperature=t) for m, t in zip(members, temperatures)]
 
-    threshold = 0.5
+    threshold = group_threshold = 0.5
     if first.val is not None and s.num_classes == 2:
         val_book = _fused_book(pooled, [m.val[0] for m in members], first.val[1], ens, weights)
         threshold = _first_set(_validation_threshold(val_book), threshold)
+        if s.group_by is not None:
+            val_groups = _split_groups(s, first.val_paths, s.val_split, first.val[1].device)
+            group_threshold = _first_set(_validation_threshold(_pooled_book(val_book, val_groups)), group_threshold)
         del val_book
+    groups = None
+    if s.group_by is not None:                                          # the members share their paths: one grouping for all
+        groups = replace(_split_groups(s, first.paths, s.split, first.clean[1].device), threshold=group_threshold)
     book = book_clean = _fused_book(pooled, [m.clean[0] for m in members], first.clean[1], ens, weights)
-    clean = _judge(s, book, threshold, None, clean=True)
+    clean = _judge(s, book, threshold, None, clean=True, groups=groups)
     clean.record.update(_ensemble_figures(book))
     scores = clean.probs[:, 1].numpy() if s.num_classes == 2 and torch.unique(clean.targets).numel() > 1 else None
     _save_plots(clean.cm, first.classes, clean.targets.numpy(), scores, run_paths.plots, roc=clean.roc)
     _emit(clean.record, run_paths, out, "[bold]Ensemble accuracy[/]:")
+    if clean.group_record is not None:
+        _emit(clean.group_record, run_paths, out, f"[bold]Ensemble accuracy per group[/] ({groups.count} groups, {groups.pool}):")
     for kind, level in first.settings.robustness:
         if not all((kind, level) in m.levels for m in members):
             continue
         book = _fused_book(pooled, [m.levels[(kind, level)] for m in members], first.clean[1], ens, weights)
-        perturbed = _judge(s, book, threshold, None).record             # at the clean pass's threshold and coefficients
-        perturbed.update(_ensemble_figures(book))
-        perturbed["perturbation"] = {kind: level}
-        _emit(perturbed, run_paths, out, f"[bold]Ensemble robustness[/] {kind}={level:g}: accuracy")
+        judged = _judge(s, book, threshold, None, groups=groups)        # at the clean pass's thresholds and coefficients
+        judged.record.update(_ensemble_figures(book))
+        for perturbed, unit in ((judged.record, ""), (judged.group_record, " per group")):
+            if perturbed is not None:
+                perturbed["perturbation"] = {kind: level}
+                _emit(perturbed, run_paths, out, f"[bold]Ensemble robustness[/] {kind}={level:g}: accuracy{unit}")
 
     device = first.clean[1].device
     div = M.diversity([m.preds.to(device) for m in members], first.clean[1], s.num_classes)    # of the predictions the records judge

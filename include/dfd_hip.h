@@ -105,7 +105,10 @@ typedef void* dfd_stream;          /* a hipStream_t */
  * 152 = dfd_stem_bwd_fused / _ok (the stem's weight gradient straight from the incoming gradient, without a stored dz; same bits as
  * dfd_act_bn_bwd + dfd_stem_conv_wgrad); dfd_act_bn_bwd takes dz = NULL: the partial sums only;
  * 153 = dfd_boot_stats, dfd_boot_counts, dfd_boot_plan, dfd_boot_ws (bootstrap resamples of the ROC statistics: Philox draws into
- * integer counts, weighted sweeps of the sorted scores; all outputs integers). */
+ * integer counts, weighted sweeps of the sorted scores; all outputs integers);
+ * 154 = dfd_group_pool, dfd_group_plan, dfd_group_ws (the rows of a group, such as the frames of a video, pooled into one row: exact
+ * integer sums), dfd_boot_stats_grouped, dfd_boot_plan_grouped, dfd_boot_ws_grouped (the cluster bootstrap: a resample draws whole
+ * groups); dfd_boot_stats itself is unchanged. */
 int dfd_version(void);
 
 /* Planner knobs: the tier switches and grid sizes by which tests and per-layer scripts reach a kernel tier.  Process-wide plain ints:
@@ -755,6 +758,68 @@ int dfd_boot_plan(int n, int B, int M, size_t ws_bytes, int* plan);
 int dfd_boot_counts(int n, int b0, int R, uint64_t seed, uint32_t* counts, dfd_stream stream);
 int dfd_boot_stats(const float* const* score_ptrs, const int* const* perm_ptrs, int M, const unsigned char* is_positive,
                    const unsigned char* hit, const double* cuts, int n, int B, uint64_t seed, void* ws, size_t ws_bytes, int64_t* stats,
+                   dfd_stream stream);
+
+/* The cluster bootstrap (csrc/dfd_boot.hip, ABI 154): the samples fall into G groups (the frames of a video), and a resample draws
+ * whole groups.  group int32 [n] holds each sample's group id in sample order, ids in any order.
+ *
+ * The resampling rule is the one above with n replaced by G: draw t (0 <= t < G) of resample b runs Philox4x32-10 with the key
+ * (seed & 0xffffffff, seed >> 32) and the counter (t >> 2, b, 0, DFD_BOOT_STREAM); u = output word t & 3; the drawn group is
+ * ((uint64_t)u * G) >> 32.  g_b[k] is how often group k was drawn, and sample i counts c_b[i] = g_b[group[i]] times; a sample whose id
+ * lies outside [0, G) counts for nothing.  With group[i] = i and G = n this is dfd_boot_stats bit for bit.
+ *
+ * dfd_boot_stats_grouped: dfd_boot_stats' arguments plus group, G and max_size, and the same ten integers per (member, resample) with
+ * the same definitions; the weighted sample count P + N of a resample now varies.  max_size is the caller's bound on the largest
+ * group: no group may have more members.  (uint64_t)G * max_size must not exceed DFD_BOOT_GROUPED_MAX_WEIGHT = 2^31 - 1, which keeps
+ * P, N and the int32 scans exact and two_u below 2^62; scores must be finite.  1 <= G <= n and 1 <= max_size <= n.
+ * The counts have G entries, so the tier boundary is on G: G <= DFD_BOOT_LDS_MAX_N runs the LDS tier for any n; above, the
+ * workspace is uint32 [R][G] and the zero and draw launches run over G.  The sweep gathers counts[group[perm[i]]].
+ * dfd_boot_ws_grouped(n, G, B): the bytes for R = B in the global tier, 0 in the LDS tier or for arguments out of range.
+ * dfd_boot_plan_grouped: plan[4] as dfd_boot_plan's, for G counts.  Arguments out of range, a NULL pointer, G * max_size above the
+ * bound, or a global-tier ws too small for one resample: DFD_EINVAL, nothing is launched. */
+#define DFD_BOOT_GROUPED_MAX_WEIGHT 2147483647
+size_t dfd_boot_ws_grouped(int n, int G, int B);
+int dfd_boot_plan_grouped(int n, int G, int max_size, int B, int M, size_t ws_bytes, int* plan);
+int dfd_boot_stats_grouped(const float* const* score_ptrs, const int* const* perm_ptrs, int M, const unsigned char* is_positive,
+                           const unsigned char* hit, const double* cuts, const int* group, int n, int G, int max_size, int B,
+                           uint64_t seed, void* ws, size_t ws_bytes, int64_t* stats, dfd_stream stream);
+
+/* Group pooling (csrc/dfd_group.hip, ABI 154): the rows of a group (the frames of a video) become one row.  probs f32 [n][J],
+ * group int32 [n] in sample order (any order of ids, 0 <= id < G), targets int64 [n]; 1 <= G <= n <= DFD_GROUP_MAX_N,
+ * 1 <= J <= DFD_GROUP_MAX_J, 0 <= positive < J.
+ *   out_probs f32 [G][J], out_preds int64 [G] (the first arg max of the stored f32 row), out_targets int64 [G], sizes int32 [G],
+ *   info int64 [4] = {invalid rows, ids out of range, groups with mixed targets, empty groups}
+ * A row is invalid when a probability is not in [0, 1] (a NaN included; -0.0 is in) or its target is outside [0, J): it is skipped
+ * and counted in info[0].  A valid row whose id is outside [0, G) is skipped and counted in info[1].  sizes counts the rows that
+ * remain.  A group's target is its smallest member target; a group whose members disagree is counted in info[2].  An empty group
+ * gets a row of zeros, pred 0, target -1, size 0 and is counted in info[3].
+ *   DFD_GROUP_MEAN  each probability becomes q = llrint((double)p * 4294967296.0), the q are summed per (group, class) in uint64
+ *                   (at most 2^24 2^32), and the stored value is (float)((double)sum / ((double)size * 4294967296.0))
+ *   DFD_GROUP_VOTE  the same cells; a row adds 2^32 to the cell of its own first arg max: the share of rows voting for each class
+ *   DFD_GROUP_MAX   a copy of the member row with the largest probs[i][positive] (-0.0 equals 0.0), the lowest i on ties: a 64-bit
+ *                   maximum of the float's bits above 0xffffffff - i, then a gather
+ * Only integer adds and maxima are atomic: the outputs do not depend on arrival order, tier or launch geometry.
+ * Launches: zero (ws and info), accumulate, finish (one thread per group).  Two accumulate tiers; dfd_group_plan tells which runs.
+ * dfd_group_ws(n, G, J) <= DFD_GROUP_LDS_BYTES: every workgroup accumulates into a private copy of the cells in LDS and adds its
+ * nonzero cells to ws with one global atomic each.  Above: a wave takes 64 consecutive rows, merges each run of equal ids with a
+ * segmented scan over its lanes, and issues one global atomic per cell and run.
+ * ws: dfd_group_ws(n, G, J) = G (8 J + 12) bytes, 8-byte aligned, no initial contents required (0 for arguments out of range).
+ * dfd_group_plan: plan[4] = {tier (DFD_GROUP_TIER_LDS / _GLOBAL), accumulate workgroups, LDS bytes, finish workgroups}.
+ * Arguments out of range, a NULL pointer or a ws too small: DFD_EINVAL, nothing is launched. */
+#define DFD_GROUP_MEAN 0
+#define DFD_GROUP_VOTE 1
+#define DFD_GROUP_MAX 2
+#define DFD_GROUP_MAX_N (1 << 24)
+#define DFD_GROUP_MAX_J 1024
+#define DFD_GROUP_LDS_BYTES 65536
+#define DFD_GROUP_LDS_MAX_BLOCKS 256
+#define DFD_GROUP_GLOBAL_MAX_BLOCKS 2048
+#define DFD_GROUP_TIER_LDS 0
+#define DFD_GROUP_TIER_GLOBAL 1
+size_t dfd_group_ws(int n, int G, int J);
+int dfd_group_plan(int n, int G, int J, int* plan);
+int dfd_group_pool(const float* probs, const int* group, const int64_t* targets, int n, int G, int J, int mode, int positive, void* ws,
+                   size_t ws_bytes, float* out_probs, int64_t* out_preds, int64_t* out_targets, int* sizes, int64_t* info,
                    dfd_stream stream);
 
 /* Input tail on the device (trainers/efficientnet.py:111-234): a uint8 NHWC
