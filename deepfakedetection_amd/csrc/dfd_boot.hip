@@ -5,19 +5,20 @@
 // resample sorts.  Everything is integer counting: the draws add 1 to uint32 counts, the sweep adds the counts up, and the only
 // atomics are integer adds, so every output is independent of arrival order and launch geometry.
 //   LDS tier      k_boot_lds     one workgroup per resample: zero the counts in LDS, draw, class totals, sweep every member
-//   global tier   k_boot_zero    counts uint32 [R][n] in the workspace
+//   global tier   k_count_zero   counts uint32 [R][n] in the workspace
 //                 k_boot_draw    one workgroup per (resample, tile of DFD_BOOT_DRAW_TILE draws): global adds without return
 //                 k_boot_glb     one workgroup per (resample, member): class totals, sweep
 // The sweep walks the sorted order in tiles of BOOT_THREADS x BOOT_PER positions, a thread owning BOOT_PER consecutive ones.  Per tile
-// it needs two block scans: the sum of the weighted positives / negatives before the thread, and the cumulative pair at the last
-// tie-group end before the thread.  Both cumulatives never decrease along the order, so "the last one" is a maximum.  With the pair
-// at a group's two ends the thread adds the group's term of two_u and tests whether the equal-error segment ends there.  P and N do
-// not depend on the member (the labels are shared), so a pass over the counts in sample order supplies them before the sweep, and
-// the sweep is one pass.  The tie-group ends are a comparison of neighbouring scores the sweep has loaded anyway.
+// it needs two of dfd_count.h's block scans: the sum of the weighted positives / negatives before the thread, and the cumulative
+// pair at the last tie-group end before the thread.  Both cumulatives never decrease along the order, so "the last one" is a
+// maximum.  With the pair at a group's two ends the thread adds the group's term of two_u and tests whether the equal-error segment
+// ends there.  P and N do not depend on the member (the labels are shared), so a pass over the counts in sample order supplies them
+// before the sweep, and the sweep is one pass.  The tie-group ends (dfd_count.h's rule, dfd_roc_curve's too) compare neighbouring
+// scores the sweep has loaded anyway.
 // The cluster bootstrap (dfd_boot_stats_grouped) draws G groups instead of n samples: the counts have G entries, and the totals and
 // the sweep read a sample's weight as counts[group[i]] (BootGrouped) where the plain bootstrap reads counts[i] (BootDirect).  The
-// kernels k_boot_lds_g / k_boot_glb_g differ from k_boot_lds / k_boot_glb in that alone; zero and draw run over G unchanged.
-#include "dfd_common.h"
+// kernels are templates on that weight and differ in nothing else; zero and draw run over G unchanged.
+#include "dfd_count.h"
 #include "dfd_philox.h"
 
 #define BOOT_THREADS 1024
@@ -46,58 +47,6 @@ struct BootScratch {
 static_assert(sizeof(BootScratch) <= DFD_BOOT_SCRATCH_BYTES, "the scratch in front of the LDS counts");
 static_assert(DFD_BOOT_SCRATCH_BYTES + 4 * DFD_BOOT_LDS_MAX_N <= 160 * 1024, "one workgroup's LDS");
 static_assert(DFD_BOOT_MAX_N <= (1 << 24), "weighted totals stay below 2^25: int32 scans, two_u below 2^50");
-
-// Exclusive scan of two non-negative ints per thread over the workgroup, by + or by max (identity 0 for both): v becomes the
-// combination over the threads before this one, total over all.  lds holds BOOT_NW * 2 ints; the trailing barrier frees it.
-template <bool MAX>
-static __device__ __forceinline__ void boot_scan2(int (&v)[2], int (&total)[2], int* lds) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int excl[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        int x = v[k];
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(x, d, 64);
-            if (lane >= d) x = MAX ? max(x, y) : x + y;
-        }
-        if (lane == 63) lds[w * 2 + k] = x;
-        const int before = __shfl_up(x, 1, 64);
-        excl[k] = lane ? before : 0;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        int before = 0, all = 0;
-        for (int u = 0; u < BOOT_NW; ++u) {
-            const int s = lds[u * 2 + k];
-            all = MAX ? max(all, s) : all + s;
-            if (u < w) before = MAX ? max(before, s) : before + s;
-        }
-        v[k] = MAX ? max(before, excl[k]) : before + excl[k];
-        total[k] = all;
-    }
-    __syncthreads();
-}
-
-// the sum of two 64-bit words per thread over the workgroup, in every thread
-static __device__ __forceinline__ void boot_reduce2(unsigned long long (&v)[2], unsigned long long* lds) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        unsigned long long x = v[k];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) x += __shfl_down(x, d, 64);
-        if ((threadIdx.x & 63) == 0) lds[(threadIdx.x >> 6) * 2 + k] = x;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        unsigned long long s = 0;
-        for (int u = 0; u < BOOT_NW; ++u) s += lds[u * 2 + k];
-        v[k] = s;
-    }
-    __syncthreads();
-}
 
 // draws 4 q .. 4 q + 3 of resample b: counts[idx] += 1 each (LDS or global, by the address space of `counts`)
 static __device__ __forceinline__ void boot_draw4(uint32_t* counts, int n, uint32_t q, uint32_t b, uint32_t k0, uint32_t k1) {
@@ -137,7 +86,7 @@ static __device__ __forceinline__ void boot_totals(const W c, const unsigned cha
         v[0] += is_positive[i] ? w : (w << 32);
         if (hit && hit[i]) v[1] += w;
     }
-    boot_reduce2(v, sc->red);
+    block_sum<2, BOOT_NW>(v, sc->red);
     P = (int)(v[0] & 0xffffffffull);
     N = (int)(v[0] >> 32);
     hits = (int)v[1];
@@ -173,7 +122,7 @@ static __device__ __forceinline__ void boot_sweep(const W c, const float* __rest
                 const bool ok = (unsigned)idx < (unsigned)n;
                 const int wt = ok ? (int)c(idx) : 0;
                 unsigned fl = ok && is_positive[idx] ? BOOT_F_POS : 0u;
-                if (i == n - 1 || !(s == s_next)) fl |= BOOT_F_END;     // dfd_roc_curve's tie groups: float comparison
+                if (tie_group_ends(s, s_next, i == n - 1)) fl |= BOOT_F_END;
                 if ((double)s >= cut) fl |= BOOT_F_CUT;                 // false for a NaN cut
                 if (fl & BOOT_F_POS) sp += wt; else sn += wt;
                 if (fl & BOOT_F_END) { ep = sp; en = sn; has_end = true; }
@@ -183,10 +132,10 @@ static __device__ __forceinline__ void boot_sweep(const W c, const float* __rest
             }
         }
         int v[2] = {sp, sn}, total[2];
-        boot_scan2<false>(v, total, sc->scan);
+        block_scan_excl<2, BOOT_NW, false>(v, total, sc->scan);
         int p = carry_p + v[0], nn = carry_n + v[1];
         int e[2] = {has_end ? p + ep : 0, has_end ? nn + en : 0}, etotal[2];
-        boot_scan2<true>(e, etotal, sc->scan);
+        block_scan_excl<2, BOOT_NW, true>(e, etotal, sc->scan);
         int bp = max(carry_ep, e[0]), bn = max(carry_en, e[1]);         // the pair at the group end before this thread, or (0, 0)
 #pragma unroll
         for (int j = 0; j < BOOT_PER; ++j) {
@@ -211,7 +160,7 @@ static __device__ __forceinline__ void boot_sweep(const W c, const float* __rest
         carry_en = max(carry_en, etotal[1]);
     }
     unsigned long long r[2] = {two_u, (unsigned long long)tp | ((unsigned long long)fp << 32)};
-    boot_reduce2(r, sc->red);                                           // its barriers also publish eer[]
+    block_sum<2, BOOT_NW>(r, sc->red);                                  // its barriers also publish eer[]
     if (t == 0) {
         out[0] = P; out[1] = N; out[2] = (int64_t)r[0];
         out[3] = (int64_t)(r[1] & 0xffffffffull); out[4] = (int64_t)(r[1] >> 32); out[5] = hits;
@@ -220,29 +169,34 @@ static __device__ __forceinline__ void boot_sweep(const W c, const float* __rest
     __syncthreads();                                                    // eer[] is reset by the next member's sweep
 }
 
+
+// a kernel's weight over the counts c of its resample: BootDirect reads neither group nor G
+template <typename W>
+static __device__ __forceinline__ W boot_weight(const uint32_t* c, const int* group, int G) {
+    if constexpr (std::is_same<W, BootDirect>::value) return {c};
+    else return {c, group, G};
+}
+
+// nc: the counts of a resample, n with W = BootDirect and the G group counts with W = BootGrouped
+template <typename W>
 __global__ void __launch_bounds__(BOOT_THREADS)
-k_boot_lds(BootMembers mem, int M, const unsigned char* __restrict__ is_positive, const unsigned char* __restrict__ hit, int n, int B,
-           uint32_t k0, uint32_t k1, int64_t* __restrict__ stats) {
+k_boot_lds(BootMembers mem, int M, const unsigned char* __restrict__ is_positive, const unsigned char* __restrict__ hit,
+           const int* __restrict__ group, int n, int nc, int B, uint32_t k0, uint32_t k1, int64_t* __restrict__ stats) {
     extern __shared__ __attribute__((aligned(16))) uint32_t boot_lds[];
     BootScratch* sc = reinterpret_cast<BootScratch*>(boot_lds);
     uint32_t* c = boot_lds + DFD_BOOT_SCRATCH_BYTES / 4;
     const int t = threadIdx.x, b = blockIdx.x;
-    for (int i = t; i < n; i += BOOT_THREADS) c[i] = 0;
+    for (int i = t; i < nc; i += BOOT_THREADS) c[i] = 0;
     __syncthreads();
-    const int nq = (n + 3) / 4;
-    for (int q = t; q < nq; q += BOOT_THREADS) boot_draw4(c, n, (uint32_t)q, (uint32_t)b, k0, k1);
+    const int nq = (nc + 3) / 4;
+    for (int q = t; q < nq; q += BOOT_THREADS) boot_draw4(c, nc, (uint32_t)q, (uint32_t)b, k0, k1);
     __syncthreads();
     int P, N, hits;
-    const BootDirect w = {c};
+    const W w = boot_weight<W>(c, group, nc);
     boot_totals(w, is_positive, hit, n, sc, P, N, hits);
     for (int m = 0; m < M; ++m)
         boot_sweep(w, mem.score[m], mem.perm[m], is_positive, mem.cut[m], n, P, N, hits, sc,
                    stats + ((size_t)m * B + b) * DFD_BOOT_STATS_LEN);
-}
-
-__global__ void __launch_bounds__(256)
-k_boot_zero(uint32_t* __restrict__ counts, size_t words) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (size_t)gridDim.x * 256) counts[i] = 0;
 }
 
 // grid (R, tiles): resample b0 + blockIdx.x, draws blockIdx.y * DFD_BOOT_DRAW_TILE ...
@@ -257,49 +211,16 @@ k_boot_draw(uint32_t* __restrict__ counts, int n, int b0, uint32_t k0, uint32_t 
     }
 }
 
-// grid (R, M): resample b0 + blockIdx.x of member blockIdx.y
+// grid (R, M): resample b0 + blockIdx.x of member blockIdx.y, over counts uint32 [R][nc]
+template <typename W>
 __global__ void __launch_bounds__(BOOT_THREADS)
 k_boot_glb(BootMembers mem, const uint32_t* __restrict__ counts, const unsigned char* __restrict__ is_positive,
-           const unsigned char* __restrict__ hit, int n, int B, int b0, int64_t* __restrict__ stats) {
-    __shared__ BootScratch sc;
-    const uint32_t* c = counts + (size_t)blockIdx.x * n;
-    const int m = blockIdx.y, b = b0 + blockIdx.x;
-    int P, N, hits;
-    const BootDirect w = {c};
-    boot_totals(w, is_positive, hit, n, &sc, P, N, hits);
-    boot_sweep(w, mem.score[m], mem.perm[m], is_positive, mem.cut[m], n, P, N, hits, &sc, stats + ((size_t)m * B + b) * DFD_BOOT_STATS_LEN);
-}
-
-// k_boot_lds with the G group counts in LDS: resample b draws G groups
-__global__ void __launch_bounds__(BOOT_THREADS)
-k_boot_lds_g(BootMembers mem, int M, const unsigned char* __restrict__ is_positive, const unsigned char* __restrict__ hit,
-             const int* __restrict__ group, int n, int G, int B, uint32_t k0, uint32_t k1, int64_t* __restrict__ stats) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t boot_lds[];
-    BootScratch* sc = reinterpret_cast<BootScratch*>(boot_lds);
-    uint32_t* c = boot_lds + DFD_BOOT_SCRATCH_BYTES / 4;
-    const int t = threadIdx.x, b = blockIdx.x;
-    for (int i = t; i < G; i += BOOT_THREADS) c[i] = 0;
-    __syncthreads();
-    const int nq = (G + 3) / 4;
-    for (int q = t; q < nq; q += BOOT_THREADS) boot_draw4(c, G, (uint32_t)q, (uint32_t)b, k0, k1);
-    __syncthreads();
-    int P, N, hits;
-    const BootGrouped w = {c, group, G};
-    boot_totals(w, is_positive, hit, n, sc, P, N, hits);
-    for (int m = 0; m < M; ++m)
-        boot_sweep(w, mem.score[m], mem.perm[m], is_positive, mem.cut[m], n, P, N, hits, sc,
-                   stats + ((size_t)m * B + b) * DFD_BOOT_STATS_LEN);
-}
-
-// k_boot_glb over counts uint32 [R][G]
-__global__ void __launch_bounds__(BOOT_THREADS)
-k_boot_glb_g(BootMembers mem, const uint32_t* __restrict__ counts, const unsigned char* __restrict__ is_positive,
-             const unsigned char* __restrict__ hit, const int* __restrict__ group, int n, int G, int B, int b0,
-             int64_t* __restrict__ stats) {
+           const unsigned char* __restrict__ hit, const int* __restrict__ group, int n, int nc, int B, int b0,
+           int64_t* __restrict__ stats) {
     __shared__ BootScratch sc;
     const int m = blockIdx.y, b = b0 + blockIdx.x;
     int P, N, hits;
-    const BootGrouped w = {counts + (size_t)blockIdx.x * G, group, G};
+    const W w = boot_weight<W>(counts + (size_t)blockIdx.x * nc, group, nc);
     boot_totals(w, is_positive, hit, n, &sc, P, N, hits);
     boot_sweep(w, mem.score[m], mem.perm[m], is_positive, mem.cut[m], n, P, N, hits, &sc, stats + ((size_t)m * B + b) * DFD_BOOT_STATS_LEN);
 }
@@ -326,10 +247,7 @@ extern "C" int dfd_boot_plan(int n, int B, int M, size_t ws_bytes, int* plan) {
 }
 
 static void boot_launch_counts(int n, int b0, int R, uint64_t seed, uint32_t* counts, hipStream_t st) {
-    const size_t words = (size_t)R * (size_t)n;
-    size_t blocks = (words + 256 * 16 - 1) / (256 * 16);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_boot_zero, dim3((unsigned)blocks), dim3(256), 0, st, counts, words);
+    count_zero<256>(counts, (size_t)R * (size_t)n, nullptr, 0, st);
     const int tiles = (n + DFD_BOOT_DRAW_TILE - 1) / DFD_BOOT_DRAW_TILE;                               // at most 4096
     hipLaunchKernelGGL(k_boot_draw, dim3(R, tiles), dim3(BOOT_DRAW_THREADS), 0, st, counts, n, b0, (uint32_t)seed,
                        (uint32_t)(seed >> 32));
@@ -343,14 +261,33 @@ extern "C" int dfd_boot_counts(int n, int b0, int R, uint64_t seed, uint32_t* co
     return DFD_CHECK_LAUNCH();
 }
 
-static bool boot_members(const float* const* score_ptrs, const int* const* perm_ptrs, const double* cuts, int M, int n, BootMembers& mem) {
+// The launches of `plan` over resamples of nc counts (n with W = BootDirect, G with BootGrouped), after the caller's own checks
+template <typename W>
+static int boot_run(const int* plan, const float* const* score_ptrs, const int* const* perm_ptrs, int M, const unsigned char* is_positive,
+                    const unsigned char* hit, const double* cuts, const int* group, int n, int nc, int B, uint64_t seed, void* ws,
+                    int64_t* stats, hipStream_t st) {
+    BootMembers mem = {};
     for (int m = 0; m < M; ++m) {
-        if (n > 0 && (!score_ptrs[m] || !perm_ptrs[m])) return false;
+        if (n > 0 && (!score_ptrs[m] || !perm_ptrs[m])) return DFD_EINVAL;
         mem.score[m] = n > 0 ? score_ptrs[m] : nullptr;
         mem.perm[m] = n > 0 ? perm_ptrs[m] : nullptr;
         mem.cut[m] = cuts ? cuts[m] : __builtin_nan("");
     }
-    return true;
+    if (plan[0] == DFD_BOOT_TIER_LDS) {
+        dfd_allow_lds_once<k_boot_lds<W>>(160 * 1024);
+        hipLaunchKernelGGL(k_boot_lds<W>, dim3(B), dim3(BOOT_THREADS), DFD_BOOT_SCRATCH_BYTES + (size_t)nc * sizeof(uint32_t), st, mem, M,
+                           is_positive, hit, group, n, nc, B, (uint32_t)seed, (uint32_t)(seed >> 32), stats);
+        return DFD_CHECK_LAUNCH();
+    }
+    if (!ws) return DFD_EINVAL;
+    const int R = plan[1];
+    for (int b0 = 0; b0 < B; b0 += R) {
+        const int r = B - b0 < R ? B - b0 : R;
+        boot_launch_counts(nc, b0, r, seed, (uint32_t*)ws, st);
+        hipLaunchKernelGGL(k_boot_glb<W>, dim3(r, M), dim3(BOOT_THREADS), 0, st, mem, (const uint32_t*)ws, is_positive, hit, group, n, nc, B,
+                           b0, stats);
+    }
+    return DFD_CHECK_LAUNCH();
 }
 
 extern "C" int dfd_boot_stats(const float* const* score_ptrs, const int* const* perm_ptrs, int M, const unsigned char* is_positive,
@@ -359,23 +296,7 @@ extern "C" int dfd_boot_stats(const float* const* score_ptrs, const int* const* 
     int plan[4];
     if (dfd_boot_plan(n, B, M, ws_bytes, plan) != DFD_OK || !stats) return DFD_EINVAL;
     if (n > 0 && (!score_ptrs || !perm_ptrs || !is_positive)) return DFD_EINVAL;
-    BootMembers mem = {};
-    if (!boot_members(score_ptrs, perm_ptrs, cuts, M, n, mem)) return DFD_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    if (plan[0] == DFD_BOOT_TIER_LDS) {
-        dfd_allow_lds_once<k_boot_lds>(160 * 1024);
-        hipLaunchKernelGGL(k_boot_lds, dim3(B), dim3(BOOT_THREADS), DFD_BOOT_SCRATCH_BYTES + (size_t)n * sizeof(uint32_t), st, mem, M,
-                           is_positive, hit, n, B, (uint32_t)seed, (uint32_t)(seed >> 32), stats);
-        return DFD_CHECK_LAUNCH();
-    }
-    if (!ws) return DFD_EINVAL;
-    const int R = plan[1];
-    for (int b0 = 0; b0 < B; b0 += R) {
-        const int r = B - b0 < R ? B - b0 : R;
-        boot_launch_counts(n, b0, r, seed, (uint32_t*)ws, st);
-        hipLaunchKernelGGL(k_boot_glb, dim3(r, M), dim3(BOOT_THREADS), 0, st, mem, (const uint32_t*)ws, is_positive, hit, n, B, b0, stats);
-    }
-    return DFD_CHECK_LAUNCH();
+    return boot_run<BootDirect>(plan, score_ptrs, perm_ptrs, M, is_positive, hit, cuts, nullptr, n, n, B, seed, ws, stats, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- cluster bootstrap
@@ -400,22 +321,5 @@ extern "C" int dfd_boot_stats_grouped(const float* const* score_ptrs, const int*
     int plan[4];
     if (dfd_boot_plan_grouped(n, G, max_size, B, M, ws_bytes, plan) != DFD_OK || !stats) return DFD_EINVAL;
     if (!score_ptrs || !perm_ptrs || !is_positive || !group) return DFD_EINVAL;
-    BootMembers mem = {};
-    if (!boot_members(score_ptrs, perm_ptrs, cuts, M, n, mem)) return DFD_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    if (plan[0] == DFD_BOOT_TIER_LDS) {
-        dfd_allow_lds_once<k_boot_lds_g>(160 * 1024);
-        hipLaunchKernelGGL(k_boot_lds_g, dim3(B), dim3(BOOT_THREADS), DFD_BOOT_SCRATCH_BYTES + (size_t)G * sizeof(uint32_t), st, mem, M,
-                           is_positive, hit, group, n, G, B, (uint32_t)seed, (uint32_t)(seed >> 32), stats);
-        return DFD_CHECK_LAUNCH();
-    }
-    if (!ws) return DFD_EINVAL;
-    const int R = plan[1];
-    for (int b0 = 0; b0 < B; b0 += R) {
-        const int r = B - b0 < R ? B - b0 : R;
-        boot_launch_counts(G, b0, r, seed, (uint32_t*)ws, st);
-        hipLaunchKernelGGL(k_boot_glb_g, dim3(r, M), dim3(BOOT_THREADS), 0, st, mem, (const uint32_t*)ws, is_positive, hit, group, n, G, B,
-                           b0, stats);
-    }
-    return DFD_CHECK_LAUNCH();
+    return boot_run<BootGrouped>(plan, score_ptrs, perm_ptrs, M, is_positive, hit, cuts, group, n, G, B, seed, ws, stats, (hipStream_t)stream);
 }

@@ -4,14 +4,14 @@
 //
 // Both entry points are two-stage sums over rows (dfd_rowred.h: the row layouts, the launch shape, stage 2, the order of every sum):
 //   dfd_calib_bins       k_rowred_zero   bins[M][3] and stats[4] = 0
-//                        k_calib_bins    stage 1: int32 / 64-bit histogram in LDS per workgroup, flushed with 64-bit integer adds; the
+//                        k_calib_bins    stage 1: int32 / 64-bit histogram in LDS per workgroup, flushed with dfd_count.h's count_add; the
 //                                        workgroup's f64 Brier partial into ws[block]
 //                        k_rowred_sum    stage 2
 //   dfd_calib_nll        k_calib_nll     stage 1: every row is read once and held in registers while the beta loop runs; the
 //                                        workgroup's f64 partials of {nll, g, h} per beta and its two int64 row counts into ws
 //                        k_rowred_sum    stage 2
 // J <= DFD_CALIB_THREAD_MAX_J takes the thread layout, wider rows the wave layout; at most DFD_CALIB_MAX_BLOCKS workgroups.
-#include "dfd_rowred.h"
+#include "dfd_count.h"
 
 #define CALIB_WAVE_COLS (DFD_CALIB_MAX_J / 64)                      // columns a lane holds of the widest row
 static_assert(DFD_CALIB_MAX_J % 64 == 0 && DFD_CALIB_THREAD_MAX_J <= 64, "a lane holds whole column strides");
@@ -102,9 +102,7 @@ k_calib_bins(const float* __restrict__ probs, const int64_t* __restrict__ target
     valid = wave_sum(valid); nonfinite = wave_sum(nonfinite); oob = wave_sum(oob);
     if (lane == 0) {
         red[w] = brier;
-        if (valid) atomicAdd(reinterpret_cast<unsigned long long*>(stats + 0), (unsigned long long)valid);
-        if (nonfinite) atomicAdd(reinterpret_cast<unsigned long long*>(stats + 1), (unsigned long long)nonfinite);
-        if (oob) atomicAdd(reinterpret_cast<unsigned long long*>(stats + 2), (unsigned long long)oob);
+        count_add(stats + 0, valid); count_add(stats + 1, nonfinite); count_add(stats + 2, oob);
     }
     __syncthreads();
     if (t == 0) {
@@ -113,13 +111,11 @@ k_calib_bins(const float* __restrict__ probs, const int64_t* __restrict__ target
         ws[blockIdx.x] = s;
     }
     if (t < M) {
-        const unsigned long long c = cc[t], q = sq[t];
-        if (c & 0xffffffffull) atomicAdd(reinterpret_cast<unsigned long long*>(bins + t * 3 + 0), c & 0xffffffffull);
-        if (c >> 32) {
-            atomicAdd(reinterpret_cast<unsigned long long*>(bins + t * 3 + 1), c >> 32);
-            atomicAdd(reinterpret_cast<unsigned long long*>(stats + 3), c >> 32);
-        }
-        if (q) atomicAdd(reinterpret_cast<unsigned long long*>(bins + t * 3 + 2), q);
+        const unsigned long long c = cc[t];
+        count_add(bins + t * 3 + 0, c & 0xffffffffull);
+        count_add(bins + t * 3 + 1, c >> 32);
+        count_add(stats + 3, c >> 32);
+        count_add(bins + t * 3 + 2, sq[t]);
     }
 }
 

@@ -12,11 +12,11 @@
 //                        k_rowred_sum    stage 2
 //   dfd_fuse_agree       k_rowred_zero   pair, hist and stats = 0
 //                        k_fuse_agree    an LDS histogram of the 2^K right / wrong patterns per workgroup, from which the workgroup
-//                                        adds its share of every table cell with 64-bit integer adds
+//                                        adds its share of every table cell with dfd_count.h's count_add
 // K J <= DFD_FUSE_THREAD_MAX_KJ takes the thread layout (in k_fuse_nll the K rows of a sample are read once into LDS and serve
 // every candidate), wider inputs the wave layout, a lane reading its columns again per candidate; at most DFD_FUSE_MAX_BLOCKS
 // workgroups.
-#include "dfd_rowred.h"
+#include "dfd_count.h"
 
 #define FUSE_K DFD_FUSE_MAX_MODELS
 #define FUSE_TRI (FUSE_K * (FUSE_K + 1) / 2)
@@ -145,14 +145,8 @@ k_fuse_scores(const fuse_ptrs_t zp, int K, int n, int J, const fuse_coef_t coef,
             }
         }
     }
-    nonfinite = wave_sum(nonfinite);
-    if (lane == 0) red[w] = nonfinite;
-    __syncthreads();
-    if (t == 0) {
-        long s = 0;
-        for (int u = 0; u < ROWRED_WAVES; ++u) s += red[u];
-        if (s) atomicAdd(reinterpret_cast<unsigned long long*>(stats), (unsigned long long)s);
-    }
+    nonfinite = block_sum<ROWRED_WAVES>(nonfinite, red);
+    if (t == 0) count_add(stats, nonfinite);
 }
 
 extern "C" int dfd_fuse_plan(int n, int J, int K, int* out) {
@@ -427,7 +421,7 @@ k_fuse_agree(const fuse_ptrs_t pp, const int64_t* __restrict__ targets, int n, i
              int64_t* __restrict__ hist, int64_t* __restrict__ stats) {
     __shared__ unsigned int cnt[1 << FUSE_K];
     __shared__ long red[ROWRED_WAVES];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int t = threadIdx.x;
     cnt[t] = 0;
     __syncthreads();
     long oob = 0;
@@ -440,9 +434,7 @@ k_fuse_agree(const fuse_ptrs_t pp, const int64_t* __restrict__ targets, int n, i
             if (k < K) pattern |= (unsigned int)(((const int64_t*)pp.p[k])[i] == y) << k;
         atomicAdd(&cnt[pattern], 1u);                                       // fewer than 2^32 rows in all (DFD_FUSE_MAX_N)
     }
-    oob = wave_sum(oob);
-    if (lane == 0) red[w] = oob;
-    __syncthreads();
+    oob = block_sum<ROWRED_WAVES>(oob, red);                                // its barriers also publish cnt[]
     const int patterns = 1 << K;
     for (int o = t; o < K * K * 4; o += ROWRED_THREADS) {
         const int q = o & 3, b = (o >> 2) % K, a = (o >> 2) / K;
@@ -450,20 +442,18 @@ k_fuse_agree(const fuse_ptrs_t pp, const int64_t* __restrict__ targets, int n, i
         long s = 0;
         for (int m = 0; m < patterns; ++m)
             if (((m >> a) & 1u) == want_a && ((m >> b) & 1u) == want_b) s += cnt[m];
-        if (s) atomicAdd(reinterpret_cast<unsigned long long*>(pair + o), (unsigned long long)s);
+        count_add(pair + o, s);
     }
     if (t <= K) {
         long s = 0;
         for (int m = 0; m < patterns; ++m)
             if (__popc(m) == t) s += cnt[m];
-        if (s) atomicAdd(reinterpret_cast<unsigned long long*>(hist + t), (unsigned long long)s);
+        count_add(hist + t, s);
     }
     if (t == ROWRED_THREADS - 1) {
-        long valid = 0, bad = 0;
+        long valid = 0;
         for (int m = 0; m < patterns; ++m) valid += cnt[m];
-        for (int u = 0; u < ROWRED_WAVES; ++u) bad += red[u];
-        if (valid) atomicAdd(reinterpret_cast<unsigned long long*>(stats + 0), (unsigned long long)valid);
-        if (bad) atomicAdd(reinterpret_cast<unsigned long long*>(stats + 1), (unsigned long long)bad);
+        count_add(stats + 0, valid); count_add(stats + 1, oob);
     }
 }
 

@@ -3,8 +3,8 @@
 //
 // Everything that is summed is an integer: a probability becomes q = llrint(p 2^32), a vote is 2^32, and the (group, class) cells
 // are uint64 sums; the max mode keeps one uint64 key per group under an integer max.  The only atomics are integer adds and maxima,
-// so every output is independent of arrival order, tier and launch geometry.
-//   k_group_zero     the workspace and info
+// so every output is independent of arrival order, tier and launch geometry (dfd_count.h: the contract, the counter flush, zeroing).
+//   k_count_zero     the workspace and info
 //   k_group_lds      LDS tier: a workgroup accumulates its rows into a private copy of the cells with LDS atomics, then adds its
 //                    nonzero cells to the workspace with one global atomic each
 //   k_group_glb      global tier: a wave takes 64 consecutive rows, merges each run of equal ids with a segmented scan over the
@@ -12,7 +12,7 @@
 //   k_group_finish   one thread per group: the division (or the gather of the winning row), the first arg max, target, size
 // The workspace holds, for G groups of J classes: cells uint64 [G][J] (max mode: the key in cell [g] of the flat array), then
 // uint32 size [G], lo [G] = max over members of J - target, hi [G] = max of target + 1; zero means "no member" in all of them.
-#include "dfd_common.h"
+#include "dfd_count.h"
 
 #define GROUP_THREADS 256
 #define GROUP_ROWS_PER_BLOCK 4096                                       // rows a workgroup takes at least before another one is added
@@ -73,21 +73,8 @@ static __device__ __forceinline__ unsigned long long group_key(float p, int i) {
 }
 
 static __device__ __forceinline__ void group_count_flush(int bad, int oob, int64_t* __restrict__ info) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        bad += __shfl_down(bad, d, 64);
-        oob += __shfl_down(oob, d, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (bad) atomicAdd(reinterpret_cast<unsigned long long*>(info + 0), (unsigned long long)bad);
-        if (oob) atomicAdd(reinterpret_cast<unsigned long long*>(info + 1), (unsigned long long)oob);
-    }
-}
-
-__global__ void __launch_bounds__(GROUP_THREADS)
-k_group_zero(uint32_t* __restrict__ ws, size_t words, int64_t* __restrict__ info) {
-    for (size_t i = (size_t)blockIdx.x * GROUP_THREADS + threadIdx.x; i < words; i += (size_t)gridDim.x * GROUP_THREADS) ws[i] = 0;
-    if (blockIdx.x == 0 && threadIdx.x < 4) info[threadIdx.x] = 0;
+    bad = wave_sum(bad); oob = wave_sum(oob);
+    if ((threadIdx.x & 63) == 0) { count_add(info + 0, bad); count_add(info + 1, oob); }
 }
 
 __global__ void __launch_bounds__(GROUP_THREADS)
@@ -119,7 +106,8 @@ k_group_lds(const float* __restrict__ probs, const int* __restrict__ group, cons
     const size_t cells = mode == DFD_GROUP_MAX ? (size_t)G : (size_t)G * J;
     for (size_t k = threadIdx.x; k < cells; k += GROUP_THREADS) {
         const unsigned long long v = l.cell[k];
-        if (v) { if (mode == DFD_GROUP_MAX) atomicMax(&w.cell[k], v); else atomicAdd(&w.cell[k], v); }
+        if (mode != DFD_GROUP_MAX) count_add(&w.cell[k], v);
+        else if (v) atomicMax(&w.cell[k], v);
     }
     for (int g = threadIdx.x; g < G; g += GROUP_THREADS) {
         const uint32_t s = l.size[g];
@@ -169,7 +157,7 @@ k_group_glb(const float* __restrict__ probs, const int* __restrict__ group, cons
         } else {
             for (int j = 0; j < J; ++j) {
                 const unsigned long long q = group_seg_scan<false>(r.ok ? group_q(row, j, mode, r.am) : 0ull, lane, start);
-                if (issue && q) atomicAdd(&w.cell[(size_t)r.g * J + j], q);
+                if (issue) count_add(&w.cell[(size_t)r.g * J + j], q);
             }
         }
         if (issue) {
@@ -210,10 +198,7 @@ k_group_finish(const float* __restrict__ probs, int G, int J, int mode, const vo
         sizes[g] = (int)size;
     }
     const int n_mixed = __popcll(__ballot(mixed)), n_empty = __popcll(__ballot(live && size == 0));
-    if ((threadIdx.x & 63) == 0) {
-        if (n_mixed) atomicAdd(reinterpret_cast<unsigned long long*>(info + 2), (unsigned long long)n_mixed);
-        if (n_empty) atomicAdd(reinterpret_cast<unsigned long long*>(info + 3), (unsigned long long)n_empty);
-    }
+    if ((threadIdx.x & 63) == 0) { count_add(info + 2, n_mixed); count_add(info + 3, n_empty); }
 }
 
 static bool group_shape_ok(int n, int G, int J) { return G >= 1 && G <= n && n <= DFD_GROUP_MAX_N && J >= 1 && J <= DFD_GROUP_MAX_J; }
@@ -248,10 +233,7 @@ extern "C" int dfd_group_pool(const float* probs, const int* group, const int64_
     const size_t need = dfd_group_ws(n, G, J);
     if (ws_bytes < need || ((uintptr_t)ws & 7)) return DFD_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const size_t words = need / 4;
-    size_t zb = (words + GROUP_THREADS * 16 - 1) / (GROUP_THREADS * 16);
-    if (zb > 4096) zb = 4096;
-    hipLaunchKernelGGL(k_group_zero, dim3((unsigned)zb), dim3(GROUP_THREADS), 0, st, (uint32_t*)ws, words, info);
+    count_zero<GROUP_THREADS>((uint32_t*)ws, need / 4, info, 4, st);
     if (plan[0] == DFD_GROUP_TIER_LDS) {
         dfd_allow_lds_once<k_group_lds>(DFD_GROUP_LDS_BYTES);
         hipLaunchKernelGGL(k_group_lds, dim3(plan[1]), dim3(GROUP_THREADS), (size_t)plan[2], st, probs, group, targets, n, G, J, mode,

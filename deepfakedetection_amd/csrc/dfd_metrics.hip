@@ -1,6 +1,7 @@
 // dfd_metrics.hip — exact evaluation metrics on the device (ABI 146): the ROC curve of sorted scores with its Mann-Whitney rank
 // statistic, a threshold sweep over that curve, and a confusion matrix.  Everything here is integer counting, so every result is
-// exact and independent of the order in which workgroups finish; the only atomics are integer adds.
+// exact and independent of the order in which workgroups finish; the only atomics are integer adds.  The block scan, the workgroup
+// sum, the counter flush and the tie-group rule are dfd_count.h's.
 //
 // No workgroup ever waits for another one: whatever depends on another workgroup's result is a later launch on the same stream.
 //   dfd_roc_curve   k_roc_tile_sums   one workgroup per tile of DFD_ROC_TILE scores: positives, negatives, group ends, non-finite
@@ -13,7 +14,7 @@
 //                   k_confusion_glb   above: one 64-bit add per sample
 // A tile is 256 threads x 8 consecutive scores.  The loads are lane-strided (coalesced); each thread then reads the flag bytes of its
 // own 8 consecutive scores from LDS as one 8-byte word, so the scan runs over 256 thread totals: one wave scan and a 4-entry sum.
-#include "dfd_common.h"
+#include "dfd_count.h"
 
 #define ROC_THREADS 256
 #define ROC_PER_THREAD (DFD_ROC_TILE / ROC_THREADS)
@@ -25,45 +26,14 @@ static_assert(DFD_ROC_SCAN_WIDTH % 64 == 0 && DFD_ROC_SCAN_WIDTH <= 1024, "whole
 #define ROC_F_END 4u
 #define ROC_F_NONFINITE 8u
 
-// Exclusive scan of K ints per thread over a workgroup of NW waves: v becomes the sum over the threads before this one, total the sum
-// over all of them.  lds holds NW * K ints; the trailing barrier lets the caller reuse it at once.
-template <int K, int NW>
-static __device__ __forceinline__ void block_scan_excl(int (&v)[K], int (&total)[K], int* lds) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int incl[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        int x = v[k];
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(x, d, 64);
-            if (lane >= d) x += y;
-        }
-        incl[k] = x;
-        if (lane == 63) lds[w * K + k] = x;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        int before = 0, all = 0;
-        for (int u = 0; u < NW; ++u) {
-            const int s = lds[u * K + k];
-            all += s;
-            if (u < w) before += s;
-        }
-        v[k] = incl[k] - v[k] + before;
-        total[k] = all;
-    }
-    __syncthreads();
-}
-
 // the flags of score i (i < n): which class it counts for, whether its tie group ends with it, whether it is NaN or +-inf
 static __device__ __forceinline__ unsigned roc_flags(const float* __restrict__ score, const int64_t* __restrict__ label, int i, int n,
                                                      int64_t positive) {
     const float s = score[i];
+    const bool last = i == n - 1;
     unsigned f = label[i] == positive ? ROC_F_POS : ROC_F_NEG;
-    if (i == n - 1 || !(s == score[i + 1])) f |= ROC_F_END;             // float comparison: -0.0 == +0.0, NaN ends its own group
-    if ((__float_as_uint(s) & 0x7f800000u) == 0x7f800000u) f |= ROC_F_NONFINITE;
+    if (tie_group_ends(s, last ? 0.f : score[i + 1], last)) f |= ROC_F_END;
+    if (f32_nonfinite(s)) f |= ROC_F_NONFINITE;
     return f;
 }
 
@@ -160,15 +130,8 @@ k_roc_two_u(const int64_t* __restrict__ cum_pos, const int64_t* __restrict__ cum
         const int64_t p0 = g ? cum_pos[g - 1] : 0, n0 = g ? cum_neg[g - 1] : 0;
         acc += (unsigned long long)(cum_pos[g] - p0) * (unsigned long long)(n0 + cum_neg[g]);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_down(acc, d, 64);
-    if ((t & 63) == 0) red[t >> 6] = acc;
-    __syncthreads();
-    if (t == 0) {
-        unsigned long long s = 0;
-        for (int u = 0; u < ROC_THREADS / 64; ++u) s += red[u];
-        if (s) atomicAdd(reinterpret_cast<unsigned long long*>(stats + 4), s);
-    }
+    acc = block_sum<ROC_THREADS / 64>(acc, red);
+    if (t == 0) count_add(stats + 4, acc);
 }
 
 extern "C" size_t dfd_roc_ws(int n) {
@@ -251,12 +214,9 @@ k_confusion_lds(const int64_t* __restrict__ truth, const int64_t* __restrict__ p
         if (a < 0 || a >= J || b < 0 || b >= J) ++bad;
         else atomicAdd(&hist[(int)a * J + (int)b], 1);
     }
-    if (bad) atomicAdd(reinterpret_cast<unsigned long long*>(oob), (unsigned long long)bad);
+    count_add(oob, bad);
     __syncthreads();
-    for (int i = t; i < cells; i += CONF_THREADS) {
-        const int c = hist[i];
-        if (c) atomicAdd(reinterpret_cast<unsigned long long*>(counts + i), (unsigned long long)c);
-    }
+    for (int i = t; i < cells; i += CONF_THREADS) count_add(counts + i, hist[i]);
 }
 
 __global__ void __launch_bounds__(CONF_THREADS)
@@ -266,9 +226,9 @@ k_confusion_glb(const int64_t* __restrict__ truth, const int64_t* __restrict__ p
     for (long i = (long)blockIdx.x * CONF_THREADS + threadIdx.x; i < n; i += (long)gridDim.x * CONF_THREADS) {
         const int64_t a = truth[i], b = pred[i];
         if (a < 0 || a >= J || b < 0 || b >= J) ++bad;
-        else atomicAdd(reinterpret_cast<unsigned long long*>(counts + (long)a * J + b), 1ull);
+        else count_add(counts + (long)a * J + b, 1);
     }
-    if (bad) atomicAdd(reinterpret_cast<unsigned long long*>(oob), (unsigned long long)bad);
+    count_add(oob, bad);
 }
 
 extern "C" int dfd_confusion(const int64_t* truth, const int64_t* pred, int n, int J, int64_t* counts, int64_t* oob, dfd_stream stream) {

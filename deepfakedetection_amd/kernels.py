@@ -1246,6 +1246,35 @@ ROC_MAX_N, ROC_MAX_CUTS, ROC_STATS_LEN = _lib.ROC_MAX_N, _lib.ROC_MAX_CUTS, _lib
 CONFUSION_LDS_MAX_J, CONFUSION_MAX_J = _lib.CONFUSION_LDS_MAX_J, _lib.CONFUSION_MAX_J
 
 
+# What the evaluation front ends (from here to group pooling) share
+def _ws(op: str, ws: torch.Tensor | None, need: int, device, align: int = 1, least: int | None = None) -> torch.Tensor:
+    """The caller's workspace if it is a uint8 tensor of at least `least` bytes (default: `need`) on `device` at an address that
+    is a multiple of `align`, or a new one of `need` bytes rounded up to whole 8-byte words."""
+    if ws is None:
+        return torch.empty((need + 7) // 8, dtype=torch.float64, device=device).view(torch.uint8)
+    least = need if least is None else least
+    if ws.dtype != torch.uint8 or ws.numel() < least or ws.device != device or ws.data_ptr() % align:
+        raise ValueError(f"{op}: ws must be a uint8 tensor of at least {least} bytes on {device}, its address a multiple of {align}")
+    return ws
+
+
+def _plan(cls, name: str, *args):
+    """A four-int planner of the library (host code) -> its answer as `cls`."""
+    out = (ctypes.c_int * 4)()
+    check(getattr(_L(), name)(*map(int, args), out), name, f"args={args}")
+    return cls(*out)
+
+
+def _outs(out, count: int):
+    """The `out=` destinations of a front end with `count` results: the caller's, or None for each."""
+    return out if out is not None else (None,) * count
+
+
+def _ptrs(tensors):
+    """The array of the members' addresses, every one through the gate."""
+    return (ctypes.c_void_p * len(tensors))(*[_p(t) for t in tensors])
+
+
 def roc_ws(n: int) -> int:
     """Bytes of workspace roc_curve needs for n scores."""
     if not 0 <= n <= ROC_MAX_N:
@@ -1261,12 +1290,8 @@ def roc_curve(scores: torch.Tensor, labels: torch.Tensor, positive: int = 1, ws:
     if scores.dim() != 1 or scores.dtype != torch.float32 or labels.shape != scores.shape or labels.dtype != torch.int64:
         raise ValueError("roc_curve: expected f32 [n] scores and int64 [n] labels")
     n, device = scores.numel(), scores.device
-    need = roc_ws(n)
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=device)
-    elif ws.dtype != torch.uint8 or ws.numel() < need or ws.device != device:
-        raise ValueError(f"roc_curve: ws must be a uint8 tensor of at least {need} bytes on {device}")
-    o_thr, o_pos, o_neg, o_stats = out if out is not None else (None, None, None, None)
+    ws = _ws("roc_curve", ws, roc_ws(n), device)
+    o_thr, o_pos, o_neg, o_stats = _outs(out, 4)
     thr = _dst(o_thr, (n,), device)
     cum_pos = _dst(o_pos, (n,), device, torch.int64)
     cum_neg = _dst(o_neg, (n,), device, torch.int64)
@@ -1285,7 +1310,7 @@ def roc_sweep(thr: torch.Tensor, cum_pos: torch.Tensor, cum_neg: torch.Tensor, s
             or cum_pos.numel() != thr.numel() or cum_neg.numel() != thr.numel() or stats.numel() != ROC_STATS_LEN:
         raise ValueError("roc_sweep: expected roc_curve's (thr, cum_pos, cum_neg, stats)")
     T, device = cuts.numel(), cuts.device
-    o_tp, o_fp = out if out is not None else (None, None)
+    o_tp, o_fp = _outs(out, 2)
     tp = _dst(o_tp, (T,), device, torch.int64)
     fp = _dst(o_fp, (T,), device, torch.int64)
     check(_L().dfd_roc_sweep(_p(thr), _p(cum_pos), _p(cum_neg), _p(stats), thr.numel(), _p(cuts), T, _p(tp), _p(fp), _stream()),
@@ -1305,7 +1330,7 @@ def confusion_counts(truth: torch.Tensor, pred: torch.Tensor, num_classes: int, 
     n, device = truth.numel(), truth.device
     if n >= 1 << 31:
         raise ValueError("confusion_counts: at most 2^31 - 1 samples")
-    o_counts, o_oob = out if out is not None else (None, None)
+    o_counts, o_oob = _outs(out, 2)
     counts = _dst(o_counts, (J, J), device, torch.int64)
     oob = _dst(o_oob, (1,), device, torch.int64)
     check(_L().dfd_confusion(_p(truth), _p(pred), n, J, _p(counts), _p(oob), _stream()), "dfd_confusion", f"n={n} J={J}")
@@ -1330,15 +1355,6 @@ class RowPlan:
 
 
 CalibPlan = FusePlan = RowPlan
-
-
-def _f64_ws(op: str, ws: torch.Tensor | None, need: int, device) -> torch.Tensor:
-    """The caller's workspace if it is an 8-byte aligned uint8 tensor of `need` bytes (it holds f64 and int64 partials), or a new one."""
-    if ws is None:
-        return torch.empty(max(need // 8, 1), dtype=torch.float64, device=device).view(torch.uint8)
-    if ws.dtype != torch.uint8 or ws.numel() < need or ws.device != device or ws.data_ptr() % 8:
-        raise ValueError(f"{op}: ws must be an 8-byte aligned uint8 tensor of at least {need} bytes on {device}")
-    return ws
 
 
 def _calib_shape(op: str, n: int, J: int, K: int | None = None) -> None:
@@ -1370,9 +1386,7 @@ def calib_nll_ws(n: int, J: int, K: int) -> int:
 
 def calib_plan(n: int, J: int) -> RowPlan:
     """Which layout and launch shape calib_bins / calib_nll use for n rows of J classes (host code)."""
-    out = (ctypes.c_int * 4)()
-    check(_L().dfd_calib_plan(int(n), int(J), out), "dfd_calib_plan", f"n={n} J={J}")
-    return RowPlan(*out)
+    return _plan(RowPlan, "dfd_calib_plan", n, J)
 
 
 def calib_bins(probs: torch.Tensor, targets: torch.Tensor, bins: int = 15, ws: torch.Tensor | None = None, out=None):
@@ -1384,8 +1398,8 @@ def calib_bins(probs: torch.Tensor, targets: torch.Tensor, bins: int = 15, ws: t
     if not 1 <= M <= CALIB_MAX_BINS:
         raise ValueError(f"calib_bins: bins must be 1..{CALIB_MAX_BINS}, got {M}")
     device = probs.device
-    ws = _f64_ws("calib_bins", ws, calib_bins_ws(n, J), device)
-    o_bins, o_stats, o_brier = out if out is not None else (None, None, None)
+    ws = _ws("calib_bins", ws, calib_bins_ws(n, J), device, align=8)          # f64 partials
+    o_bins, o_stats, o_brier = _outs(out, 3)
     table = _dst(o_bins, (M, 3), device, torch.int64)
     stats = _dst(o_stats, (4,), device, torch.int64)
     brier = _dst(o_brier, (1,), device, torch.float64)
@@ -1405,8 +1419,8 @@ def calib_nll(logits: torch.Tensor, targets: torch.Tensor, betas, ws: torch.Tens
     if not 1 <= K <= CALIB_MAX_BETAS or not all(math.isfinite(b) and b > 0.0 for b in values):
         raise ValueError(f"calib_nll: expected 1..{CALIB_MAX_BETAS} finite betas > 0, got {values}")
     device = logits.device
-    ws = _f64_ws("calib_nll", ws, calib_nll_ws(n, J, K), device)
-    o_out, o_stats = out if out is not None else (None, None)
+    ws = _ws("calib_nll", ws, calib_nll_ws(n, J, K), device, align=8)         # f64 and int64 partials
+    o_out, o_stats = _outs(out, 2)
     sums = _dst(o_out, (K, 3), device, torch.float64)
     stats = _dst(o_stats, (2,), device, torch.int64)
     check(_L().dfd_calib_nll(_p(logits), _p(targets), n, J, (ctypes.c_double * K)(*values), K, _p(ws), ws.numel(), _p(sums), _p(stats),
@@ -1457,7 +1471,7 @@ def _fuse_members(op: str, members, dtype: torch.dtype, dim: int):
             raise ValueError(f"{op}: every member must be {dtype} with {dim} dimensions, one shape and one device, got "
                              f"{[(m.dtype, tuple(m.shape)) for m in members]}")
     _fuse_shape(op, first.shape[0], first.shape[1] if dim == 2 else 1, K)
-    return members, (ctypes.c_void_p * K)(*[_p(m) for m in members])
+    return members, _ptrs(members)
 
 
 def _fuse_targets(op: str, targets: torch.Tensor, n: int) -> None:
@@ -1467,9 +1481,7 @@ def _fuse_targets(op: str, targets: torch.Tensor, n: int) -> None:
 
 def fuse_plan(n: int, J: int, K: int) -> RowPlan:
     """Which layout and launch shape fuse_scores / fuse_nll use for n rows of J classes from K members (host code)."""
-    out = (ctypes.c_int * 4)()
-    check(_L().dfd_fuse_plan(int(n), int(J), int(K), out), "dfd_fuse_plan", f"n={n} J={J} K={K}")
-    return RowPlan(*out)
+    return _plan(RowPlan, "dfd_fuse_plan", n, J, K)
 
 
 def fuse_nll_ws(n: int, J: int, K: int, C: int) -> int:
@@ -1494,7 +1506,7 @@ def fuse_scores(logits_list, coef, mode: int = FUSE_LOGIT, beta=None, want_probs
     if mode == FUSE_PROB and (min(values) < 0.0 or abs(math.fsum(values) - 1.0) > 1e-12 or min(betas) <= 0.0):
         raise ValueError(f"fuse_scores: the probability pool takes coefficients >= 0 that sum to 1 and betas > 0, got {values}, {betas}")
     device = members[0].device
-    o_probs, o_preds, o_logits, o_stats = out if out is not None else (None, None, None, None)
+    o_probs, o_preds, o_logits, o_stats = _outs(out, 4)
     probs = _dst(o_probs, (n, J), device) if want_probs or o_probs is not None else None
     fused = _dst(o_logits, (n, J), device) if want_logits or o_logits is not None else None
     preds = _dst(o_preds, (n,), device, torch.int64)
@@ -1518,8 +1530,8 @@ def fuse_nll(logits_list, targets: torch.Tensor, cands, ws: torch.Tensor | None 
     if not 1 <= C <= FUSE_MAX_CANDS or any(len(r) != K or not all(math.isfinite(v) for v in r) for r in rows):
         raise ValueError(f"fuse_nll: expected 1..{FUSE_MAX_CANDS} candidates of {K} finite coefficients, got {rows}")
     device = members[0].device
-    ws = _f64_ws("fuse_nll", ws, fuse_nll_ws(n, J, K, C), device)
-    o_out, o_stats = out if out is not None else (None, None)
+    ws = _ws("fuse_nll", ws, fuse_nll_ws(n, J, K, C), device, align=8)        # f64 and int64 partials
+    o_out, o_stats = _outs(out, 2)
     sums = _dst(o_out, (C, fuse_terms(K)), device, torch.float64)
     stats = _dst(o_stats, (2,), device, torch.int64)
     flat = [v for r in rows for v in r]
@@ -1537,7 +1549,7 @@ def fuse_agree(preds_list, targets: torch.Tensor, num_classes: int, out=None):
     _fuse_targets("fuse_agree", targets, n)
     _fuse_shape("fuse_agree", n, J, K)
     device = members[0].device
-    o_pair, o_hist, o_stats = out if out is not None else (None, None, None)
+    o_pair, o_hist, o_stats = _outs(out, 3)
     pair = _dst(o_pair, (K, K, 4), device, torch.int64)
     hist = _dst(o_hist, (K + 1,), device, torch.int64)
     stats = _dst(o_stats, (2,), device, torch.int64)
@@ -1587,15 +1599,14 @@ def boot_plan(n: int, B: int, M: int = 1, ws_bytes: int | None = None) -> BootPl
     allocates by itself), and in how many passes (host code)."""
     _boot_shape("boot_plan", n, B, M)
     if ws_bytes is None:
-        ws_bytes = _boot_default_ws(n, B)
-    out = (ctypes.c_int * 4)()
-    check(_L().dfd_boot_plan(int(n), int(B), int(M), int(ws_bytes), out), "dfd_boot_plan", f"n={n} B={B} M={M} ws={ws_bytes}")
-    return BootPlan(*out)
+        ws_bytes = _boot_default_ws(boot_ws(n, B), n)
+    return _plan(BootPlan, "dfd_boot_plan", n, B, M, ws_bytes)
 
 
-def _boot_default_ws(n: int, B: int) -> int:
-    need = boot_ws(n, B)
-    return need if need <= BOOT_WS_CAP else max(BOOT_WS_CAP // (4 * n), 1) * 4 * n
+def _boot_default_ws(need: int, count: int) -> int:
+    """The workspace boot_stats takes by itself when one pass needs `need` bytes for `count` counts per resample: all of it, or
+    the whole resamples that fit in BOOT_WS_CAP."""
+    return need if need <= BOOT_WS_CAP else max(BOOT_WS_CAP // (4 * count), 1) * 4 * count
 
 
 def boot_counts(n: int, b0: int, R: int, seed: int, device, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -1636,20 +1647,28 @@ def boot_stats(sorted_scores, perms, is_positive: torch.Tensor, replicates: int,
     optionally uint8 [n] hit) in sample order -> int64 [M, B, BOOT_STATS_LEN] = P, N, two_u, tp, fp, hits, f0, t0, f1, t1 of
     every bootstrap resample (include/dfd_hip.h).  cuts: one float or None per member (None: no cut).  `ws`: uint8 scratch for the
     global tier, at least 4 n bytes (one resample per pass); by default boot_ws(n, B) bytes capped at BOOT_WS_CAP.  No host sync."""
-    members, perm_list, values = _boot_inputs("boot_stats", sorted_scores, perms, is_positive, hit, cuts)
+    return _boot_stats("boot_stats", sorted_scores, perms, is_positive, replicates, seed, cuts, hit, ws, out)
+
+
+def _boot_stats(op: str, sorted_scores, perms, is_positive, replicates, seed, cuts, hit, ws, out, grouped=None):
+    """The body of boot_stats (a resample holds n counts) and of boot_stats_grouped (grouped = (groups, G, max_size): G counts)."""
+    groups, G, max_size = grouped or (None, 0, 0)
+    members, perm_list, values = _boot_inputs(op, sorted_scores, perms, is_positive, hit, cuts, groups)
     M, B, n, device = len(members), int(replicates), members[0].numel(), members[0].device
-    _boot_shape("boot_stats", n, B, M)
-    seed = _boot_seed("boot_stats", seed)
-    if ws is None:
-        ws = torch.empty(_boot_default_ws(n, B), dtype=torch.uint8, device=device)
-    elif ws.dtype != torch.uint8 or ws.device != device or (n > BOOT_LDS_MAX_N and ws.numel() < 4 * n):
-        raise ValueError(f"boot_stats: ws must be a uint8 tensor of at least {4 * n} bytes on {device}")
+    if grouped is None:
+        _boot_shape(op, n, B, M)
+        count, need = n, boot_ws(n, B)
+    else:
+        _boot_grouped_shape(op, n, G, max_size, B, M)
+        count, need = G, boot_ws_grouped(n, G, B)
+    seed = _boot_seed(op, seed)
+    # only the global tier reads the workspace: one resample's counts at least
+    ws = _ws(op, ws, _boot_default_ws(need, count), device, least=4 * count if count > BOOT_LDS_MAX_N else 0)
     stats = _dst(out, (M, B, BOOT_STATS_LEN), device, torch.int64)
-    score_ptrs = (ctypes.c_void_p * M)(*[_p(t) for t in members])
-    perm_ptrs = (ctypes.c_void_p * M)(*[_p(t) for t in perm_list])
-    check(_L().dfd_boot_stats(score_ptrs, perm_ptrs, M, _p(is_positive), _p(hit), (ctypes.c_double * M)(*values), n, B,
-                              seed, _p(ws) if ws.numel() else None, ws.numel(), _p(stats), _stream()),
-          "dfd_boot_stats", f"n={n} B={B} M={M}")
+    shape = (n,) if grouped is None else (_p(groups), n, G, max_size)
+    check(getattr(_L(), "dfd_" + op)(_ptrs(members), _ptrs(perm_list), M, _p(is_positive), _p(hit), (ctypes.c_double * M)(*values),
+                                     *shape, B, seed, _p(ws) if ws.numel() else None, ws.numel(), _p(stats), _stream()),
+          "dfd_" + op, f"n={n} B={B} M={M}" + (f" G={G} max_size={max_size}" if grouped else ""))
     return stats
 
 
@@ -1670,21 +1689,13 @@ def boot_ws_grouped(n: int, num_groups: int, B: int) -> int:
     return _L().dfd_boot_ws_grouped(int(n), int(num_groups), int(B))
 
 
-def _boot_grouped_default_ws(n: int, G: int, B: int) -> int:
-    need = boot_ws_grouped(n, G, B)
-    return need if need <= BOOT_WS_CAP else max(BOOT_WS_CAP // (4 * G), 1) * 4 * G
-
-
 def boot_plan_grouped(n: int, num_groups: int, max_size: int, B: int, M: int = 1, ws_bytes: int | None = None) -> BootPlan:
     """boot_plan of the cluster bootstrap: the tier boundary is on num_groups (host code)."""
     n, G, max_size = int(n), int(num_groups), int(max_size)
     _boot_grouped_shape("boot_plan_grouped", n, G, max_size, B, M)
     if ws_bytes is None:
-        ws_bytes = _boot_grouped_default_ws(n, G, B)
-    out = (ctypes.c_int * 4)()
-    check(_L().dfd_boot_plan_grouped(n, G, max_size, int(B), int(M), int(ws_bytes), out), "dfd_boot_plan_grouped",
-          f"n={n} G={G} max_size={max_size} B={B} M={M} ws={ws_bytes}")
-    return BootPlan(*out)
+        ws_bytes = _boot_default_ws(boot_ws_grouped(n, G, B), G)
+    return _plan(BootPlan, "dfd_boot_plan_grouped", n, G, max_size, B, M, ws_bytes)
 
 
 def boot_stats_grouped(sorted_scores, perms, is_positive: torch.Tensor, groups: torch.Tensor, num_groups: int, max_size: int,
@@ -1694,21 +1705,8 @@ def boot_stats_grouped(sorted_scores, perms, is_positive: torch.Tensor, groups: 
     often as its group groups[i] (int32 [n], sample order; an id outside [0, num_groups) counts for nothing) was drawn.  max_size:
     the caller's bound on the largest group; num_groups * max_size <= BOOT_GROUPED_MAX_WEIGHT.  `ws`: uint8 scratch for the global
     tier (num_groups > BOOT_LDS_MAX_N), at least 4 num_groups bytes.  No host sync."""
-    members, perm_list, values = _boot_inputs("boot_stats_grouped", sorted_scores, perms, is_positive, hit, cuts, groups)
-    M, B, G, max_size, n, device = len(members), int(replicates), int(num_groups), int(max_size), members[0].numel(), members[0].device
-    _boot_grouped_shape("boot_stats_grouped", n, G, max_size, B, M)
-    seed = _boot_seed("boot_stats_grouped", seed)
-    if ws is None:
-        ws = torch.empty(_boot_grouped_default_ws(n, G, B), dtype=torch.uint8, device=device)
-    elif ws.dtype != torch.uint8 or ws.device != device or (G > BOOT_LDS_MAX_N and ws.numel() < 4 * G):
-        raise ValueError(f"boot_stats_grouped: ws must be a uint8 tensor of at least {4 * G} bytes on {device}")
-    stats = _dst(out, (M, B, BOOT_STATS_LEN), device, torch.int64)
-    score_ptrs = (ctypes.c_void_p * M)(*[_p(t) for t in members])
-    perm_ptrs = (ctypes.c_void_p * M)(*[_p(t) for t in perm_list])
-    check(_L().dfd_boot_stats_grouped(score_ptrs, perm_ptrs, M, _p(is_positive), _p(hit), (ctypes.c_double * M)(*values), _p(groups), n, G,
-                                      max_size, B, seed, _p(ws) if ws.numel() else None, ws.numel(), _p(stats), _stream()),
-          "dfd_boot_stats_grouped", f"n={n} G={G} max_size={max_size} B={B} M={M}")
-    return stats
+    return _boot_stats("boot_stats_grouped", sorted_scores, perms, is_positive, replicates, seed, cuts, hit, ws, out,
+                       (groups, int(num_groups), int(max_size)))
 
 
 # ------------------------------------------------------------------ group pooling (ABI 154, csrc/dfd_group.hip)
@@ -1743,9 +1741,7 @@ def group_ws(n: int, num_groups: int, J: int) -> int:
 def group_plan(n: int, num_groups: int, J: int) -> GroupPlan:
     """Which tier group_pool runs for n rows of J classes in num_groups groups, and its launch shape (host code)."""
     _group_shape("group_plan", n, num_groups, J)
-    out = (ctypes.c_int * 4)()
-    check(_L().dfd_group_plan(int(n), int(num_groups), int(J), out), "dfd_group_plan", f"n={n} G={num_groups} J={J}")
-    return GroupPlan(*out)
+    return _plan(GroupPlan, "dfd_group_plan", n, num_groups, J)
 
 
 def group_pool(probs: torch.Tensor, groups: torch.Tensor, targets: torch.Tensor, num_groups: int, mode: int = GROUP_MEAN,
@@ -1765,10 +1761,8 @@ def group_pool(probs: torch.Tensor, groups: torch.Tensor, targets: torch.Tensor,
     if mode not in (GROUP_MEAN, GROUP_VOTE, GROUP_MAX) or not 0 <= positive < J:
         raise ValueError(f"group_pool: mode must be 0..2 and positive a class below {J}, got {mode}, {positive}")
     device = probs.device
-    need = group_ws(n, G, J)                                            # G (8 J + 12): not always a multiple of 8
-    ws = _f64_ws("group_pool", ws, need, device) if ws is not None else \
-        torch.empty((need + 7) // 8, dtype=torch.float64, device=device).view(torch.uint8)
-    o = out if out is not None else (None,) * 5
+    ws = _ws("group_pool", ws, group_ws(n, G, J), device, align=8)      # uint64 cells
+    o = _outs(out, 5)
     pooled = _dst(o[0], (G, J), device)
     preds = _dst(o[1], (G,), device, torch.int64)
     tgt = _dst(o[2], (G,), device, torch.int64)
